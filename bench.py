@@ -17,7 +17,9 @@ headline.  Multi-GPU: every rank owns an independent batch (weak scaling, no
 data-path collective); weights are broadcast once from rank 0 over RCCL.
 `roofline.mean_sclk_mhz` / `mean_power_w` are sampled while the timed steps run
 (a slow box — lower clock at the socket power cap — reads differently from a
-regression).
+regression).  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy (inputs and weights are seeded: two builds can be compared
+output for output).
 
 Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (conv
 engine), `cpu_baseline` (the oracle timed on the host cores) and — at N=1 —
@@ -84,7 +86,15 @@ def parse():
                     help="write the per-launch table of the roofline passes (label, us, TFLOP/s, algorithmic GB/s) to this file")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration")
     ap.add_argument("--no-telemetry", action="store_true", help="do not sample clock / power beside the timed regions")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (detections, crops, ok flags; label maps / class counts "
+                         "of the full workload) to DIR/<name>.npy, float32 or float64, at most 64 MB in all (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 class Telemetry:
@@ -232,7 +242,7 @@ class Pipeline:
         self.images = torch.randint(0, 256, (batch, size, size, 3), generator=g, dtype=torch.uint8).to(dev)
         self.face_total = torch.zeros((), dtype=torch.int64, device=dev)
         self.enhanced_total = 0
-        self.enh = self.par = None
+        self.enh = self.par = self.parsed = None
         if full:
             from face_crop_plus_amd.rrdb import RRDBNet
             from face_crop_plus_amd.bise import BiSeNet
@@ -270,7 +280,7 @@ class Pipeline:
                                                  valid_total=self.face_total if count else None)
         if self.par is not None:
             with trace.range("fcp:parse"):
-                self.par.parse(crops)                    # label maps + class histograms stay on the device
+                self.parsed = self.par.parse(crops)      # label maps + class histograms stay on the device
         self.last = (res, crops, ok)
         return crops
 
@@ -396,6 +406,53 @@ def time_pipeline(p: Pipeline, steps, warmup, autotune=True, dist=None, live_eve
         telemetry.__exit__()
         p.telemetry = telemetry.summary(t0, t1)
     return t1 - t0, p.face_total.clone()
+
+
+DUMP_LIMIT_BYTES = 64 << 20         # --dump-outputs: payload of all .npy files together
+
+
+def step_outputs(p: Pipeline):
+    """Host copies of what the last step handed its caller, live faces only (rows before face_offset[-1]): the detections
+    (landmarks, image index per face, per-image face offsets), the crops with their ok flags and, when the workload parses,
+    BiSeNet's label maps and class counts.  Must run before anything else launches on those buffers (the roofline / HBM
+    passes rewrite them; a captured graph owns them)."""
+    res, crops, ok = p.last
+    nf = int(res["face_offset"][-1].item())
+    out = {"face_offset": res["face_offset"], "img_idx": res["img_idx"][:nf], "landmarks": res["landmarks"][:nf],
+           "crops": crops[:nf], "ok": ok[:nf]}
+    if p.parsed is not None:
+        labels, counts = p.parsed
+        out.update(labels=labels[:nf], class_counts=counts[:nf])
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def write_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """`arrays` (from step_outputs) -> out_dir/<name>.npy: uint8 / float sources as float32, integer sources as float64 (both
+    exact).  Above `limit` bytes in all, every per-face array keeps the same fixed, seeded sample of faces (one face count ->
+    one set of rows), and the sampled row numbers go to face_sample.npy.  Returns {name: shape} of what was written."""
+    def cast(a):
+        return a.astype(np.float32 if a.dtype == np.uint8 or (a.dtype.kind == "f" and a.itemsize <= 4) else np.float64)
+
+    arrays = {k: cast(v) for k, v in arrays.items()}
+    whole = {k: v for k, v in arrays.items() if k == "face_offset"}
+    per_face = {k: v for k, v in arrays.items() if k not in whole}
+    nf = next(iter(per_face.values())).shape[0] if per_face else 0
+    row = sum(v[0].nbytes for v in per_face.values()) if nf else 0
+    fixed = sum(v.nbytes for v in whole.values()) + 128 * (len(arrays) + 1)          # + one .npy header per file
+    os.makedirs(out_dir, exist_ok=True)
+    sample = os.path.join(out_dir, "face_sample.npy")
+    if nf and fixed + nf * row > limit:
+        keep = max(0, (limit - fixed) // (row + 8))
+        rows = np.sort(np.random.default_rng(seed).choice(nf, keep, replace=False))
+        per_face = {k: v[rows] for k, v in per_face.items()}
+        whole["face_sample"] = rows.astype(np.float64)
+    elif os.path.exists(sample):
+        os.remove(sample)                                # left by an earlier run into the same directory
+    written = {}
+    for k, v in {**whole, **per_face}.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+        written[k] = list(v.shape)
+    return written
 
 
 def _pmc_traffic(key, launches=None):
@@ -714,6 +771,9 @@ def main():
     elapsed, faces = time_pipeline(p, args.steps, args.warmup, autotune=not args.no_autotune, dist=dist, live_events=live,
                                    telemetry=tele)
     last_timed = p.last                            # outputs of the LAST TIMED step (the roofline passes below overwrite p.last)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = {"dir": args.dump_outputs, "arrays": write_outputs(step_outputs(p), args.dump_outputs)}
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -763,6 +823,8 @@ def main():
             "roofline": roofline, "hbm_kernels": hbm_kernels, "cpu_baseline": cpu_baseline,
             "parity_check": parity_check,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if broadcast is not None:
             line["weight_broadcast"] = broadcast
             line["config"]["broadcast_bytes"], line["config"]["broadcast_ms"] = broadcast["bytes"], broadcast["ms"]

@@ -179,3 +179,69 @@ def test_telemetry_samples_a_window_and_lands_in_the_roofline_record():
     assert dead.summary()["mean_sclk_mhz"] is None and dead.summary()["samples"] == 0
     real = bench.Telemetry(0)                                  # this container has no GPU: must degrade, not raise
     assert real.source is None or isinstance(real.source, str)
+
+
+def _fake_last_step(nf=3, cap=5, out=16, parsed=True):
+    """Pipeline stand-in holding what Pipeline.step leaves in `last` / `parsed`: `nf` live faces in `cap` rows."""
+    import types
+    g = torch.Generator().manual_seed(5)
+    res = {"face_offset": torch.tensor([0, 2, 2, nf], dtype=torch.int32), "img_idx": torch.tensor([0, 0, 2, 0, 0], dtype=torch.int32)[:cap],
+           "landmarks": torch.rand((cap, 5, 2), generator=g) * 300}
+    crops = torch.randint(0, 256, (cap, out, out, 3), generator=g, dtype=torch.uint8)
+    ok = torch.tensor([1, 0, 1, 0, 0], dtype=torch.int32)[:cap]
+    p = types.SimpleNamespace(last=(res, crops, ok), parsed=None)
+    if parsed:
+        p.parsed = (torch.randint(0, 19, (cap, out, out), generator=g, dtype=torch.uint8),
+                    torch.randint(0, out * out, (cap, 19), generator=g, dtype=torch.int32))
+    return p
+
+
+def test_dump_outputs_writes_the_live_rows_of_the_last_step_as_float_arrays(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    p = _fake_last_step()
+    res, crops, ok = p.last
+    written = bench.write_outputs(bench.step_outputs(p), str(tmp_path))
+    names = {"face_offset", "img_idx", "landmarks", "crops", "ok", "labels", "class_counts"}
+    assert set(written) == names and {f.name for f in tmp_path.iterdir()} == {n + ".npy" for n in names}
+    want = {"face_offset": res["face_offset"], "img_idx": res["img_idx"][:3], "landmarks": res["landmarks"][:3], "crops": crops[:3],
+            "ok": ok[:3], "labels": p.parsed[0][:3], "class_counts": p.parsed[1][:3]}
+    for k, v in want.items():
+        a = np.load(tmp_path / (k + ".npy"))
+        assert a.dtype == (np.float64 if v.dtype == torch.int32 else np.float32), k
+        assert written[k] == list(v.shape) and np.array_equal(a, v.numpy()), k            # exact: no value is rounded
+    # the detect-only workload has no parse outputs
+    assert set(bench.write_outputs(bench.step_outputs(_fake_last_step(parsed=False)), str(tmp_path / "d"))) == names - {"labels", "class_counts"}
+
+
+def test_dump_outputs_keeps_a_fixed_seeded_face_sample_under_the_size_limit(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {"face_offset": np.array([0, 40, 70], np.int32), "img_idx": np.repeat(np.int32([0, 1]), [40, 30]),
+              "crops": np.random.default_rng(1).integers(0, 256, (70, 32, 32, 3), dtype=np.uint8)}
+    limit = 20 * 32 * 32 * 3 * 4 + 4096                                          # room for ~20 of the 70 faces
+    a, b = tmp_path / "a", tmp_path / "b"
+    wa = bench.write_outputs(arrays, str(a), limit=limit)
+    wb = bench.write_outputs(arrays, str(b), limit=limit)
+    assert wa == wb and 0 < wa["crops"][0] < 70 and wa["img_idx"] == [wa["crops"][0]]
+    assert sum(f.stat().st_size for f in a.iterdir()) <= limit
+    rows = np.load(a / "face_sample.npy")
+    assert np.array_equal(rows, np.load(b / "face_sample.npy")) and np.all(np.diff(rows) > 0)
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(a / "crops.npy"), arrays["crops"][r]) and np.array_equal(np.load(a / "img_idx.npy"), arrays["img_idx"][r])
+    assert np.array_equal(np.load(a / "face_offset.npy"), arrays["face_offset"])         # not per face: kept whole
+    # a later run that fits into the same directory leaves no stale sample behind
+    bench.write_outputs(arrays, str(a))
+    assert not (a / "face_sample.npy").exists() and np.load(a / "crops.npy").shape[0] == 70
+
+
+def test_steps_and_warmup_are_checked(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 0 and args.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *bad])
+        with pytest.raises(SystemExit):
+            bench.parse()

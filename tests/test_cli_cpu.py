@@ -65,7 +65,7 @@ def test_host_utils(tmp_path):
     assert lm.shape == (2, 5, 2) and fn.tolist() == ["a.png", "b.png"]
 
 
-def test_clean_names(tmp_path):
+def test_clean_names(tmp_path, monkeypatch):
     """utils.clean_names (reference utils.py:344-453): transliteration, excluded characters, truncation,
     case-insensitive de-duplication; copy mode and in-place mode."""
     from face_crop_plus_amd import utils
@@ -74,6 +74,12 @@ def test_clean_names(tmp_path):
     names = ["České.jpg", "a?b#c.d.png", "dup.jpg", "DUP.jpg", "dup-1.jpg", "plain.png", "x" * 80 + ".jpg"]
     for i, n in enumerate(names):
         (src / n).write_bytes(bytes([i]))
+    # de-duplication suffixes depend on the iteration order, which is the file system's: list `src` in creation order.
+    # (Like the reference, in-place mode renames over a name that is still to come in some orders, e.g. DUP.jpg, dup.jpg,
+    # dup-1.jpg: dup.jpg -> dup-1.jpg replaces the original dup-1.jpg.)
+    real_listdir, order = os.listdir, {n: i for i, n in enumerate(names)}
+    monkeypatch.setattr(os, "listdir", lambda d: sorted(real_listdir(d), key=lambda n: order.get(n, len(order)))
+                        if os.path.abspath(d) == str(src) else real_listdir(d))
     out = tmp_path / "out"
     utils.clean_names(str(src), str(out), desc=None)
     got = sorted(os.listdir(out))
@@ -88,3 +94,4 @@ def test_clean_names(tmp_path):
         utils.clean_names(str(src), None, max_chars=len(str(src)) + 3, desc=None)
     utils.clean_names(str(src), None, desc=None)                                         # in place
     assert sorted(os.listdir(src)) == got
+    assert all((src / g).read_bytes() == (out / g).read_bytes() for g in got)           # each file under the same new name
