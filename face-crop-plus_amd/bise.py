@@ -13,7 +13,6 @@ the device.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -40,8 +39,6 @@ class BiSeNet:
         self.device = None
         self._p = None
         self.precision = 0
-        # fp16x3 path: conv1 + bn1 + relu + maxpool of the ResNet-18 stem in one launch (A/B switch: FCP_BISE_FUSED_STEM=0)
-        self.fused_stem = os.environ.get("FCP_BISE_FUSED_STEM", "1") != "0"
 
     def load(self, device="cuda:0", weights=None, precision=None):
         device = torch.device(device)
@@ -173,7 +170,7 @@ class BiSeNet:
         # read by the small attention kernels (avg-pool / scale-add) stay fp32
         f = 1 if self.precision == 1 else 0
         sp = (lambda a: E.f32_to_split32(a)) if f else (lambda a: a)
-        if f and self.fused_stem and "stem_fused" in p:
+        if f and "stem_fused" in p:     # conv1 + bn1 + relu + maxpool of the ResNet-18 stem in one launch
             x = E.stem_relu_pool_f32(p["stem_fused"], x4, out_fmt=1)        # the 256 x 256 x 64 stem map never reaches HBM
         else:
             x = E.maxpool3x3s2(E.conv(p["stem"], x4, act_slope=0.0, out_fmt=f))

@@ -10,11 +10,11 @@
 // the bench size (64 x 160 x 160 px: x and out are 1.68 GB each at 4 B per element) and run at the HBM rate;
 // fused, a workgroup reads its t1 tile (+ halo, from L2) and its x tile, writes out and t1':  4.2 GB.
 //
-// One 256-thread workgroup owns 128 consecutive output pixels; two workgroups share a CU (80 KiB of LDS each), so
+// One 256-thread workgroup owns an 8 x 16 patch of output pixels; two workgroups share a CU (80 KiB of LDS each), so
 // one computes while the other waits on memory.
 //
-//   phase 1   implicit GEMM 128 x 64 x 576 exactly as conv_igemm_f16x3_dma<64, 2> (both operands by LDS-DMA, two
-//             stages, taps fastest), epilogue -> T2 in LDS as the split32 operand image [2 slices][128 rows][128 B].
+//   phase 1   implicit GEMM 128 x 64 x 576 over the patch's halo, staged once per channel slice (see PATCH below),
+//             epilogue -> T2 in LDS as the split32 operand image [2 slices][128 rows][128 B].
 //   chunks    for each group j of 32 output channels of conv3 (8 groups):
 //               phase 2  acc2[128 x 32]  = T2 . W3[j]^T                (K = 64; W3 group by LDS-DMA, double-buffered)
 //               epilogue out[:, j] = relu(acc2 * ws3 + b3 + x[:, j]) -> HBM, and -> T3 in LDS (operand image)
@@ -25,8 +25,8 @@
 // K slices in ascending order, the same fp32 epilogue expressions, the same hi/lo split of every stored tensor), so
 // out and t1' are BIT-IDENTICAL to running the three convolutions separately (tests/test_chain_gpu.py).
 //
-// The same chunk loop also runs WITHOUT phase 1 ("pair": HAS_C2 = false) on 128-channel inputs, whose operand tile is
-// then fetched by LDS-DMA instead of being computed:
+// The same chunk loop also runs WITHOUT phase 1 ("pair": HAS_C2 = false) on tiles of 128 consecutive pixels of
+// 128-channel inputs, whose operand tile is then fetched by LDS-DMA instead of being computed:
 //     out = relu(bn3(conv3_1x1(t)) [+ x])   128 -> NOUT;    t1' = relu(bn1'(conv1'_1x1(out)))   NOUT -> CN
 //   * NOUT = 512, with residual, CN = 128:  conv3 of a layer-2 identity block + conv1 of the next block: the 512-channel
 //     tensor (0.84 GB at the bench size) is not read back by a separate conv1 launch;
@@ -61,39 +61,39 @@ struct ChainK {
   const float* t1b; unsigned t1b_bytes; int t1b_ld, hb, wb, sb;
 };
 
-// Pixels per workgroup tile: BMT = 128 (4 waves, up to two workgroups per CU; the default) or 256 (8 waves, one workgroup per
-// CU: every filter byte the tile fetches — W2, the conv3 groups, the conv1' slices: 45 % of a 128-pixel tile's vector-memory
-// traffic — serves twice the pixels; an option, not faster: profiles/r03_probes.md).  A wave owns 32 rows either way.
+// Pixels per workgroup tile: BMT = 128, 4 waves, up to two workgroups per CU; a wave owns 32 rows.  (Tiles of 256 pixels on
+// 8 waves, one workgroup per CU, halve the filter traffic per pixel and were measured 0-6 % slower: profiles/r03_probes.md.)
+constexpr int BMT = 128;
 constexpr int C = 64;                 // bottleneck width of the variant with phase 1
 constexpr int ROWB = 128;             // bytes per LDS operand row: 32 hi + 32 lo binary16
-constexpr int stage_bytes(int bmt) { return (bmt + C) * ROWB; }       // one phase-1 stage (A rows then B rows): 24 | 40 KiB
-constexpr int CT_OFF = 0;                       // chunk loop: BMT x 32 fp32 epilogue tile, rewritten in place as T3 (16 | 32 KiB)
-constexpr int w1b_off(int bmt) { return bmt * 128; }                  // chunk loop: K slice j of conv1' (CN rows x 128 B)
-// conv1' K slices are double-buffered wherever LDS allows (everything but the 128-pixel conv2 form with CN = 128, whose
-// chunk buffers live in the 48 KiB of the dead phase-1 stages): the next slice's DMA can then be issued BEFORE the chunk's
-// `out` stores, see the chunk loop
-constexpr bool w1_double(int bmt, int cn, bool has_c2) { return !has_c2 || w1b_off(bmt) + 2 * cn * 128 + 2 * C * 128 <= 2 * stage_bytes(bmt); }
-constexpr int w3b_off(int bmt, int cn, bool has_c2) { return w1b_off(bmt) + (w1_double(bmt, cn, has_c2) ? 2 : 1) * cn * 128; }   // conv3 filter groups, 2 x (CW * 128 B)
+constexpr int STAGE = (BMT + C) * ROWB;         // 24 KiB; region 0 of the conv2 forms is two of these (phase 1's halo patch and filter stages)
+constexpr int CT_OFF = 0;                       // chunk loop: BMT x 32 fp32 epilogue tile, rewritten in place as T3 (16 KiB)
+constexpr int W1B_OFF = BMT * 128;              // chunk loop: K slice j of conv1' (CN rows x 128 B)
+// conv1' K slices are double-buffered wherever LDS allows (everything but the conv2 form with CN = 128, whose chunk buffers
+// live in the 48 KiB of the dead phase-1 stages): the next slice's DMA can then be issued BEFORE the chunk's `out` stores,
+// see the chunk loop
+constexpr bool w1_double(int cn, bool has_c2) { return !has_c2 || W1B_OFF + 2 * cn * 128 + 2 * C * 128 <= 2 * STAGE; }
+constexpr int w3b_off(int cn, bool has_c2) { return W1B_OFF + (w1_double(cn, has_c2) ? 2 : 1) * cn * 128; }   // conv3 filter groups, 2 x (CW * 128 B)
 // region 0 = phase-1 stages | epilogue tiles | chunk buffers; the operand tile T2 (BMT x CW, 4 B per element) follows it
-constexpr int r0_bytes(int bmt, int cw, int cn, bool has_c2) { return has_c2 ? 2 * stage_bytes(bmt) : w3b_off(bmt, cn, has_c2) + 2 * cw * 128; }
+constexpr int r0_bytes(int cw, int cn, bool has_c2) { return has_c2 ? 2 * STAGE : w3b_off(cn, has_c2) + 2 * cw * 128; }
 // In the pair forms T2 ALIASES the chunk buffers: a wave's T2 fragments are the same for every chunk and live in
 // registers, so the tile is only needed until they have been read.  That is what lets the 256-wide pair fit at all
 // (144 + 128 KiB otherwise) and brings the 128-wide pairs down to 80 KiB: TWO workgroups per CU, the second one's
 // MFMAs under the first one's epilogue (FCP_CHAIN_NOALIAS: the 128-wide pairs as before, 128-144 KiB, one per CU).
-constexpr bool alias_t2(int bmt, int cw, int cn, bool has_c2) { return !has_c2; }
+constexpr bool alias_t2(bool has_c2) { return !has_c2; }
 // DIRECT (two-source pair forms, round 5): the operand tile never exists in LDS at all — a lane's fragments are 16-byte pieces of
 // the split32 pixel rows, i.e. plain buffer loads straight into the registers they live in for the whole chunk loop (a
 // 128 x 384-channel tile is 192 KiB: it fits neither LDS nor an alias of the chunk buffers); LDS holds the chunk buffers only.
-constexpr int lds_bytes(int bmt, int cw, int cn, bool has_c2, bool direct = false) {   // 80 KiB (two per CU) | 112-160 KiB
-  const int r0 = r0_bytes(bmt, cw, cn, has_c2), t2 = bmt * cw * 4;
+constexpr int lds_bytes(int cw, int cn, bool has_c2, bool direct = false) {   // 80 KiB (two per CU) | 112-160 KiB
+  const int r0 = r0_bytes(cw, cn, has_c2), t2 = BMT * cw * 4;
   if (direct) return r0;
-  return !alias_t2(bmt, cw, cn, has_c2) ? r0 + t2 : (r0 > w1b_off(bmt) + t2 ? r0 : w1b_off(bmt) + t2);
+  return !alias_t2(has_c2) ? r0 + t2 : (r0 > W1B_OFF + t2 ? r0 : W1B_OFF + t2);
 }
-constexpr int wgs_per_cu(int bmt, int cw, int cn, bool has_c2, bool direct = false) {
+constexpr int wgs_per_cu(int cw, int cn, bool has_c2, bool direct = false) {
   // the two-source DIRECT pair holds 48 fragments + conv1's accumulators: one wave per SIMD; the EXPAND form (cn = 0: conv3 only,
   // no conv1' — no accumulators, no conv1' buffers: 80 KiB, < 256 registers) runs two workgroups per CU
-  if (direct) return bmt == 128 && cn == 0 && lds_bytes(bmt, cw, cn, has_c2, true) <= 80 * 1024 ? 2 : 1;
-  return bmt == 128 && lds_bytes(bmt, cw, cn, has_c2) <= 80 * 1024 ? 2 : 1;
+  if (direct) return cn == 0 && lds_bytes(cw, cn, has_c2, true) <= 80 * 1024 ? 2 : 1;
+  return lds_bytes(cw, cn, has_c2) <= 80 * 1024 ? 2 : 1;
 }
 
 __device__ __forceinline__ int swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
@@ -106,9 +106,9 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-// PATCH (conv2 forms, 128-pixel tiles): the tile is an 8 x 16 PATCH of one image instead of 128 consecutive pixels, and
-// phase 1 stages the patch's (8 + 2) x (16 + 2) halo ONCE per 32-channel slice; the nine taps read it at shifted rows (the
-// scheme of conv3x3_halo_f16x3).  The linear form fetches a 128-byte operand row per pixel, tap and slice: 288 of the ~720
+// PATCH (the conv2 forms): the tile is an 8 x 16 PATCH of one image instead of 128 consecutive pixels, and phase 1 stages the
+// patch's (8 + 2) x (16 + 2) halo ONCE per 32-channel slice; the nine taps read it at shifted rows (the scheme of
+// conv3x3_halo_f16x3).  A tile of consecutive pixels fetches a 128-byte operand row per pixel, tap and slice: 288 of the ~720
 // one-KiB vector-memory instructions a tile issues — and the chain kernels are bound by exactly that path
 // (profiles/r04_probes.md section 1: same cycles with and without their MFMAs).  The halo form issues 46.  Same K order (channel
 // slice outer, taps inner), same terms: bit-identical.
@@ -117,31 +117,28 @@ __device__ __forceinline__ void static_for(F&& f) {
 // Where the pair needs one wave per SIMD (layer 3: 128 accumulator + 128 fragment registers), the expand form needs 128 + 16 and
 // 80 KiB, i.e. two workgroups per CU like the forms that sit nearest their floors, and conv1' runs on the 256-row kernel.
 constexpr bool direct_form(int cn, int cw2) { return cw2 > 0 || cn == 0; }
-template <int CN, int CW, int NOUT, bool HAS_C2, bool HAS_RES, int BMT, bool PATCH = false, int CW2 = 0>
-__global__ void __launch_bounds__(2 * BMT, wgs_per_cu(BMT, CW, CN, HAS_C2, direct_form(CN, CW2)) * BMT / 128) bneck_chain_c64(const ChainK p) {
+template <int CN, int CW, int NOUT, bool HAS_C2, bool HAS_RES, int CW2 = 0>
+__global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_form(CN, CW2))) bneck_chain_c64(const ChainK p) {
   constexpr bool DIRECT = direct_form(CN, CW2);   // fragments loaded straight from global memory: the two-source pair (CW - CW2 channels from t1, CW2 from t1b)
-  static_assert(!DIRECT || (!HAS_C2 && BMT == 128 && CW2 % 32 == 0 && CW2 < CW), "direct forms are pair forms on 128-pixel tiles");
+  static_assert(!DIRECT || (!HAS_C2 && CW2 % 32 == 0 && CW2 < CW), "direct forms are pair forms");
   constexpr bool HAS_P3 = CN > 0;                   // conv1' of the next block (phase 3); false: the expand form
   static_assert(!HAS_C2 || CW == C, "phase 1 is written for 64-channel bottlenecks");
-  static_assert(!PATCH || HAS_C2, "the patch form is a conv2 form");
-  constexpr int PH = BMT / 16;                      // PATCH: rows of the (PH x 16)-pixel patch: 8 (4 waves) or 16 (8 waves)
-  static_assert(BMT == 128 || BMT == 256, "tile height");
+  constexpr bool PATCH = HAS_C2;                    // the conv2 forms run on pixel patches
+  constexpr int PH = BMT / 16;                      // PATCH: rows of the (PH x 16)-pixel patch: 8
   constexpr int NTHR = 2 * BMT;                     // threads: one wave per 32 rows
   constexpr int NW = NTHR / 64;                     // waves
   constexpr int LR = NTHR / 8;                      // rows one DMA pass of the workgroup covers (8 rows per wave instruction)
-  constexpr int STAGE = stage_bytes(BMT);
-  constexpr int W1B_OFF = w1b_off(BMT);
   constexpr int TN3 = CN / 32;
   constexpr int TN3A = TN3 > 0 ? TN3 : 1;           // array extents (the expand form has no conv1' tiles)
   constexpr int CS = CW / 32;                       // K slices of conv3
   constexpr int NCH = NOUT / 32;                    // groups of 32 conv3 filters
   constexpr int W3CH = CW * 128;                    // bytes of one conv3 filter group in LDS
-  constexpr bool ALIAS = alias_t2(BMT, CW, CN, HAS_C2) && !DIRECT;
-  constexpr int T2_OFF = ALIAS ? W1B_OFF : r0_bytes(BMT, CW, CN, HAS_C2);
-  constexpr int WGS = wgs_per_cu(BMT, CW, CN, HAS_C2, DIRECT);
+  constexpr bool ALIAS = alias_t2(HAS_C2) && !DIRECT;
+  constexpr int T2_OFF = ALIAS ? W1B_OFF : r0_bytes(CW, CN, HAS_C2);
+  constexpr int WGS = wgs_per_cu(CW, CN, HAS_C2, DIRECT);
   constexpr int WPS = WGS * NW / 4;                 // waves per SIMD: 2 = 256 registers per wave
-  static_assert(lds_bytes(BMT, CW, CN, HAS_C2, DIRECT) <= 160 * 1024, "LDS budget");
-  constexpr bool W1DB = w1_double(BMT, CN, HAS_C2);
+  static_assert(lds_bytes(CW, CN, HAS_C2, DIRECT) <= 160 * 1024, "LDS budget");
+  constexpr bool W1DB = w1_double(CN, HAS_C2);
   // The next chunk's filter DMAs: one at a time BETWEEN the phase-2 MFMAs, or as a burst at the top of the chunk.  An LDS-DMA
   // instruction holds its wave until the vector-memory path has taken it.  With ONE wave per SIMD (the one-workgroup pair
   // forms) a burst of CS + CN / 32 of them is ~1000-2000 cycles with the matrix pipe idle, and spreading them wins (layer-3
@@ -159,7 +156,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(BMT, CW, CN, HAS_C2, direc
   constexpr int PQ = ROT ? TN3 / CS : 0;                // phase-3 MFMAs behind every phase-2 MFMA (6 TN3 against 6 CS)
   static_assert(!ROT || (TN3 % CS == 0 && PQ >= 1), "rotated loop: TN3 must be a multiple of CS");
   constexpr bool W1PRE = !ROT && W1DB && !DIRECT && (HAS_C2 ? CN <= 64 || WPS == 1 : CN <= 128 && WPS == 1);   // conv1' fragments of a chunk requested under phase 2 (registers permitting)
-  constexpr int W3B_OFF = w3b_off(BMT, CN, HAS_C2);
+  constexpr int W3B_OFF = w3b_off(CN, HAS_C2);
   static_assert(!HAS_C2 || W3B_OFF + 2 * W3CH <= 2 * STAGE, "chunk buffers must fit the phase-1 stage region");
   constexpr int NRES = HAS_RES ? 4 : 0;             // residual loads per chunk and thread
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -204,7 +201,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(BMT, CW, CN, HAS_C2, direc
     }
   };
 
-  // ---- conv2 epilogue (both phase-1 forms): fp32 tile [BMT][64] over the dead phase-1 buffers -> relu(acc * ws2 + b2) -> T2
+  // ---- conv2 epilogue: fp32 tile [BMT][64] over the dead phase-1 buffers -> relu(acc * ws2 + b2) -> T2
   auto conv2_epilogue = [&](const f32x16 (&acc1)[2], int wm, int wn) {
     float* Cs = smem;
 #pragma unroll
@@ -247,19 +244,18 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(BMT, CW, CN, HAS_C2, direc
   };
 
   // =========================================================================================== phase 1: 3x3 conv
-  if constexpr (HAS_C2 && PATCH) {
-    constexpr int HALO = (PH + 2) * 18;                          // 10 x 18 = 180 | 18 x 18 = 324 halo rows ...
-    constexpr int HROWS = (HALO + LR - 1) / LR * LR;             // ... padded to whole DMA passes: 192 | 384
+  if constexpr (HAS_C2) {
+    constexpr int HALO = (PH + 2) * 18;                          // 10 x 18 = 180 halo rows ...
+    constexpr int HROWS = (HALO + LR - 1) / LR * LR;             // ... padded to whole DMA passes: 192
     constexpr int ASL = HROWS * ROWB;                            // one channel slice of the halo patch: 24 KiB
-    // filter stages behind the two slices: TPB taps (K slices of 8 KiB) per stage and per workgroup barrier — 2 where the
-    // patch form runs two workgroups per CU in 80 KiB, 3 in the 8-wave form
-    // (one tap per barrier measured equal in the 4-wave form and 3.5-4 % slower in the 8-wave form: profiles/r04_probes.md 1e)
-    constexpr int TPB = BMT == 128 ? 2 : 3, NSTEP = 18 / TPB;
+    // filter stages behind the two slices: TPB = 2 taps (K slices of 8 KiB) per stage and per workgroup barrier
+    // (one tap per barrier measured equal: profiles/r04_probes.md 1e)
+    constexpr int TPB = 2, NSTEP = 18 / TPB;
     static_assert(18 % TPB == 0, "taps per barrier must divide the 18 K slices");
     constexpr int BST_OFF = 2 * ASL, BSL = C * ROWB, BSTG = TPB * BSL;
     static_assert(BST_OFF + 2 * BSTG <= T2_OFF + BMT * C * 4, "halo patch + filter stages must fit region 0 + T2");
     f32x16 acc1[2];
-    const int wm = wave / 2, wn = wave % 2;                      // 2 x 2 waves of 64 x 32, as in the linear form
+    const int wm = wave / 2, wn = wave % 2;                      // 2 x 2 waves of 64 x 32
     __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t1), 0, p.t1_bytes, 0x00020000);
     __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w2), 0, p.w2_bytes, 0x00020000);
     // ---- the halo patch, both channel slices: 6 passes of 32 rows each (rows >= 180 and pixels outside the image: zero fill)
@@ -346,132 +342,6 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(BMT, CW, CN, HAS_C2, direc
     __builtin_amdgcn_s_barrier();                                  // every wave has consumed the last slice: patch and stages are dead
     __builtin_amdgcn_sched_barrier(0);
     conv2_epilogue(acc1, wm, wn);
-  } else if constexpr (HAS_C2) {
-    f32x16 acc1[2];
-    constexpr int A_LD = BMT / LR, B_LD = C / LR;
-    const int wm = wave / 2, wn = wave % 2;                      // (NW / 2) x 2 waves of 64 x 32
-    TapPiece tp[A_LD];
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-      const int m = tile_m * BMT + lrow + LR * i;
-      unsigned pbase = 0;
-      int hi0 = -(1 << 28), wi0 = 0;
-      if (m < p.M) {
-        const int ni = m / hw;
-        const int rem = m - ni * hw;
-        const int ho = rem / p.w;
-        pbase = (unsigned)(ni * hw);
-        hi0 = ho - 1;
-        wi0 = rem - ho * p.w - 1;
-      }
-      tp[i].base = ((pbase + (unsigned)(hi0 * p.w + wi0)) * (unsigned)p.t1_ld + (unsigned)(csrc * 4)) * 4u;
-      tp[i].mask = 0u;
-#pragma unroll
-      for (int q = 0; q < 9; ++q) {
-        const bool ok = (unsigned)(hi0 + q / 3) < (unsigned)p.h && (unsigned)(wi0 + q % 3) < (unsigned)p.w;
-        tp[i].mask |= ok ? (1u << q) : 0u;
-      }
-    }
-    __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t1), 0, p.t1_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w2), 0, p.w2_bytes, 0x00020000);
-    unsigned woff[B_LD];
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) woff[i] = (unsigned)(((lrow + LR * i) * (9 * C) + csrc * 4) * 4);
-    unsigned rowoff[A_LD];
-    auto set_tap = [&](int tap, int kh_i, int kw_i) {
-      const unsigned tapoff = (unsigned)((kh_i * p.w + kw_i) * p.t1_ld) * 4u;
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) rowoff[i] = ((tp[i].mask >> tap) & 1u) ? tp[i].base + tapoff : 0xFFFFFFFFu;
-    };
-    int tap = 0, kh_i = 0, kw_i = 0, c0 = 0;
-    auto advance = [&]() {
-      ++tap;
-      if (++kw_i >= 3) {
-        kw_i = 0;
-        if (++kh_i >= 3) { kh_i = 0; tap = 0; c0 += BK; }
-      }
-      set_tap(tap, kh_i, kw_i);
-    };
-    auto dma_slice = [&](int kt, int stage) {
-      char* a = lds + stage * STAGE + wave_u * 8 * ROWB;
-      char* b = a + BMT * ROWB;
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        const unsigned ro = rowoff[i];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (__attribute__((address_space(3))) void*)(a + LR * i * ROWB), 16,
-                                                 (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)(c0 * 4)), 0, 0, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < B_LD; ++i) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(b + LR * i * ROWB), 16,
-                                                 (int)(woff[i] + (unsigned)(kt * BK * 4)), 0, 0, 0);
-      }
-    };
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc1[i][e] = 0.f;
-
-    const int aoff = (wm * 64 + l31) * ROWB;
-    const int boff = BMT * ROWB + (wn * 32 + l31) * ROWB;
-    constexpr int KT = 9 * C / 32;                               // 18 K slices
-    // Two stages: the next slice is issued inside the iteration and waited for at its end.  (FCP_CHAIN_C2_STAGES3: three
-    // stages, slices fetched TWO ahead — the third stage costs no LDS, it lies in the T2 region, which is only written by the
-    // conv2 epilogue — measured equal, 1327-1341 vs 1328-1340 us: with two workgroups per CU the other one covers the DMA
-    // round trip already; profiles/r03_probes.md.)
-    constexpr int NST = 2;
-    static_assert(NST * STAGE <= T2_OFF + BMT * C * 4, "phase-1 stages must fit region 0 + T2");
-    set_tap(0, 0, 0);
-    dma_slice(0, 0);
-    if constexpr (NST == 3) {
-      advance();
-      dma_slice(1, 1);
-    }
-    int stage = 0;
-    const int kt_end = KT;
-    for (int kt = 0; kt < kt_end; ++kt) {
-      // slice kt has landed (the one or two younger slices may still fly) and every wave is done with slice kt - 1
-      if (NST == 3 && kt + 1 < KT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_LD + B_LD) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      const char* Ab = lds + stage * STAGE + aoff;
-      const char* Bb = lds + stage * STAGE + boff;
-      f16x8 ah[2][2], al[2][2], bh[2], bl[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          ah[s][i] = *reinterpret_cast<const f16x8*>(Ab + i * 32 * ROWB + offH[s]);
-          al[s][i] = *reinterpret_cast<const f16x8*>(Ab + i * 32 * ROWB + offL[s]);
-        }
-        bh[s] = *reinterpret_cast<const f16x8*>(Bb + offH[s]);
-        bl[s] = *reinterpret_cast<const f16x8*>(Bb + offL[s]);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      if (kt + NST - 1 < KT) {                                   // into the stage slice kt - 1 has just left
-        advance();
-        const int nstage = stage == 0 ? NST - 1 : stage - 1;     // (stage + NST - 1) % NST
-        dma_slice(kt + NST - 1, nstage);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s][i], bh[s], acc1[i], 0, 0, 0);
-          acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s][i], bl[s], acc1[i], 0, 0, 0);
-          acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s][i], bh[s], acc1[i], 0, 0, 0);
-        }
-      __builtin_amdgcn_sched_barrier(0);
-      stage = stage + 1 == NST ? 0 : stage + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                  // every wave has consumed the last slice: the stages are dead
-    __builtin_amdgcn_sched_barrier(0);
-
-    conv2_epilogue(acc1, wm, wn);
   } else if constexpr (!DIRECT) {
     // ---- no conv2: the operand tile is the input itself (CS slices of 128 pixels x 128 B), by LDS-DMA
     __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.t1), 0, p.t1_bytes, 0x00020000);
@@ -490,7 +360,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(BMT, CW, CN, HAS_C2, direc
   __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w3), 0, p.w3_bytes, 0x00020000);
   __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w1n), 0, p.w1n_bytes, 0x00020000);
   // conv3 filter group j: 32 rows x CS K slices = 4 CS pieces of 8 rows.  Wave w moves pieces w PW3 .. w PW3 + PW3 - 1.
-  constexpr int PW3 = 4 * CS / NW;                  // per wave: CS (4 waves) | CS / 2 (8 waves)
+  constexpr int PW3 = 4 * CS / NW;                  // per wave: CS
   constexpr int PW1 = CN / (8 * NW);                // conv1' slice: CN rows, 8 per wave instruction
   static_assert(PW3 >= 1 && (PW1 >= 1 || !HAS_P3), "filter pieces per wave");
   auto dma_w3 = [&](int j, int buf) {
@@ -955,12 +825,12 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(BMT, CW, CN, HAS_C2, direc
   }
 }
 
-template <int CN, int CW, int NOUT, bool HAS_C2, bool HAS_RES, int BMT, bool PATCH = false, int CW2 = 0>
+template <int CN, int CW, int NOUT, bool HAS_C2, bool HAS_RES, int CW2 = 0>
 int launch(const ChainK& k, hipStream_t s) {
-  constexpr int LDS = lds_bytes(BMT, CW, CN, HAS_C2, direct_form(CN, CW2));
-  FCP_LDS_OPT_IN((&bneck_chain_c64<CN, CW, NOUT, HAS_C2, HAS_RES, BMT, PATCH, CW2>), LDS);
-  const int tiles = PATCH ? k.n * fcp_cdiv(k.h, BMT / 16) * ((k.w + 15) >> 4) : fcp_cdiv(k.M, BMT);
-  hipLaunchKernelGGL((bneck_chain_c64<CN, CW, NOUT, HAS_C2, HAS_RES, BMT, PATCH, CW2>), dim3(tiles), dim3(2 * BMT), LDS, s, k);
+  constexpr int LDS = lds_bytes(CW, CN, HAS_C2, direct_form(CN, CW2));
+  FCP_LDS_OPT_IN((&bneck_chain_c64<CN, CW, NOUT, HAS_C2, HAS_RES, CW2>), LDS);
+  const int tiles = HAS_C2 ? k.n * fcp_cdiv(k.h, BMT / 16) * ((k.w + 15) >> 4) : fcp_cdiv(k.M, BMT);   // conv2 forms: 8 x 16 patches
+  hipLaunchKernelGGL((bneck_chain_c64<CN, CW, NOUT, HAS_C2, HAS_RES, CW2>), dim3(tiles), dim3(2 * BMT), LDS, s, k);
   FCP_LAUNCH_OK();
   return 0;
 }
@@ -1019,25 +889,17 @@ extern "C" int fcp_bottleneck_chain_f16x3(const fcp_chain_desc* d, fcp_stream_t 
     k.t1b = d->t1b; k.t1b_bytes = (unsigned)tb; k.t1b_ld = d->t1b_ld; k.hb = d->t1b_h; k.wb = d->t1b_w; k.sb = d->t1b_stride;
   }
   k.out_even = (d->flags & FCP_CHAIN_OUT_EVEN_ONLY) ? 1 : 0;
-  FCP_REQUIRE(!k.out_even || d->tile_m == 16 || d->tile_m == 32, "chain: FCP_CHAIN_OUT_EVEN_ONLY needs a patch form (tile_m = 16 | 32)");
+  FCP_REQUIRE(!k.out_even || has_c2, "chain: FCP_CHAIN_OUT_EVEN_ONLY needs a conv2 form");
   hipStream_t s = (hipStream_t)stream;
-  // tile height: 128 pixels / 4 waves (two independent workgroups per CU drift against each other: one's MFMAs beside the
-  // other's epilogue); d->tile_m = 256 asks for the 8-wave form where the operand tile fits LDS and two waves per SIMD fit
-  // the registers (same bits; measured 0-6 % slower: what halving the filter traffic gains, one barrier domain of eight
-  // waves loses — profiles/r03_probes.md)
-  const bool big = d->tile_m == 256;
-  // d->tile_m = 16: the conv2 forms on 8 x 16 patches with a staged halo (PATCH; same bits)
-  // d->tile_m = 32: the same with 16 x 16 patches on 8 waves (one workgroup per CU; every filter byte serves 256 pixels)
-  const bool patch = d->tile_m == 16, patch2 = d->tile_m == 32;
-  FCP_REQUIRE(!(patch || patch2) || has_c2, "chain: tile_m = 16 / 32 (pixel patches) exist for the conv2 forms only");
+  // d->tile_m is a hint this library ignores: the conv2 forms run on 8 x 16 patches, the others on 128-pixel tiles
   switch (variant) {
-    case 1: return patch2 ? launch<64, 64, 256, true, true, 256, true>(k, s) : patch ? launch<64, 64, 256, true, true, 128, true>(k, s) : big ? launch<64, 64, 256, true, true, 256>(k, s) : launch<64, 64, 256, true, true, 128>(k, s);
-    case 2: return patch2 ? launch<128, 64, 256, true, true, 256, true>(k, s) : patch ? launch<128, 64, 256, true, true, 128, true>(k, s) : big ? launch<128, 64, 256, true, true, 256>(k, s) : launch<128, 64, 256, true, true, 128>(k, s);
-    case 3: return big ? launch<128, 128, 512, false, true, 256>(k, s) : launch<128, 128, 512, false, true, 128>(k, s);
-    case 5: return launch<256, 256, 1024, false, true, 128>(k, s);
-    case 6: return launch<256, 128, 512, false, true, 128>(k, s);     // CN = 256: 128 accumulator registers, one wave per SIMD only
-    case 7: return launch<128, 384, 512, false, false, 128, false, 256>(k, s);   // [conv2 out 128 | x(::2, ::2) 256] -> 512 -> 128
-    case 8: return launch<0, 256, 1024, false, true, 128>(k, s);                  // expand form: conv3 256 -> 1024 + identity, no conv1'
-    default: return big ? launch<64, 128, 256, false, false, 256>(k, s) : launch<64, 128, 256, false, false, 128>(k, s);
+    case 1: return launch<64, 64, 256, true, true>(k, s);
+    case 2: return launch<128, 64, 256, true, true>(k, s);
+    case 3: return launch<128, 128, 512, false, true>(k, s);
+    case 5: return launch<256, 256, 1024, false, true>(k, s);
+    case 6: return launch<256, 128, 512, false, true>(k, s);     // CN = 256: 128 accumulator registers, one wave per SIMD only
+    case 7: return launch<128, 384, 512, false, false, 256>(k, s);   // [conv2 out 128 | x(::2, ::2) 256] -> 512 -> 128
+    case 8: return launch<0, 256, 1024, false, true>(k, s);          // expand form: conv3 256 -> 1024 + identity, no conv1'
+    default: return launch<64, 128, 256, false, false>(k, s);
   }
 }

@@ -384,8 +384,6 @@ extern "C" int fcp_conv2d_nhwc_f32(const fcp_conv_desc* d, fcp_stream_t stream) 
     k.in_bytes = (unsigned)in_bytes;
     k.w_bytes = (unsigned)w_bytes;
     // split32 activations: both operands are pure byte copies -> LDS-DMA kernel
-    // two LDS stages (three were measured slower: they cost an occupancy step); profiling builds may override
-    const int dma_stages = 2;
     if (halo) {
       k.grid_n = 1;
       const unsigned long out_bytes = (unsigned long)M * d->out_ld * 4ul;
@@ -400,7 +398,7 @@ extern "C" int fcp_conv2d_nhwc_f32(const fcp_conv_desc* d, fcp_stream_t stream) 
       k.w_bytes = (unsigned)((unsigned long)fcp_cdiv(d->cout, 128) * 128ul * k.wrow * 4ul);   // filters are padded to 128 rows
       return launch_f16x3_big(k, d->tile_n, s);
     }
-    if (k.in_fmt == 1 && !d->cin4) return launch_f16x3_dma(k, d->tile_n, dma_stages, s);
+    if (k.in_fmt == 1 && !d->cin4) return launch_f16x3_dma(k, d->tile_n, s);
     return launch_f16x3(k, d->tile_n, d->cin4 != 0, s);
   }
   k.in_bytes = buf ? (unsigned)in_bytes : 0u;

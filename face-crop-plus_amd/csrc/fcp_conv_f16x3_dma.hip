@@ -10,7 +10,7 @@
 //
 // Pipeline (NST LDS stages, one barrier per slice): all fragment reads of slice kt are issued
 // first, then the DMA of slice kt+NST-1 (so the compiler never has an LDS read behind a pending
-// DMA), then the 24 MFMAs; a counted vmcnt + s_barrier closes the step.
+// DMA), then the 24 MFMAs; a vmcnt(0) + s_barrier closes the step.
 #include "fcp_conv_common.h"
 
 using namespace fcp_conv;
@@ -19,9 +19,11 @@ namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
+constexpr int NST = 2;   // LDS stages (three were measured slower: they cost an occupancy step)
+
 // EP8: the output or a residual is split32 (cout % 8 == 0): the tile is accumulated transposed (filters x pixels — same bits) and
 // the epilogue works from the registers (conv_epilogue_regs); else the pixel-major tile and the staged fp32 epilogue.
-template <int BN, int NST, bool EP8>
+template <int BN, bool EP8>
 __global__ void __launch_bounds__(256, (BN == 128 ? 2 : 3)) conv_igemm_f16x3_dma(const ConvK p) {
   constexpr int WAVES_N = (BN == 32) ? 1 : 2;
   constexpr int WAVES_M = 4 / WAVES_N;
@@ -173,13 +175,7 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : 3)) conv_igemm_f16x3_dma
 
   set_tap(0, 0, 0);
   dma_slice(0, 0);
-  if (NST == 3 && p.ktiles > 1) {
-    advance();
-    dma_slice(1, 1);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_LD + B_LD) : "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
   int stage = 0;
@@ -229,10 +225,8 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : 3)) conv_igemm_f16x3_dma
           }
         }
     __builtin_amdgcn_sched_barrier(0);   // keep the waits below behind the MFMAs ("memory" does not order MFMAs)
-    // slice kt+1 must have landed before anyone reads it; with three stages the DMA issued in this
-    // step (slice kt+2) may stay in flight across the barrier
-    if (NST == 3 && issue) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_LD + B_LD) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // slice kt+1 must have landed before anyone reads it
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (++stage >= NST) stage = 0;
@@ -247,38 +241,31 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : 3)) conv_igemm_f16x3_dma
   }
 }
 
-template <int BN, int NST, bool EP8>
+template <int BN, bool EP8>
 int launch_ep(const ConvK& k, hipStream_t s) {
   size_t lds = (size_t)NST * (BM + BN) * 128;
   const size_t epi = EP8 ? 0 : (size_t)BM * BN * 4;       // the staged epilogue's C tile
   if (lds < epi) lds = epi;
-  FCP_LDS_OPT_IN((&conv_igemm_f16x3_dma<BN, NST, EP8>), lds);
-  hipLaunchKernelGGL((conv_igemm_f16x3_dma<BN, NST, EP8>), dim3(k.grid_m * k.grid_n), dim3(256), lds, s, k);
+  FCP_LDS_OPT_IN((&conv_igemm_f16x3_dma<BN, EP8>), lds);
+  hipLaunchKernelGGL((conv_igemm_f16x3_dma<BN, EP8>), dim3(k.grid_m * k.grid_n), dim3(256), lds, s, k);
   FCP_LAUNCH_OK();
   return 0;
 }
-template <int BN, int NST>
+template <int BN>
 int launch(const ConvK& k, hipStream_t s) {
   const bool ep8 = (k.out_fmt | k.res1_fmt | k.res2_fmt) != 0;
-  return ep8 ? launch_ep<BN, NST, true>(k, s) : launch_ep<BN, NST, false>(k, s);
+  return ep8 ? launch_ep<BN, true>(k, s) : launch_ep<BN, false>(k, s);
 }
 
 }  // namespace
 
 namespace fcp_conv {
 
-int launch_f16x3_dma(const ConvK& k, int tile_n, int stages, hipStream_t s) {
-  if (stages == 3) {
-    switch (tile_n) {
-      case 32: return launch<32, 3>(k, s);
-      case 64: return launch<64, 3>(k, s);
-      default: return launch<128, 3>(k, s);
-    }
-  }
+int launch_f16x3_dma(const ConvK& k, int tile_n, hipStream_t s) {
   switch (tile_n) {
-    case 32: return launch<32, 2>(k, s);
-    case 64: return launch<64, 2>(k, s);
-    default: return launch<128, 2>(k, s);
+    case 32: return launch<32>(k, s);
+    case 64: return launch<64>(k, s);
+    default: return launch<128>(k, s);
   }
 }
 

@@ -856,8 +856,7 @@ int launch_f16x3_halo(const ConvK& k, hipStream_t s) {
   return 0;
 }
 
-#define FCP_WIDE2_BT 2
-constexpr int WIDE2_BT = FCP_WIDE2_BT;   // taps per barrier of the 64-filter form (eight 8 KB slots); tools/wide2_ab.sh: RRDB conv5 610 / 586 / 605 us for 1 / 2 / 3
+constexpr int WIDE2_BT = 2;   // taps per barrier of the 64-filter form (eight 8 KB slots); profiles/r03_probes.md: RRDB conv5 610 / 586 / 605 us for 1 / 2 / 3
 
 int launch_f16x3_halo_wide(const ConvK& k, hipStream_t s) {
   const int tn = k.cout <= 64 ? 2 : 4;

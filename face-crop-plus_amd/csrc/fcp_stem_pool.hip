@@ -44,30 +44,23 @@ constexpr int IH = 2 * SH + 5;                 // 27 image rows (+1 spare row fo
 constexpr int SPITCH = 68;                     // floats per staged stem pixel (64 + 4: conflict-free pooling)
 constexpr int KSTEPS = 11;                     // 22 chunks of 8 K values (7 rows x 3 chunks, +1 zero chunk)
 
-// Patch geometry as a function of the patch width PW (pooled pixels): 16 = the product form, 512 threads, one workgroup per CU;
-// 8 = 256 threads and 74 KiB of LDS, TWO workgroups per CU (round 5).  A patch runs as a sequence of phases separated by
-// workgroup barriers (commit -> MFMAs -> pooling + stores -> conv1 -> its epilogue), the matrix pipe being busy in one of them
-// only (23 % of the cycles in the round-3 probes): the idea was that two independent workgroups per CU put one's MFMA phase beside
-// the other's LDS / store phases.  Same work per wave and patch (3 row tiles x 11 k-steps), same K order per stem pixel, same
-// bits (tools/stem_hash.py: identical digest) — and 8.8 % SLOWER in an in-call A/B (689.7 vs 634.0 us: +10 % image bytes and +3 %
-// stem pixels per pooled pixel for the narrower halo, and no overlap gained: profiles/r05_probes.md section 3).  Kept as a
-// build-time geometry (-DFCP_STEM_PW=8) for that record.
-template <int PW_>
+// Patch geometry: PW = 16 pooled pixels per patch row, 512 threads, one workgroup per CU.  (A patch width of 8 — two 4-wave
+// workgroups per CU, same bits — was 8.8 % slower in an in-call A/B: profiles/r05_probes.md section 3.)
 struct StemGeo {
-  static constexpr int PW = PW_;
-  static constexpr int SW = 2 * PW + 1;                    // stem columns per patch: 33 | 17
-  static constexpr int NSTEM = SH * SW;                    // 363 | 187
-  static constexpr int NTILES = (NSTEM + 31) / 32;         // 12 | 6 row tiles of 32 stem pixels
-  static constexpr int IWB = (2 * SW + 5) * 3;             // 213 | 117 bytes per image row of the patch
-  static constexpr int IPITCH = 6 * SW + 18;               // 216 | 120 binary16 elements per staged image row (a lane's last K chunk ends at 6 SW + 17)
+  static constexpr int PW = 16;
+  static constexpr int SW = 2 * PW + 1;                    // stem columns per patch: 33
+  static constexpr int NSTEM = SH * SW;                    // 363
+  static constexpr int NTILES = (NSTEM + 31) / 32;         // 12 row tiles of 32 stem pixels
+  static constexpr int IWB = (2 * SW + 5) * 3;             // 213 bytes per image row of the patch
+  static constexpr int IPITCH = 6 * SW + 18;               // 216 binary16 elements per staged image row (a lane's last K chunk ends at 6 SW + 17)
   static constexpr int IN_ELEMS = (IH + 1) * IPITCH;
   static constexpr int NT = 32 * PW;                       // threads: the pooling pass is (32 channel pairs) x (PW pooled columns)
   static constexpr int NGRP = NT / 128;                    // row-tile groups: waves = NGRP x 2 column tiles
-  static constexpr int TPR = NT / 28;                      // threads per patch row: 18 | 9 (a whole number of pixels: 6 | 3)
-  static constexpr int NLOAD = (IWB + TPR - 1) / TPR;      // 12 | 13 bytes per thread: columns c0 + TPR j of its row
-  static constexpr int C1ROWS = (PH * PW + 31) / 32 * 32;  // the patch's pooled pixels padded to MFMA row tiles: 96 | 64
+  static constexpr int TPR = NT / 28;                      // threads per patch row: 18 (a whole number of pixels: 6)
+  static constexpr int NLOAD = (IWB + TPR - 1) / TPR;      // 12 bytes per thread: columns c0 + TPR j of its row
+  static constexpr int C1ROWS = (PH * PW + 31) / 32 * 32;  // the patch's pooled pixels padded to MFMA row tiles: 96
   static constexpr int C1_BYTES = C1ROWS * 2 * 128;        // conv1 operand image: [rows][2 channel slices][128 B]
-  static constexpr int WGS = PW <= 8 ? 2 : 1;              // workgroups per CU
+  static constexpr int WGS = 1;                            // workgroups per CU
   static_assert(TPR % 3 == 0 && IH * TPR <= NT && IPITCH % 2 == 0 && NTILES % NGRP == 0, "stem patch geometry");
 };
 
@@ -105,10 +98,10 @@ __device__ __forceinline__ void lds_barrier() {
 // zero, lo = x - hi, the split of every other fp16x3 kernel) and a k-step is three matrix instructions (al*wh + ah*wl + ah*wh)
 // instead of two.  Everything else — patch walk, K order (kh, kw * 3 + c), staging, separable max-pool, scale / bias / ReLU on
 // the pooled pixels — is the same code.
-template <bool HAS_C1, int PW_, bool F32IN = false>
-__global__ void __launch_bounds__(StemGeo<PW_>::NT, StemGeo<PW_>::WGS) stem_pool_kernel(const StemParams p) {
+template <bool HAS_C1, bool F32IN = false>
+__global__ void __launch_bounds__(StemGeo::NT, StemGeo::WGS) stem_pool_kernel(const StemParams p) {
   static_assert(!(HAS_C1 && F32IN), "the fp32-input stem has no conv1 tail");
-  using G = StemGeo<PW_>;
+  using G = StemGeo;
   constexpr int PW = G::PW, SW = G::SW, NSTEM = G::NSTEM, NTILES = G::NTILES, IWB = G::IWB, IPITCH = G::IPITCH;
   constexpr int IN_ELEMS = G::IN_ELEMS, NT = G::NT, NGRP = G::NGRP, TPR = G::TPR, NLOAD = G::NLOAD, C1ROWS = G::C1ROWS;
   constexpr int KPG = NTILES / NGRP;                                // row tiles per wave: 3
@@ -405,10 +398,6 @@ __global__ void __launch_bounds__(StemGeo<PW_>::NT, StemGeo<PW_>::WGS) stem_pool
 
 }  // namespace
 
-#ifndef FCP_STEM_PW
-#define FCP_STEM_PW 16     // pooled pixels per patch row: 16 = one 8-wave workgroup per CU; 8 = two 4-wave workgroups (round 5: same bits, 8.8 % slower)
-#endif
-
 extern "C" int fcp_stem7x7s2_relu_pool_conv1_u8(const uint8_t* images, int n, int h, int w, const int32_t* mean_rgb,
                                                 const void* wfrag, const float* bias, const float* wscale, float* out,
                                                 int out_ld, int out_fmt, const void* w1, const float* ws1, const float* b1,
@@ -433,22 +422,22 @@ extern "C" int fcp_stem7x7s2_relu_pool_conv1_u8(const uint8_t* images, int n, in
   p.hs = (h + 6 - 7) / 2 + 1; p.ws = (w + 6 - 7) / 2 + 1;
   p.hp = (p.hs + 2 - 3) / 2 + 1; p.wp = (p.ws + 2 - 3) / 2 + 1;
   p.out_ld = out_ld; p.out_fmt = out_fmt;
-  p.tiles_y = fcp_cdiv(p.hp, PH); p.tiles_x = fcp_cdiv(p.wp, StemGeo<FCP_STEM_PW>::PW);
+  p.tiles_y = fcp_cdiv(p.hp, PH); p.tiles_x = fcp_cdiv(p.wp, StemGeo::PW);
   const long np = (long)n * p.tiles_y * p.tiles_x;
   FCP_REQUIRE(np < (1L << 31) && (long)n * h * w * 3 < (1L << 40), "stem: batch too large");
   p.npatches = (int)np;
   for (int c = 0; c < 3; ++c) p.mean[c] = mean_rgb[c];
   p.w1 = static_cast<const char*>(w1); p.ws1 = ws1; p.b1 = b1; p.t1 = t1; p.t1_ld = t1_ld;
-  using G = StemGeo<FCP_STEM_PW>;
+  using G = StemGeo;
   const size_t lds = (size_t)G::NSTEM * SPITCH * 4 + (has_c1 ? G::C1_BYTES : 0);   // stem staging (+ conv1's operand image); the binary16 image patch is a static array
   const int cus = fcp_cu_count() * G::WGS;
   const int grid = (int)(np < cus ? np : cus);
   if (has_c1) {
-    FCP_LDS_OPT_IN((&stem_pool_kernel<true, FCP_STEM_PW>), lds);
-    hipLaunchKernelGGL((stem_pool_kernel<true, FCP_STEM_PW>), dim3(grid), dim3(G::NT), lds, (hipStream_t)stream, p);
+    FCP_LDS_OPT_IN((&stem_pool_kernel<true>), lds);
+    hipLaunchKernelGGL((stem_pool_kernel<true>), dim3(grid), dim3(G::NT), lds, (hipStream_t)stream, p);
   } else {
-    FCP_LDS_OPT_IN((&stem_pool_kernel<false, FCP_STEM_PW>), lds);
-    hipLaunchKernelGGL((stem_pool_kernel<false, FCP_STEM_PW>), dim3(grid), dim3(G::NT), lds, (hipStream_t)stream, p);
+    FCP_LDS_OPT_IN((&stem_pool_kernel<false>), lds);
+    hipLaunchKernelGGL((stem_pool_kernel<false>), dim3(grid), dim3(G::NT), lds, (hipStream_t)stream, p);
   }
   FCP_LAUNCH_OK();
   return 0;
@@ -462,7 +451,7 @@ extern "C" int fcp_stem7x7s2_relu_pool_f32(const float* x4, int n, int h, int w,
   FCP_REQUIRE(out_ld >= 64 && out_ld % (out_fmt ? 32 : 4) == 0 && ((uintptr_t)out & (out_fmt ? 127 : 15)) == 0,
               "stem(f32): misaligned output view");
   FCP_REQUIRE(((uintptr_t)wfrag & 15) == 0 && ((uintptr_t)x4 & 15) == 0, "stem(f32): input / filter fragments must be 16-byte aligned");
-  using G = StemGeo<FCP_STEM_PW>;
+  using G = StemGeo;
   StemParams p = {};
   p.imgf = x4; p.wfrag = static_cast<const uint32_t*>(wfrag); p.bias = bias; p.wscale = wscale; p.out = out;
   p.n = n; p.h = h; p.w = w;
@@ -476,8 +465,8 @@ extern "C" int fcp_stem7x7s2_relu_pool_f32(const float* x4, int n, int h, int w,
   const size_t lds = (size_t)G::NSTEM * SPITCH * 4;
   const int cus = fcp_cu_count() * G::WGS;
   const int grid = (int)(np < cus ? np : cus);
-  FCP_LDS_OPT_IN((&stem_pool_kernel<false, FCP_STEM_PW, true>), lds);
-  hipLaunchKernelGGL((stem_pool_kernel<false, FCP_STEM_PW, true>), dim3(grid), dim3(G::NT), lds, (hipStream_t)stream, p);
+  FCP_LDS_OPT_IN((&stem_pool_kernel<false, true>), lds);
+  hipLaunchKernelGGL((stem_pool_kernel<false, true>), dim3(grid), dim3(G::NT), lds, (hipStream_t)stream, p);
   FCP_LAUNCH_OK();
   return 0;
 }

@@ -334,9 +334,6 @@ def thread_main_stream(dev):
     return st["main"]
 
 
-BIG_TILES = os.environ.get("FCP_BIG_TILES", "1") != "0"   # offer the 256-row kernel to the autotuner
-BALANCE_TAIL = os.environ.get("FCP_BALANCE_TAIL", "1") != "0"   # and its balanced M-tile schedule (FCP_CONV_BALANCE_TAIL)
-
 _budget = threading.local()
 
 
@@ -711,7 +708,7 @@ def conv(pc: PackedConv, x: Act, out: Act | None = None, *, act_slope: float = 1
     if tile_n is None and tile_m is None and (pc.cout > 64 or halo_ok) and (Autotune.enabled or Autotune.cache):
         key = (pc.cin, pc.cout, pc.kh, pc.kw, pc.stride, m, int(in_up2), res1 is not None, res2 is not None,
                pc.precision, x.fmt, out.fmt, None if x2 is None else (x2.c, x2_stride), d.cu_budget)
-        cands = tile_candidates(pc.cout, halo_ok, wide_ok and HALO_WIDE, big_ok and BIG_TILES, BALANCE_TAIL)
+        cands = tile_candidates(pc.cout, halo_ok, wide_ok, big_ok)
         best = Autotune.cache.get(key)          # a tuned shape keeps its tile after tuning is switched off
         if best is not None and tuple(best) not in cands:
             with Autotune._lock:                # (save() walks the cache under the same lock in another GPU worker thread)
@@ -774,7 +771,7 @@ def conv(pc: PackedConv, x: Act, out: Act | None = None, *, act_slope: float = 1
     return out
 
 
-def tile_candidates(cout: int, halo_ok: bool, wide_ok: bool, big_ok: bool, balance_tail: bool = True):
+def tile_candidates(cout: int, halo_ok: bool, wide_ok: bool, big_ok: bool):
     """The tile vocabulary the tuner chooses from for one conv shape, in order of preference (``Autotune.pick``).  The tuned
     tables store these tuples: a change of their MEANING (not the mere addition of a shape class) needs a new
     ``Autotune.TABLE_VERSION`` — tests/test_autotune_cache_cpu.py pins the vocabulary's digest to the version."""
@@ -786,8 +783,7 @@ def tile_candidates(cout: int, halo_ok: bool, wide_ok: bool, big_ok: bool, balan
     if big_ok:
         big = [(256, 128)] + ([(256, 256)] if cout >= 256 else []) + ([(256, 192)] if 128 < cout <= 192 else [])
         cands += big
-        if balance_tail:          # the same tiles with the last dispatch round cut into shorter M-tiles (same bits)
-            cands += [(tm, tn, N.CONV_BALANCE_TAIL) for tm, tn in big]
+        cands += [(tm, tn, N.CONV_BALANCE_TAIL) for tm, tn in big]   # the last dispatch round cut into shorter M-tiles (same bits)
     return cands
 
 
@@ -809,7 +805,7 @@ def chain_supported(pc2: PackedConv | None, pc3: PackedConv, pc1n: PackedConv | 
     if pc1n is None:          # expand form: conv3 + identity only (1x1 256 -> 1024 + residual; layer 3), no next conv1
         return pc2 is None and residual and not cb and one(pc3, 256, 1024)
     if cb:
-        return pc2 is None and not residual and cb == 256 and one(pc3, 384, 512) and one(pc1n, 512, 128) and CHAIN_TWO_SOURCE
+        return pc2 is None and not residual and cb == 256 and one(pc3, 384, 512) and one(pc1n, 512, 128)
     if pc2 is not None:
         return ((pc2.cin, pc2.cout, pc2.kh, pc2.kw, pc2.stride, pc2.pad) == (64, 64, 3, 3, 1, 1) and residual
                 and one(pc3, 64, 256) and (one(pc1n, 256, 64) or one(pc1n, 256, 128)))
@@ -819,31 +815,17 @@ def chain_supported(pc2: PackedConv | None, pc3: PackedConv, pc1n: PackedConv | 
     return one(pc3, 128, 256) and one(pc1n, 256, 64)
 
 
-HALO_WIDE = os.environ.get("FCP_HALO_WIDE", "1") != "0"       # A/B switch: offer the wide halo-tile kernel to the tile tuner
-CHAIN_TILE_M = int(os.environ.get("FCP_CHAIN_TILE_M", "0"))   # 0 / 128: 4-wave tiles of 128 pixels; 256: 8-wave tiles where they fit
-# conv2 forms (layer 1): 8 x 16 pixel patches whose halo is staged once per channel slice (tile_m = 16 in the descriptor)
-# instead of 128 consecutive pixels fetched once per tap; same bits.  FCP_CHAIN_PATCH=0 = the linear tiles.
-CHAIN_PATCH = os.environ.get("FCP_CHAIN_PATCH", "1") != "0"
-# ... and a block whose output only a stride-2 consumer reads stores the even pixels only (bottleneck_chain(out_even_only=True))
-CHAIN_SPARSE_OUT = os.environ.get("FCP_CHAIN_SPARSE_OUT", "1") != "0"
-# layer2.0's two-source conv3 (+ downsample) and layer2.1.conv1 as one pair launch (A/B switch: 0 = the two conv launches)
-CHAIN_TWO_SOURCE = os.environ.get("FCP_CHAIN_TWO_SOURCE", "1") != "0"
-# layer-3 identity blocks: "pair-only" (default) = conv3 + identity + next conv1 in one launch (one wave per SIMD), the stand-alone
-# layer3.5.conv3 on the tuned conv tile; "pair" = the same, layer3.5.conv3 on the expand form; "expand" = every conv3 + identity on
-# the expand form (two workgroups per CU) followed by an ordinary conv1 launch.  Same bits; a three-way tie in the in-call A/B
-# (profiles/r05_probes.md section 10), so the product keeps the launch mix its profiles were taken with.
-L3_FORM = os.environ.get("FCP_L3_FORM", "pair-only")
-
 
 def bottleneck_chain(pc2: PackedConv | None, pc3: PackedConv, pc1n: PackedConv, t1: Act, res: Act | None,
-                     out: Act | None = None, t1n: Act | None = None, tile_m: int | None = None, out_even_only: bool = False,
+                     out: Act | None = None, t1n: Act | None = None, tile_m: int = 0, out_even_only: bool = False,
                      t1b: Act | None = None, t1b_stride: int = 1):
     """One launch for  out = relu(conv3(relu(conv2(t1))) [+ res]),  t1n = relu(conv1n(out))  (BatchNorm folded): conv2 /
     conv3 of a bottleneck and conv1 of the next block; ``pc2`` None: the pair forms (no conv2, see ``chain_supported``).
-    Bit-identical to the separate ``conv`` calls.  Returns (out, t1n), both split32.  ``out_even_only`` (conv2 forms on patch
-    tiles): ``out`` is only stored at pixels with even y and even x — for a block whose output nothing but a stride-2 consumer
+    Bit-identical to the separate ``conv`` calls.  Returns (out, t1n), both split32.  ``out_even_only`` (conv2 forms):
+    ``out`` is only stored at pixels with even y and even x — for a block whose output nothing but a stride-2 consumer
     reads (the other three quarters of the tensor are never written nor read; ``t1n`` is complete).  Ignored, i.e. a full
-    ``out``, where the patch form is not in use or a ``RangeMonitor`` wants to see the whole tensor.  ``t1b`` (two-source
+    ``out``, for the pair forms or where a ``RangeMonitor`` wants to see the whole tensor.  ``tile_m``: the descriptor's tile
+    hint, passed through (the library picks the form by shape and may ignore it; every value gives the same bits).  ``t1b`` (two-source
     pair): the trailing ``t1b.c`` input channels of conv3 are read from ``t1b`` at ``(y * t1b_stride, x * t1b_stride)`` —
     what ``conv(..., x2=, x2_stride=)`` does for the stand-alone two-source conv."""
     cb = t1b.c if t1b is not None else 0
@@ -861,9 +843,7 @@ def bottleneck_chain(pc2: PackedConv | None, pc3: PackedConv, pc1n: PackedConv, 
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     opt = lambda pc, f: None if pc is None else getattr(pc, f)
-    if tile_m is None:
-        tile_m = 16 if (pc2 is not None and CHAIN_PATCH and CHAIN_TILE_M == 0) else (CHAIN_TILE_M if (pc2 is not None or CHAIN_TILE_M not in (16, 32)) else 0)
-    flags = N.CHAIN_OUT_EVEN_ONLY if (out_even_only and tile_m in (16, 32) and CHAIN_SPARSE_OUT and RangeMonitor.active is None) else 0
+    flags = N.CHAIN_OUT_EVEN_ONLY if (out_even_only and pc2 is not None and RangeMonitor.active is None) else 0
     d = None
     if T.ENABLED and out is None and t1n is None:
         # FCP_BOUNDARY=torch: the registered custom op allocates and returns both tensors

@@ -38,16 +38,14 @@ class RetinaFace:
         self.device = None
         self._p = None
         self.precision = 0
-        self.fused_stem = os.environ.get("FCP_FUSED_STEM", "1") != "0"   # fp16x3 path: uint8 -> stem + pool in one launch
-        self.fused_stem_conv1 = os.environ.get("FCP_FUSED_STEM_CONV1", "1") != "0"   # ... + layer1.0.conv1 in the same launch
         # The network runs on the two halves of a batch concurrently, on two HIP streams: the tail wave of one
         # half's launch (layers 3-4 fill only ~78 % of their last round of workgroups) overlaps the head of the
         # other's.  Images are independent, so the result is bit-identical to the single-stream pass.
-        # conv2 + conv3 of an identity bottleneck and conv1 of the next block in one launch (layer 1; bit-identical)
-        self.fused_chain = os.environ.get("FCP_FUSED_CHAIN", "1") != "0"
+        # conv2 + conv3 of an identity bottleneck and conv1 of the next block in one launch (bit-identical; False = the
+        # stand-alone convs, the reference tests/test_chain_gpu.py compares against)
+        self.fused_chain = True
         self.streams = int(os.environ.get("FCP_DET_STREAMS", "2"))
         self.min_images_per_stream = 6      # tools/probe_min_images_per_stream.py: batch 8 is best on one stream (1210 vs 1165 faces/s), batch 12 on two (1308 vs 1288)
-        self.split_cu_budget = os.environ.get("FCP_SPLIT_CU_BUDGET", "1") != "0"
         self._tls = threading.local()
 
     # ------------------------------------------------------------------ load
@@ -102,7 +100,7 @@ class RetinaFace:
             tuning, E.Autotune.enabled = E.Autotune.enabled, False        # a check must not spend time tuning tiles
             try:
                 with E.RangeMonitor() as mon:
-                    heads = self.forward_heads(None, images_u8) if "stem_fused" in self._p and self.fused_stem else \
+                    heads = self.forward_heads(None, images_u8) if "stem_fused" in self._p else \
                         self.forward_heads(E.u8_to_nhwc4(images_u8, sub=(123.0, 117.0, 104.0)))
                 rep = {"launch_absmax": mon.check("RetinaFace"), "limit": E.RangeMonitor.LIMIT, "head_rel_diff": None}
                 if sd is not None:
@@ -190,7 +188,7 @@ class RetinaFace:
             hp, wp = ((h - 1) // 2) // 2 + 1, ((w - 1) // 2) // 2 + 1
             cat = E.Act.empty(n, hp, wp, 128, images_u8.device, f)                   # [conv2 out | pooled stem]
             c1 = p["blocks"][0]["c1"]
-            if self.fused_stem_conv1 and f == 1 and E.stem_conv1_supported(c1):
+            if f == 1 and E.stem_conv1_supported(c1):
                 # ... and conv1 of layer1.0 in the same launch: the pooled map is written (downsample branch) but not re-read
                 x, stem_t1 = E.stem_relu_pool_u8(p["stem_fused"], images_u8, cat.slice(64, 64), conv1=c1)
             else:
@@ -235,12 +233,6 @@ class RetinaFace:
                     feats.append(x)
                 continue
             o = E.conv(blk["c2"], o, act_slope=0.0, out_fmt=f)
-            if chain and blk["ds"] is None and E.chain_supported(None, blk["c3"], None) and (
-                    E.L3_FORM == "expand" or (E.L3_FORM == "pair" and (nxt is None or not E.chain_supported(None, blk["c3"], nxt["c1"])))):
-                x, _ = E.bottleneck_chain(None, blk["c3"], None, o, x)       # conv3 + identity on the expand form; conv1 follows as a launch
-                if blk["feat"]:
-                    feats.append(x)
-                continue
             if (chain and blk["ds"] is None and nxt is not None and E.chain_supported(None, blk["c3"], nxt["c1"])):
                 x, pre = E.bottleneck_chain(None, blk["c3"], nxt["c1"], o, x)          # conv3 (+ identity) + next conv1 (layers 2-3)
                 if blk["feat"]:
@@ -288,7 +280,7 @@ class RetinaFace:
         bounds = [n * i // k for i in range(k + 1)]
         side = self._side_streams(dev, k)
         # each sub-batch lays out the last dispatch round of its 256-row conv launches for its share of the CUs
-        cus = E.device_props(dev).multi_processor_count // k if self.split_cu_budget else 0
+        cus = E.device_props(dev).multi_processor_count // k
         for st, a, b in zip(side, bounds[:-1], bounds[1:]):
             tuned = len(E.Autotune.cache)
             if st != cur:
@@ -315,7 +307,7 @@ class RetinaFace:
         """
         if self.strategy not in STRATEGIES:
             raise ValueError(f"Unsupported startegy: {self.strategy}")
-        fused = x4 is None and "stem_fused" in self._p and self.fused_stem
+        fused = x4 is None and "stem_fused" in self._p   # fp16x3 path: uint8 -> stem + pool in one launch
         if x4 is None and not fused:
             # RGB order is kept; means are (R,G,B) = (123,117,104) (retinaface.py:450)
             x4 = E.u8_to_nhwc4(images_u8, sub=(123.0, 117.0, 104.0))

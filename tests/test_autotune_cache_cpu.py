@@ -97,7 +97,7 @@ def test_autotune_off_still_reads_the_tables_and_tables_have_their_own_switch(tu
         assert out.stdout.split("\n")[-2] == want, out.stdout + out.stderr
 
 
-def test_tile_vocabulary_is_pinned_to_the_table_version():
+def test_tile_candidates_vocabulary_is_pinned_to_the_table_version():
     """The tuned tables store tile tuples; their meaning is fixed per ``Autotune.TABLE_VERSION``.  Whoever changes what
     ``tile_candidates`` offers (or the flag bit a third element carries) gets this failure and either bumps TABLE_VERSION
     and this pin (the shipped table must then be re-measured: tools/dump_autotune.py) or restores the vocabulary."""
@@ -108,7 +108,7 @@ def test_tile_vocabulary_is_pinned_to_the_table_version():
         for halo in (False, True):
             for wide in (False, True):
                 for big in (False, True):
-                    vocab.append((cout, halo, wide, big, E.tile_candidates(cout, halo, wide, big, True)))
+                    vocab.append((cout, halo, wide, big, E.tile_candidates(cout, halo, wide, big)))
     digest = hashlib.sha256(repr(vocab).encode()).hexdigest()[:16]
     pinned = {13: PINNED_VOCAB_13}
     assert E.Autotune.TABLE_VERSION in pinned, "TABLE_VERSION changed: pin the new vocabulary digest here"
