@@ -267,15 +267,52 @@ class RetinaFace:
         main = E.thread_streams(dev)["main"]
         return E.thread_side_streams(dev, k, with_main=main is not None and torch.cuda.current_stream(dev) == main)
 
-    def _forward_heads_split(self, images_u8: torch.Tensor):
+    # The fp16x3 kernels address each operand with 32-bit byte offsets and refuse tensors of 4 GiB or more (fcp_conv.hip,
+    # fcp_bneck_chain.hip).  The largest activation of the network is layer 1's output: 256 channels at 1/4 resolution, 64 MiB
+    # per 1024^2 image, so one launch takes at most 63 such images.
+    MAX_OPERAND_BYTES = 0xFFFFFFF0
+
+    def _images_per_launch(self, h: int, w: int) -> int | None:
+        """Most images one launch of the network may carry at (h, w) (None: no limit, the exact-fp32 kernels switch to 64-bit
+        addressing by themselves)."""
+        if self.precision != 1:
+            return None
+        hp, wp = ((h - 1) // 2) // 2 + 1, ((w - 1) // 2) // 2 + 1
+        return max(1, (self.MAX_OPERAND_BYTES - 1) // (4 * 256 * hp * wp))
+
+    def _streams_for(self, n: int) -> int:
+        """Sub-batches (HIP streams) ``_forward_heads_split`` runs n images on."""
+        k = min(self.streams, n // max(1, self.min_images_per_stream))
+        return 1 if k < 2 or torch.cuda.is_current_stream_capturing() else k
+
+    def _chunked(self, n: int, h: int, w: int, dev, run, split: bool = True):
+        """Head maps of n images, computed by ``run(a, b, heads_out)`` over the fewest consecutive image chunks [a, b) that keep
+        every launch below ``MAX_OPERAND_BYTES`` (``split``: ``run`` spreads a chunk over ``_streams_for`` sub-batches, each
+        writing its rows of the shared head maps); ``run(0, n, None)`` itself, i.e. the very same launches, when the batch fits."""
+        per = self._images_per_launch(h, w)
+        q = 1
+        while True:
+            bounds = [n * i // q for i in range(q + 1)]
+            sub = lambda c: -(-c // (self._streams_for(c) if split else 1))           # images per launch of a c-image chunk
+            if per is None or all(sub(b - a) <= per for a, b in zip(bounds[:-1], bounds[1:])):
+                break
+            q += 1
+        if q == 1:
+            return run(0, n, None)
+        heads = [E.Act.empty(n, -(-h // s), -(-w // s), 32, dev) for s in (8, 16, 32)]
+        for a, b in zip(bounds[:-1], bounds[1:]):
+            run(a, b, [E.Act(hd.buf[a:b]) for hd in heads])
+        return heads
+
+    def _forward_heads_split(self, images_u8: torch.Tensor, heads_out=None):
         """``forward_heads`` of a uint8 batch, its ``self.streams`` contiguous sub-batches enqueued on side streams
         that fork from and re-join the caller's stream; every sub-batch writes its rows of the shared head maps."""
         n, h, w, _ = images_u8.shape
-        k = min(self.streams, n // max(1, self.min_images_per_stream))
-        if k < 2 or torch.cuda.is_current_stream_capturing():
-            return self.forward_heads(None, images_u8)
+        k = self._streams_for(n)
+        if k < 2:
+            return self.forward_heads(None, images_u8, heads_out)
         dev = images_u8.device
-        heads = [E.Act.empty(n, -(-h // s), -(-w // s), 32, dev) for s in (8, 16, 32)]
+        heads = heads_out if heads_out is not None else [E.Act.empty(n, -(-h // s), -(-w // s), 32, dev) for s in (8, 16, 32)]
         cur = torch.cuda.current_stream(dev)
         bounds = [n * i // k for i in range(k + 1)]
         side = self._side_streams(dev, k)
@@ -314,11 +351,12 @@ class RetinaFace:
         if fused:
             images_u8 = images_u8.contiguous()
             (n, h, w), dev = images_u8.shape[:3], images_u8.device
-            heads = self._forward_heads_split(images_u8)
+            heads = self._chunked(n, h, w, dev, lambda a, b, ho: self._forward_heads_split(images_u8[a:b], ho))
         else:
             n, h, w = x4.n, x4.h, x4.w
             dev = x4.buf.device
-            heads = self.forward_heads(x4)
+            heads = self._chunked(n, h, w, dev, lambda a, b, ho: self.forward_heads(x4 if (a, b) == (0, n) else E.Act(x4.buf[a:b]),
+                                                                                    None, ho), split=False)
         P = sum(2 * (-(-h // s)) * (-(-w // s)) for s in (8, 16, 32))
         f32, i32 = torch.float32, torch.int32
         cand_score = torch.empty((n, P), dtype=f32, device=dev)
