@@ -79,6 +79,7 @@ SIGNATURES = {
     "fcp_label_mask_u8": [_P, _L, C.c_uint32, _P, _P],
     "fcp_bicubic_down4_u8": [_P, _I, _I, _I, _P, _P],
     "fcp_warp_affine_u8": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "fcp_warp_affine_u8_float": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "fcp_build_batch_u8": [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P],
 }
 EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes"] + list(SIGNATURES)

@@ -50,11 +50,15 @@ class Cropper:
         device: str | torch.device = "cuda:0",
         weights: dict | None = None,
         precision: str | None = None,
+        warp_family: str | None = None,
     ):
         """Arguments as in the reference (cropper.py:139-156).  ``device`` must be a GPU
         (``"cuda:N"``); ``weights`` optionally maps "retinaface"/"rrdb"/"bisenet" to a
         state dict / path / "generated" (default: the real checkpoints, from ``$FCP_WEIGHTS_DIR`` or the
-        torch hub cache, else downloaded like the reference does; there is no silent random-weight fallback)."""
+        torch hub cache, else downloaded like the reference does; there is no silent random-weight fallback).
+        ``warp_family``: which cv2.warpAffine algorithm the crops reproduce byte for byte — "fixed" (OpenCV's classic
+        fixed-point warp), "float32" (the float warp of newer OpenCV builds) or "auto" (whichever the installed cv2 runs,
+        "fixed" without cv2); None = ``$FCP_WARP_FAMILY``, else "fixed" (``align.resolve_warp_family``)."""
         self.output_size = output_size
         self.output_format = output_format
         self.resize_size = resize_size
@@ -107,6 +111,7 @@ class Cropper:
 
         self._init_models()
         self._init_landmarks_target()
+        self.warp_family = align.resolve_warp_family(warp_family, self.padding, self.device)
 
     # ------------------------------------------------------------------ init
     def _init_models(self):
@@ -144,7 +149,7 @@ class Cropper:
         pads = None if paddings is None else torch.as_tensor(np.asarray(paddings), dtype=torch.int32)
         idx = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int32)
         crops, ok, _ = align.crop_align(images_dev, idx, landmarks_dev, self.landmarks_target, self.output_size,
-                                        align.border_code(self.padding), self.allow_skew, pads)
+                                        align.border_code(self.padding), self.allow_skew, pads, family=self.warp_family)
         return crops, ok
 
     def crop_align(self, images, padding, indices, landmarks_source) -> np.ndarray:

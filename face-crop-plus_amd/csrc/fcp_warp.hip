@@ -11,6 +11,10 @@
 // weights = (32-fy)(32-fx)*32 etc. (sum 32768), out = (sum + 16384) >> 15,
 // borders through cv::borderInterpolate.  Built with -ffp-contract=off so the
 // double expressions round exactly like the scalar C++ they restate.
+//
+// warp (float family, opt-in): the float32 SIMD linear warp of newer OpenCV
+// builds — same inverse map rounded to float, sx = x*m0 + (y*m1 + m2) and the
+// bilinear blend in separately rounded float32 ops, rintf to uint8.
 #include "fcp_common.h"
 #include "fcp_hip.h"
 
@@ -245,6 +249,125 @@ __global__ void __launch_bounds__(256) warp_affine_kernel(
   }
 }
 
+// Bilinear blend of the float family: two row lerps, one column lerp, each a separately rounded float32 op (no FMA:
+// the library is built with -ffp-contract=off), then round-half-even and saturate to uint8.
+__device__ __forceinline__ uint8_t lerp2_f32(float p00, float p01, float p10, float p11, float ax, float ay) {
+  const float v0 = p00 + ax * (p01 - p00);
+  const float v1 = p10 + ax * (p11 - p10);
+  const float v = rintf(v0 + ay * (v1 - v0));
+  return (uint8_t)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v));
+}
+
+// The float32 family of cv::warpAffine(INTER_LINEAR) (the SIMD linear warp of newer OpenCV builds): source coordinates and
+// bilinear weights in float32, one rounding at the end.  Same launch geometry, un-padding, border handling and stores as
+// warp_affine_kernel; only the coordinate / weight arithmetic differs.
+template <int PX>
+__global__ void __launch_bounds__(256) warp_affine_float_kernel(
+    const uint8_t* __restrict__ images, int n, int h, int w, const int* __restrict__ img_idx,
+    const double* __restrict__ mat, const int* __restrict__ ok, const int* __restrict__ paddings,
+    int out_h, int out_w, int border, uint8_t* __restrict__ out) {
+  const int face = blockIdx.y;
+  const int groups_per_row = (out_w + PX - 1) / PX;
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = g < groups_per_row * out_h;
+  const int y = active ? g / groups_per_row : 0;
+  const int x0 = active ? (g - y * groups_per_row) * PX : 0;
+  uint8_t* dst = out + (((long)face * out_h + y) * out_w + x0) * 3;
+  uint8_t px[PX * 3];
+#pragma unroll
+  for (int q = 0; q < PX * 3; ++q) px[q] = 0;
+
+  const bool valid = ok == nullptr || ok[face] != 0;       // uniform over the workgroup (one face per blockIdx.y)
+  // inverse map in double exactly as warp_affine_kernel, then each coefficient rounded to float once
+  __shared__ float sM[6];
+  if (valid && threadIdx.x == 0) {
+    double M[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) M[q] = mat[(long)face * 6 + q];
+    double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0 ? 1. / D : 0;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+    const double b1 = -M[0] * M[2] - M[1] * M[5];
+    const double b2 = -M[3] * M[2] - M[4] * M[5];
+    M[2] = b1; M[5] = b2;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) sM[q] = (float)M[q];
+  }
+  __syncthreads();
+  if (!active) return;
+  if (valid) {
+    const int img = img_idx[face];
+    int pt = 0, pb = 0, pl = 0, pr = 0;
+    if (paddings != nullptr) { pt = paddings[img * 4]; pb = paddings[img * 4 + 1]; pl = paddings[img * 4 + 2]; pr = paddings[img * 4 + 3]; }
+    const int sh = h - pt - pb, sw = w - pl - pr;  // un-padded slice (cropper.py:538-539)
+    const long sstep = (long)w * 3;
+    const long s0off = ((long)img * h + pt) * sstep + (long)pl * 3;
+    const uint8_t* S0 = images + s0off;
+    const long total = (long)n * h * sstep;          // bytes of the batch: bound of the 12-byte loads
+    const float m0 = sM[0], m1 = sM[1], m2 = sM[2], m3 = sM[3], m4 = sM[4], m5 = sM[5];
+    const float fy = (float)y;
+    const float bx = fy * m1 + m2, by = fy * m4 + m5;     // the (y*m1 + m2) term of sx = x*m0 + (y*m1 + m2)
+    const int width1 = sw - 1 > 0 ? sw - 1 : 0, height1 = sh - 1 > 0 ? sh - 1 : 0;
+#pragma unroll
+    for (int q = 0; q < PX; ++q) {
+      const int x = x0 + q;
+      if (x >= out_w) break;
+      const float fx = (float)x;
+      const float sxf = fx * m0 + bx, syf = fx * m3 + by;
+      const float ixf = floorf(sxf), iyf = floorf(syf);
+      const float ax = sxf - ixf, ay = syf - iyf;
+      // clamped in float before the conversion; the clamped value drives the border logic below
+      const int sx = (int)fminf(fmaxf(ixf, -32768.f), 32767.f), sy = (int)fminf(fmaxf(iyf, -32768.f), 32767.f);
+      if ((unsigned)sx < (unsigned)width1 && (unsigned)sy < (unsigned)height1) {
+        const long o0 = s0off + sy * sstep + sx * 3, o1 = o0 + sstep;
+        if (((o1 & ~3L) + 12) <= total) {
+          const unsigned long long r0 = load6(images, o0), r1 = load6(images, o1);
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            px[q * 3 + c] = lerp2_f32((float)(int)((r0 >> (8 * c)) & 255u), (float)(int)((r0 >> (8 * c + 24)) & 255u),
+                                      (float)(int)((r1 >> (8 * c)) & 255u), (float)(int)((r1 >> (8 * c + 24)) & 255u), ax, ay);
+          continue;
+        }
+        const uint8_t* v0 = images + o0;
+        const uint8_t* v2 = v0 + sstep;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          px[q * 3 + c] = lerp2_f32(v0[c], v0[3 + c], v2[c], v2[3 + c], ax, ay);
+        continue;
+      }
+      if (border == 0 && (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0)) continue;  // all-constant: 0
+      int sx0, sx1, sy0, sy1;
+      if (border == 1) {
+        sx0 = sx < 0 ? 0 : (sx < sw ? sx : sw - 1);
+        sx1 = sx + 1 < 0 ? 0 : (sx + 1 < sw ? sx + 1 : sw - 1);
+        sy0 = sy < 0 ? 0 : (sy < sh ? sy : sh - 1);
+        sy1 = sy + 1 < 0 ? 0 : (sy + 1 < sh ? sy + 1 : sh - 1);
+      } else {
+        sx0 = border_interp(sx, sw, border); sx1 = border_interp(sx + 1, sw, border);
+        sy0 = border_interp(sy, sh, border); sy1 = border_interp(sy + 1, sh, border);
+      }
+      const uint8_t zero[3] = {0, 0, 0};                   // a constant-border tap outside the slice reads 0
+      const uint8_t* v0 = (sx0 >= 0 && sy0 >= 0) ? S0 + sy0 * sstep + sx0 * 3 : zero;
+      const uint8_t* v1 = (sx1 >= 0 && sy0 >= 0) ? S0 + sy0 * sstep + sx1 * 3 : zero;
+      const uint8_t* v2 = (sx0 >= 0 && sy1 >= 0) ? S0 + sy1 * sstep + sx0 * 3 : zero;
+      const uint8_t* v3 = (sx1 >= 0 && sy1 >= 0) ? S0 + sy1 * sstep + sx1 * 3 : zero;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) px[q * 3 + c] = lerp2_f32(v0[c], v1[c], v2[c], v3[c], ax, ay);
+    }
+  }
+  if (PX == 4 && x0 + 4 <= out_w && (out_w & 3) == 0) {
+    uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);  // 12 aligned bytes
+    d32[0] = px[0] | (px[1] << 8) | (px[2] << 16) | ((uint32_t)px[3] << 24);
+    d32[1] = px[4] | (px[5] << 8) | (px[6] << 16) | ((uint32_t)px[7] << 24);
+    d32[2] = px[8] | (px[9] << 8) | (px[10] << 16) | ((uint32_t)px[11] << 24);
+  } else {
+    for (int q = 0; q < PX && x0 + q < out_w; ++q) {
+      dst[q * 3] = px[q * 3]; dst[q * 3 + 1] = px[q * 3 + 1]; dst[q * 3 + 2] = px[q * 3 + 2];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int fcp_estimate_transform_counted(const float* src, const float* dst, int f, int k, int allow_skew,
@@ -272,6 +395,21 @@ extern "C" int fcp_warp_affine_u8(const uint8_t* images, int n, int h, int w, co
   FCP_REQUIRE(f <= 65535, "warp_affine: at most 65535 faces per call");
   const int groups = ((out_w + 3) / 4) * out_h;
   hipLaunchKernelGGL((warp_affine_kernel<4>), dim3(fcp_cdiv(groups, 256), f), dim3(256), 0,
+                     (hipStream_t)stream, images, n, h, w, img_idx, mat, ok, paddings, out_h, out_w, border,
+                     out);
+  FCP_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int fcp_warp_affine_u8_float(const uint8_t* images, int n, int h, int w, const int32_t* img_idx,
+                                        const double* mat, const int32_t* ok, const int32_t* paddings, int f,
+                                        int out_h, int out_w, int border, uint8_t* out, fcp_stream_t stream) {
+  FCP_REQUIRE(images && img_idx && mat && out, "warp_affine_float: null pointer");
+  FCP_REQUIRE(n > 0 && h > 0 && w > 0 && f > 0 && out_h > 0 && out_w > 0, "warp_affine_float: bad sizes");
+  FCP_REQUIRE(border >= 0 && border <= 4, "warp_affine_float: unsupported border mode %d", border);
+  FCP_REQUIRE(f <= 65535, "warp_affine_float: at most 65535 faces per call");
+  const int groups = ((out_w + 3) / 4) * out_h;
+  hipLaunchKernelGGL((warp_affine_float_kernel<4>), dim3(fcp_cdiv(groups, 256), f), dim3(256), 0,
                      (hipStream_t)stream, images, n, h, w, img_idx, mat, ok, paddings, out_h, out_w, border,
                      out);
   FCP_LAUNCH_OK();

@@ -2,7 +2,7 @@
 // namespace ... stateless ops on the current HIP stream, tensors in/out, no hidden global state").
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
-//     warp_affine_u8 / bicubic_down4_round / parse_argmax_hist
+//     warp_affine_u8 / warp_affine_u8_float / bicubic_down4_round / parse_argmax_hist
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -262,19 +262,34 @@ std::tuple<Tensor, Tensor> similarity_from_5pt(const Tensor& src, const Tensor& 
   return {mat, okf};
 }
 
-Tensor warp_affine_u8(const Tensor& images, const Tensor& img_idx, const Tensor& mat, const c10::optional<Tensor>& okf,
-                      const c10::optional<Tensor>& paddings, int64_t out_w, int64_t out_h, int64_t border) {
+// Both warpAffine families share parameters and checks; only the C entry point differs.
+using warp_fn = int (*)(const uint8_t*, int, int, int, const int32_t*, const double*, const int32_t*, const int32_t*, int, int,
+                        int, int, uint8_t*, fcp_stream_t);
+
+Tensor warp_affine_with(warp_fn fn, const char* what, const Tensor& images, const Tensor& img_idx, const Tensor& mat,
+                        const c10::optional<Tensor>& okf, const c10::optional<Tensor>& paddings, int64_t out_w, int64_t out_h,
+                        int64_t border) {
   dev(images, "images", at::kByte); dev(img_idx, "img_idx", at::kInt); dev(mat, "mat", at::kDouble);
   FCP_DEVICE_GUARD(images);
   TORCH_CHECK(images.dim() == 4 && images.size(3) == 3, "images (n,h,w,3) uint8");
   const int64_t f = img_idx.size(0);
   TORCH_CHECK(mat.dim() == 3 && mat.size(0) == f && mat.size(1) == 2 && mat.size(2) == 3, "mat must be (", f, ", 2, 3) float64");
   Tensor out = at::empty({f, out_h, out_w, 3}, images.options());
-  ok(fcp_warp_affine_u8(images.data_ptr<uint8_t>(), (int)images.size(0), (int)images.size(1), (int)images.size(2),
-                        img_idx.data_ptr<int>(), mat.data_ptr<double>(), optp<int>(okf, "ok", at::kInt),
-                        optp<int>(paddings, "paddings", at::kInt), (int)f, (int)out_h, (int)out_w, (int)border,
-                        out.data_ptr<uint8_t>(), cur_stream()), "fcp::warp_affine_u8");
+  ok(fn(images.data_ptr<uint8_t>(), (int)images.size(0), (int)images.size(1), (int)images.size(2), img_idx.data_ptr<int>(),
+        mat.data_ptr<double>(), optp<int>(okf, "ok", at::kInt), optp<int>(paddings, "paddings", at::kInt), (int)f, (int)out_h,
+        (int)out_w, (int)border, out.data_ptr<uint8_t>(), cur_stream()), what);
   return out;
+}
+
+Tensor warp_affine_u8(const Tensor& images, const Tensor& img_idx, const Tensor& mat, const c10::optional<Tensor>& okf,
+                      const c10::optional<Tensor>& paddings, int64_t out_w, int64_t out_h, int64_t border) {
+  return warp_affine_with(fcp_warp_affine_u8, "fcp::warp_affine_u8", images, img_idx, mat, okf, paddings, out_w, out_h, border);
+}
+
+Tensor warp_affine_u8_float(const Tensor& images, const Tensor& img_idx, const Tensor& mat, const c10::optional<Tensor>& okf,
+                            const c10::optional<Tensor>& paddings, int64_t out_w, int64_t out_h, int64_t border) {
+  return warp_affine_with(fcp_warp_affine_u8_float, "fcp::warp_affine_u8_float", images, img_idx, mat, okf, paddings, out_w,
+                          out_h, border);
 }
 
 Tensor bicubic_down4_round(const Tensor& x4) {
@@ -326,6 +341,8 @@ TORCH_LIBRARY(fcp, m) {
   m.def("similarity_from_5pt(Tensor src, Tensor dst, bool allow_skew, Tensor? face_count=None, Tensor(a!)? valid_total=None) "
         "-> (Tensor, Tensor)");
   m.def("warp_affine_u8(Tensor images, Tensor img_idx, Tensor mat, Tensor? ok, Tensor? paddings, int out_w, int out_h, int border) -> Tensor");
+  m.def("warp_affine_u8_float(Tensor images, Tensor img_idx, Tensor mat, Tensor? ok, Tensor? paddings, int out_w, int out_h, "
+        "int border) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -344,6 +361,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("gather_faces", &gather_faces);
   m.impl("similarity_from_5pt", &similarity_from_5pt);
   m.impl("warp_affine_u8", &warp_affine_u8);
+  m.impl("warp_affine_u8_float", &warp_affine_u8_float);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

@@ -338,6 +338,23 @@ int fcp_warp_affine_u8(const uint8_t* images, int n, int h, int w,
                        const int32_t* paddings, int f, int out_h, int out_w, int border,
                        uint8_t* out, fcp_stream_t stream);
 
+/* The same warp in the float32 family of cv::warpAffine(INTER_LINEAR), the SIMD
+ * linear warp newer OpenCV builds run instead of the fixed-point tables; same
+ * parameters, argument checks, un-padding and borders as fcp_warp_affine_u8.
+ * The inverse map is computed in double as above, then each coefficient is
+ * rounded to float.  Per output pixel (x,y), every step a separately rounded
+ * float32 operation in this order (no FMA):
+ *   sx = x*m0 + (y*m1 + m2),  sy = x*m3 + (y*m4 + m5);
+ *   ix = floor(sx), ax = sx - ix (likewise iy, ay); ix, iy clamped to
+ *   [-32768, 32767] in float, then converted: they select the taps and the
+ *   all-outside test of the constant border (a constant-border tap reads 0);
+ *   v0 = p00 + ax*(p01 - p00), v1 = p10 + ax*(p11 - p10), v = v0 + ay*(v1 - v0);
+ *   out = round-half-even(v) saturated to 0..255. */
+int fcp_warp_affine_u8_float(const uint8_t* images, int n, int h, int w,
+                             const int32_t* img_idx, const double* mat, const int32_t* ok,
+                             const int32_t* paddings, int f, int out_h, int out_w, int border,
+                             uint8_t* out, fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */
