@@ -25,7 +25,9 @@ using fcp_conv::split8;
 using fcp_conv::split_chan_off;
 using fcp_conv::u32x4_t;
 
-// 4 pixels (12 bytes in, 64 bytes out) per thread iteration.
+// 4 pixels (12 bytes in, 64 bytes out) per thread iteration.  IN_ALIGNED: `in` is 4-byte aligned and the 12 bytes are three
+// dword loads; otherwise (an image of a batch whose h*w is not a multiple of 4) they are 12 byte loads.
+template <bool IN_ALIGNED>
 __global__ void __launch_bounds__(256) u8_to_nhwc4_kernel(const uint8_t* __restrict__ in,
                                                           float* __restrict__ out, long npix,
                                                           float s0, float s1, float s2, float div,
@@ -33,8 +35,16 @@ __global__ void __launch_bounds__(256) u8_to_nhwc4_kernel(const uint8_t* __restr
   const long nquad = npix >> 2;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += stride) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(in + q * 12);
-    const uint32_t w0 = src[0], w1 = src[1], w2 = src[2];
+    uint32_t w0, w1, w2;
+    if (IN_ALIGNED) {
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(in + q * 12);
+      w0 = src[0]; w1 = src[1]; w2 = src[2];
+    } else {
+      const uint8_t* src = in + q * 12;
+      w0 = src[0] | (uint32_t)src[1] << 8 | (uint32_t)src[2] << 16 | (uint32_t)src[3] << 24;
+      w1 = src[4] | (uint32_t)src[5] << 8 | (uint32_t)src[6] << 16 | (uint32_t)src[7] << 24;
+      w2 = src[8] | (uint32_t)src[9] << 8 | (uint32_t)src[10] << 16 | (uint32_t)src[11] << 24;
+    }
     const uint8_t b[12] = {(uint8_t)w0, (uint8_t)(w0 >> 8), (uint8_t)(w0 >> 16), (uint8_t)(w0 >> 24),
                            (uint8_t)w1, (uint8_t)(w1 >> 8), (uint8_t)(w1 >> 16), (uint8_t)(w1 >> 24),
                            (uint8_t)w2, (uint8_t)(w2 >> 8), (uint8_t)(w2 >> 16), (uint8_t)(w2 >> 24)};
@@ -229,11 +239,16 @@ extern "C" int fcp_u8_to_nhwc4_f32(const uint8_t* in, float* out, int64_t npix,
                                    const float* sub_host, float div, fcp_stream_t stream) {
   FCP_REQUIRE(in && out && sub_host, "u8_to_nhwc4: null pointer");
   FCP_REQUIRE(npix > 0, "u8_to_nhwc4: empty input");
-  FCP_REQUIRE(((uintptr_t)in & 3) == 0 && ((uintptr_t)out & 15) == 0, "u8_to_nhwc4: misaligned buffers");
+  FCP_REQUIRE(((uintptr_t)out & 15) == 0, "u8_to_nhwc4: output must be 16-byte aligned");
   const int do_div = div != 1.0f;
-  hipLaunchKernelGGL(u8_to_nhwc4_kernel, dim3(grid_for((npix + 3) / 4, 256)), dim3(256), 0,
-                     (hipStream_t)stream, in, out, (long)npix, sub_host[0], sub_host[1], sub_host[2], div,
-                     do_div);
+  if (((uintptr_t)in & 3) == 0)
+    hipLaunchKernelGGL(u8_to_nhwc4_kernel<true>, dim3(grid_for((npix + 3) / 4, 256)), dim3(256), 0,
+                       (hipStream_t)stream, in, out, (long)npix, sub_host[0], sub_host[1], sub_host[2], div,
+                       do_div);
+  else
+    hipLaunchKernelGGL(u8_to_nhwc4_kernel<false>, dim3(grid_for((npix + 3) / 4, 256)), dim3(256), 0,
+                       (hipStream_t)stream, in, out, (long)npix, sub_host[0], sub_host[1], sub_host[2], div,
+                       do_div);
   FCP_LAUNCH_OK();
   return 0;
 }

@@ -199,7 +199,9 @@ int fcp_bottleneck_chain_f16x3(const fcp_chain_desc* desc, fcp_stream_t stream);
 /* uint8 NHWC RGB (n,h,w,3) -> fp32 NHWC4 (n,h,w,4): out[c] = (in[c]-sub[c])/div, out[3]=0.
  * Replaces utils.py:222-224 (as_tensor) fused with retinaface.py:450-451 (mean
  * subtraction; the BGR swap is folded into the stem filter's channel order) or
- * with rrdb.py:142 (`.div(255)`).  sub_host: 3 floats on the host. */
+ * with rrdb.py:142 (`.div(255)`).  sub_host: 3 floats on the host.  `in` may have any
+ * byte alignment (an image of a uint8 batch whose h*w is not a multiple of 4 starts
+ * mid-word; 4-byte aligned inputs take a dword-load path); `out` must be 16-byte aligned. */
 int fcp_u8_to_nhwc4_f32(const uint8_t* in, float* out, int64_t npix,
                         const float* sub_host, float div, fcp_stream_t stream);
 
