@@ -36,6 +36,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-b", "--batch-size", type=int, default=8)
     p.add_argument("-n", "--num-processes", type=int, default=1)
     p.add_argument("-d", "--device", type=str, default="auto")
+    # absent from the parsed arguments unless given, so that they stay exactly the reference parser's; Cropper's default
+    # is "batch"
+    p.add_argument("-cs", "--crop-source", type=str, default=argparse.SUPPRESS, choices=("batch", "original"),
+                   help="sample crops from the resized batch (default 'batch', the reference's behaviour) or from the "
+                        "full-resolution file ('original')")
     return p
 
 

@@ -81,6 +81,9 @@ SIGNATURES = {
     "fcp_warp_affine_u8": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "fcp_warp_affine_u8_float": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "fcp_build_batch_u8": [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P],
+    "fcp_warp_affine_u8_ragged": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "fcp_warp_affine_u8_float_ragged": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "fcp_resize_area_ragged_u8": [_P, _L, _P, _P, _I, _P, _L, _P],
 }
 EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes"] + list(SIGNATURES)
 

@@ -155,3 +155,162 @@ def crop_align(images_u8, img_idx, landmarks, target, output_size, border=0, all
     mat, ok = estimate_transform(landmarks, target, allow_skew, face_count, valid_total)
     crops = warp_affine(images_u8, img_idx, mat, ok, paddings, output_size, border, family)
     return crops, ok, mat
+
+
+# ------------------------------------------------------------------ crop_source="original"
+# Crops sampled from the decoded files instead of the resized batch.  A face whose crop would minify the file by 2 or more
+# is sampled from a power-of-two INTER_AREA level of it instead (cv2.resize(O, (w >> L, h >> L), INTER_AREA)), so that the
+# final bilinear warp never minifies below 0.5.  Every step is a composition of OpenCV calls.
+
+_WARP_FAMILY_CODE = {"fixed": 0, "float32": 1}
+WARP_SRC_DTYPE = np.dtype([("off", "<i8"), ("h", "<i4"), ("w", "<i4")])                           # fcp_warp_src
+AREA_LEVEL_DTYPE = np.dtype([("src_off", "<i8"), ("sh", "<i4"), ("sw", "<i4"), ("dst_off", "<i8"), ("dh", "<i4"),
+                             ("dw", "<i4")])                                                     # fcp_area_level
+MAX_SOURCE_SIDE = 32767      # the fixed-point warp saturates source coordinates to short, as cv2.warpAffine does
+
+
+def source_landmarks(landmarks, w, h, ww, hh, left, top):
+    """Batch landmarks (F,k,2) float32 (the detector's, before un-padding) -> the same points in the decoded (h,w) image:
+    ``(x - left + 0.5) * (w / ww) - 0.5`` (and likewise y), float64 in that order, then float32 — the pixel-centre
+    convention of cv2.resize.  ``w, h, ww, hh, left, top``: scalars or per-face (F,) arrays of the image size, the resized
+    size in the batch and the batch padding in front of it (``batch.batch_geometry``)."""
+    lm = np.asarray(landmarks, np.float32).astype(np.float64)
+    col = lambda v: np.asarray(v, np.float64).reshape(-1, 1) if np.ndim(v) else np.float64(v)
+    rx = col(np.asarray(w, np.float64) / np.asarray(ww, np.float64))
+    ry = col(np.asarray(h, np.float64) / np.asarray(hh, np.float64))
+    out = np.empty(lm.shape, np.float32)
+    out[..., 0] = ((lm[..., 0] - col(left) + 0.5) * rx - 0.5).astype(np.float32)
+    out[..., 1] = ((lm[..., 1] - col(top) + 0.5) * ry - 0.5).astype(np.float32)
+    return out
+
+
+def pyramid_level(mat, w: int, h: int) -> int:
+    """The level L a face is cropped from: the largest L with ``s * 2**L <= 1``, s = sqrt(|det M[:, :2]|) the crop pixels
+    per source pixel (L = 0 when s > 0.5), capped so that the level keeps at least one pixel a side."""
+    m = np.asarray(mat, np.float64).reshape(6)
+    s = float(np.sqrt(abs(m[0] * m[4] - m[1] * m[3])))
+    if not (s > 0.0 and np.isfinite(s)):
+        return 0
+    lv = 0
+    while s * float(1 << (lv + 1)) <= 1.0 and (w >> (lv + 1)) >= 1 and (h >> (lv + 1)) >= 1:
+        lv += 1
+    return lv
+
+
+def compose_level(mat, w: int, h: int, level: int) -> np.ndarray:
+    """The forward transform M (2x3) re-expressed on level ``level`` of a (h,w) image, pixel-centre aligned:
+    M_L = M . [(x_L + 0.5) / sx - 0.5] with sx = (w >> L) / w, sy = (h >> L) / h.  M itself at level 0."""
+    m = np.asarray(mat, np.float64).reshape(2, 3)
+    if level == 0:
+        return m.copy()
+    sx, sy = (w >> level) / w, (h >> level) / h
+    out = np.empty((2, 3), np.float64)
+    for r in range(2):
+        out[r, 0] = m[r, 0] / sx
+        out[r, 1] = m[r, 1] / sy
+        out[r, 2] = m[r, 2] + m[r, 0] * (0.5 / sx - 0.5) + m[r, 1] * (0.5 / sy - 0.5)
+    return out
+
+
+def warp_affine_ragged(blob: torch.Tensor, srcs, mat: torch.Tensor, ok: torch.Tensor | None, output_size, border: int = 0,
+                       family: str = "fixed") -> torch.Tensor:
+    """One crop per face from its own (h,w,3) image inside the device uint8 ``blob``: ``srcs`` (F,3) int64 host array of
+    (byte offset, h, w) per face; ``mat`` (F,6) f64 device forward transforms; -> (F,oh,ow,3) u8."""
+    _check_family(family)
+    assert blob.dtype == torch.uint8 and blob.is_contiguous() and blob.dim() == 1
+    srcs = np.asarray(srcs, np.int64).reshape(-1, 3)
+    f = srcs.shape[0]
+    rec = np.zeros(f, WARP_SRC_DTYPE)
+    rec["off"], rec["h"], rec["w"] = srcs[:, 0], srcs[:, 1], srcs[:, 2]
+    ow, oh = int(output_size[0]), int(output_size[1])
+    mat = mat.contiguous()
+    if T.ENABLED:
+        return T.load().warp_affine_u8_ragged(blob, torch.from_numpy(rec.view(np.int64).reshape(f, 2)), mat, ok, ow, oh,
+                                              int(border), _WARP_FAMILY_CODE[family])
+    out = torch.empty((f, oh, ow, 3), dtype=torch.uint8, device=blob.device)
+    rec_dev = torch.from_numpy(rec.view(np.uint8)).to(blob.device)
+    entry = "fcp_warp_affine_u8_ragged" if family == "fixed" else "fcp_warp_affine_u8_float_ragged"
+    N.check(getattr(N.lib(), entry)(N.ptr(blob), blob.numel(), rec.ctypes.data, N.ptr(rec_dev), N.ptr(mat), N.ptr(ok), f, oh,
+                                    ow, int(border), N.ptr(out), N.stream_ptr()), entry)
+    return out
+
+
+def resize_area_ragged(src: torch.Tensor, levels, dst: torch.Tensor) -> None:
+    """cv2.resize(INTER_AREA) of every row of ``levels`` ((n,6) int64 host array of (src_off, sh, sw, dst_off, dh, dw)):
+    the (sh,sw,3) image at src_off of the device uint8 blob ``src`` into the (dh,dw,3) image at dst_off of ``dst``
+    (dst_off a multiple of 4), one launch.  ``dst`` may be ``src`` itself when the regions do not overlap."""
+    levels = np.asarray(levels, np.int64).reshape(-1, 6)
+    n = levels.shape[0]
+    if n == 0:
+        return
+    rec = np.zeros(n, AREA_LEVEL_DTYPE)
+    for k, name in enumerate(AREA_LEVEL_DTYPE.names):
+        rec[name] = levels[:, k]
+    if T.ENABLED:
+        T.load().resize_area_u8_ragged(src, torch.from_numpy(rec.view(np.int64).reshape(n, 4)), dst)
+        return
+    rec_dev = torch.from_numpy(rec.view(np.uint8)).to(src.device)
+    N.check(N.lib().fcp_resize_area_ragged_u8(N.ptr(src), src.numel(), rec.ctypes.data, N.ptr(rec_dev), n, N.ptr(dst),
+                                              dst.numel(), N.stream_ptr()), "fcp_resize_area_ragged_u8")
+
+
+def plan_sources(table, idx, mats, ok):
+    """Host plan of ``crop_align_sources`` for F faces: ``table`` (N,3) (offset, h, w) of the sources, ``idx`` (F,) image of
+    each face, ``mats`` (F,6) forward transforms, ``ok`` (F,) flags.  -> (level jobs for ``resize_area_ragged``: one per
+    distinct (image, L >= 1), packed after the last source at 16-byte aligned offsets; (F,3) source of each face for
+    ``warp_affine_ragged``; (F,6) matrices on those sources; (F,) levels; bytes of the blob the plan needs)."""
+    f = len(idx)
+    levels = np.zeros(f, np.int64)
+    for k in range(f):
+        if ok[k]:
+            levels[k] = pyramid_level(mats[k], int(table[idx[k], 2]), int(table[idx[k], 1]))
+    pos = (int((table[:, 0] + table[:, 1] * table[:, 2] * 3).max()) + 15) // 16 * 16 if len(table) else 0
+    slots, jobs = {}, []
+    for i, lv in sorted({(int(i), int(lv)) for i, lv in zip(idx, levels) if lv > 0}):
+        off, h, w = (int(v) for v in table[i])
+        hl, wl = h >> lv, w >> lv
+        slots[(i, lv)] = pos
+        jobs.append((off, h, w, pos, hl, wl))
+        pos += (hl * wl * 3 + 15) // 16 * 16
+    srcs = np.zeros((f, 3), np.int64)
+    mat_l = np.zeros((f, 6), np.float64)
+    for k in range(f):
+        off, h, w = (int(v) for v in table[idx[k]])
+        lv = int(levels[k])
+        srcs[k] = (off, h, w) if lv == 0 else (slots[(int(idx[k]), lv)], h >> lv, w >> lv)
+        mat_l[k] = compose_level(mats[k], w, h, lv).reshape(6)
+    return jobs, srcs, mat_l, levels, pos
+
+
+def crop_align_sources(blob: torch.Tensor, table, img_idx, landmarks, target, output_size, border=0, allow_skew=False,
+                       family="fixed"):
+    """Device crop_align from the decoded originals (crop_source="original").  ``blob``, ``table``: the sources as
+    ``batch.upload_sources`` / ``build_batch(keep_sources=True)`` return them (the blob has room for the levels after the
+    last source); ``img_idx`` (F,) image of each face; ``landmarks`` (F,k,2) in source pixel coordinates.
+    -> (crops (F,oh,ow,3) u8, ok (F,) i32 device, mat_L (F,6) f64 device: the transform applied to each face's level,
+    level (F,) int64 host).  The matrices come back to the host once (with ok) to pick the levels; the level images
+    are built in one launch, the crops in another."""
+    _check_family(family)
+    dev = blob.device
+    table = np.asarray(table, np.int64).reshape(-1, 3)
+    if len(table) and int(table[:, 1:].max()) > MAX_SOURCE_SIDE:
+        raise ValueError(f"crop_source='original' supports images of at most {MAX_SOURCE_SIDE} px a side")
+    idx = np.asarray(img_idx.cpu() if isinstance(img_idx, torch.Tensor) else img_idx, np.int64).reshape(-1)
+    f = len(idx)
+    if f == 0:
+        ow, oh = int(output_size[0]), int(output_size[1])
+        return (torch.empty((0, oh, ow, 3), dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty((0, 6), dtype=torch.float64, device=dev), np.zeros(0, np.int64))
+    landmarks = torch.as_tensor(landmarks).to(device=dev, dtype=torch.float32)
+    if not isinstance(target, torch.Tensor):
+        target = torch.from_numpy(np.ascontiguousarray(target, dtype=np.float32))
+    mat, ok = estimate_transform(landmarks, target.to(dev), allow_skew)
+    both = torch.cat([mat, ok.to(torch.float64)[:, None]], 1).cpu().numpy()      # one read-back: matrices and ok
+    jobs, srcs, mat_l, levels, need = plan_sources(table, idx, both[:, :6], both[:, 6] != 0)
+    if need > blob.numel():
+        raise ValueError(f"the source blob ({blob.numel()} bytes) has no room for the levels ({need} bytes needed): "
+                         f"upload the sources with batch.upload_sources or build_batch(keep_sources=True)")
+    resize_area_ragged(blob, jobs, blob)
+    mat_l_dev = torch.from_numpy(mat_l).to(dev)
+    crops = warp_affine_ragged(blob, srcs, mat_l_dev, ok, output_size, border, family)
+    return crops, ok, mat_l_dev, levels

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import align, trace
-from .batch import build_batch
+from .batch import batch_geometry, build_batch, upload_sources
 from .utils import get_ldm_slices, parse_landmarks_file, read_image, read_images, write_image
 
 
@@ -51,6 +51,7 @@ class Cropper:
         weights: dict | None = None,
         precision: str | None = None,
         warp_family: str | None = None,
+        crop_source: str = "batch",
     ):
         """Arguments as in the reference (cropper.py:139-156).  ``device`` must be a GPU
         (``"cuda:N"``); ``weights`` optionally maps "retinaface"/"rrdb"/"bisenet" to a
@@ -58,7 +59,17 @@ class Cropper:
         torch hub cache, else downloaded like the reference does; there is no silent random-weight fallback).
         ``warp_family``: which cv2.warpAffine algorithm the crops reproduce byte for byte — "fixed" (OpenCV's classic
         fixed-point warp), "float32" (the float warp of newer OpenCV builds) or "auto" (whichever the installed cv2 runs,
-        "fixed" without cv2); None = ``$FCP_WARP_FAMILY``, else "fixed" (``align.resolve_warp_family``)."""
+        "fixed" without cv2); None = ``$FCP_WARP_FAMILY``, else "fixed" (``align.resolve_warp_family``).
+        ``crop_source``: "batch" samples every crop from the resized batch image, as the reference does; "original" samples
+        it from the decoded file, through a power-of-two INTER_AREA level of it when the crop minifies the file by 2 or more
+        (``align.crop_align_sources``).  "original" cannot be combined with ``enh_threshold``: the enhancer works on the
+        resized batch, which this mode does not sample."""
+        if crop_source not in ("batch", "original"):
+            raise ValueError(f"unknown crop_source {crop_source!r}: choose 'batch' or 'original'")
+        if crop_source == "original" and enh_threshold is not None:
+            raise ValueError("crop_source='original' cannot be combined with enh_threshold: the enhancer works on the "
+                             "resized batch, which this mode does not sample")
+        self.crop_source = crop_source
         self.output_size = output_size
         self.output_format = output_format
         self.resize_size = resize_size
@@ -151,6 +162,14 @@ class Cropper:
         crops, ok, _ = align.crop_align(images_dev, idx, landmarks_dev, self.landmarks_target, self.output_size,
                                         align.border_code(self.padding), self.allow_skew, pads, family=self.warp_family)
         return crops, ok
+
+    def _source_landmarks(self, images, paddings, indices, lm_batch):
+        """Detector landmarks in the batch (before un-padding) -> the same points in each face's decoded image."""
+        geo = [batch_geometry(im.shape[0], im.shape[1], self.resize_size) for im in images]
+        idx = np.asarray(indices, np.int64)
+        w = np.array([images[i].shape[1] for i in idx]); h = np.array([images[i].shape[0] for i in idx])
+        ww = np.array([geo[i][0] for i in idx]); hh = np.array([geo[i][1] for i in idx])
+        return align.source_landmarks(lm_batch, w, h, ww, hh, paddings[idx, 2], paddings[idx, 0])
 
     def crop_align(self, images, padding, indices, landmarks_source) -> np.ndarray:
         """Reference signature (cropper.py:441-552): numpy in, numpy out.  ``images`` is an
@@ -283,6 +302,8 @@ class Cropper:
         if len(images) == 0:
             return
         paddings, landmarks, indices, images_dev = None, None, None, None
+        original = self.crop_source == "original"
+        sources = None                       # crop_source="original": (device blob, (N,3) table) of the decoded images
         with torch.cuda.device(self.device):
             if self.landmarks is None and self.det_model is None:
                 indices = list(range(len(file_names)))              # one "face" per image, no alignment
@@ -296,10 +317,15 @@ class Cropper:
                 landmarks = table[[row for _, row in pairs]]
             else:
                 with trace.range("fcp:build_batch"):
-                    images_dev, _, paddings = build_batch(images, self.resize_size, "constant", self.device, pinned)
+                    images_dev, _, paddings, *kept = build_batch(images, self.resize_size, "constant", self.device, pinned,
+                                                                 keep_sources=original)
                 with trace.range("fcp:detect"):
                     lm_np, indices = self.det_model.predict(images_dev)
-                landmarks = lm_np - paddings[indices][:, None, [2, 0]].astype(np.float32) if len(indices) else lm_np
+                if original:
+                    sources = kept[0]
+                    landmarks = self._source_landmarks(images, paddings, indices, lm_np) if len(indices) else lm_np
+                else:
+                    landmarks = lm_np - paddings[indices][:, None, [2, 0]].astype(np.float32) if len(indices) else lm_np
 
             if landmarks is not None and len(landmarks) == 0:
                 return
@@ -322,7 +348,18 @@ class Cropper:
 
             groups = (None, None)
             if landmarks is not None:
-                if images_dev is not None:
+                if original:
+                    with trace.range("fcp:align"):
+                        if sources is None:          # given landmarks: the originals have not been uploaded yet
+                            sources = upload_sources(images, self.device, pinned)
+                        crops_dev, ok, _, _ = align.crop_align_sources(
+                            *sources, indices, np.ascontiguousarray(landmarks, dtype=np.float32), self.landmarks_target,
+                            self.output_size, align.border_code(self.padding), self.allow_skew, self.warp_family)
+                    keep = ok.cpu().numpy() != 0
+                    crops_dev = crops_dev[torch.from_numpy(keep).to(self.device)]
+                    indices = [i for i, k in zip(indices, keep) if k]
+                    faces_dev, faces = crops_dev, crops_dev.cpu().numpy()
+                elif images_dev is not None:
                     with trace.range("fcp:align"):
                         crops_dev, ok = self._crop_align_device(
                             images_dev, paddings, list(indices),

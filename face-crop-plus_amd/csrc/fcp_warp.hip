@@ -132,11 +132,50 @@ __device__ __forceinline__ unsigned long long load6(const uint8_t* __restrict__ 
   return sh ? (lo >> sh) | ((unsigned long long)d2 << (64u - sh)) : lo;
 }
 
-template <int PX>
+// Where the source pixels of one face are: first pixel at byte s0off of the source base, sh x sw pixels, rows sstep bytes
+// apart; the 12-byte interior loads stay below byte `total` of the base.
+struct SrcView {
+  long s0off, sstep, total;
+  int sh, sw;
+};
+
+// Source policy of the batch warp: face -> image img_idx[face] of an (n,h,w,3) batch, un-padded by paddings[img] (t,b,l,r)
+// when given (cropper.py:538-539).
+struct BatchSource {
+  const uint8_t* base;
+  int n, h, w;
+  const int* img_idx;
+  const int* paddings;
+  __device__ __forceinline__ void view(int face, SrcView& v) const {
+    const int img = img_idx[face];
+    int pt = 0, pb = 0, pl = 0, pr = 0;
+    if (paddings != nullptr) { pt = paddings[img * 4]; pb = paddings[img * 4 + 1]; pl = paddings[img * 4 + 2]; pr = paddings[img * 4 + 3]; }
+    v.sh = h - pt - pb; v.sw = w - pl - pr;
+    v.sstep = (long)w * 3;
+    v.s0off = ((long)img * h + pt) * v.sstep + (long)pl * 3;
+    v.total = (long)n * h * v.sstep;             // bytes of the batch
+  }
+};
+
+// Source policy of the ragged warp: face -> its own (h,w,3) image at a 64-bit offset of one byte blob of `bytes` bytes
+// (descriptors validated by the launcher).
+struct RaggedSource {
+  const uint8_t* base;
+  long bytes;
+  const fcp_warp_src* srcs;
+  __device__ __forceinline__ void view(int face, SrcView& v) const {
+    const fcp_warp_src s = srcs[face];
+    v.sh = s.h; v.sw = s.w;
+    v.sstep = (long)s.w * 3;
+    v.s0off = s.off;
+    v.total = bytes;
+  }
+};
+
+template <int PX, class Src>
 __global__ void __launch_bounds__(256) warp_affine_kernel(
-    const uint8_t* __restrict__ images, int n, int h, int w, const int* __restrict__ img_idx,
-    const double* __restrict__ mat, const int* __restrict__ ok, const int* __restrict__ paddings,
-    int out_h, int out_w, int border, uint8_t* __restrict__ out) {
+    const Src src, const double* __restrict__ mat, const int* __restrict__ ok, int out_h, int out_w, int border,
+    uint8_t* __restrict__ out) {
   const int face = blockIdx.y;
   const int groups_per_row = (out_w + PX - 1) / PX;
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -169,14 +208,12 @@ __global__ void __launch_bounds__(256) warp_affine_kernel(
   __syncthreads();
   if (!active) return;
   if (valid) {
-    const int img = img_idx[face];
-    int pt = 0, pb = 0, pl = 0, pr = 0;
-    if (paddings != nullptr) { pt = paddings[img * 4]; pb = paddings[img * 4 + 1]; pl = paddings[img * 4 + 2]; pr = paddings[img * 4 + 3]; }
-    const int sh = h - pt - pb, sw = w - pl - pr;  // un-padded slice (cropper.py:538-539)
-    const long sstep = (long)w * 3;
-    const long s0off = ((long)img * h + pt) * sstep + (long)pl * 3;
+    SrcView v;
+    src.view(face, v);
+    const uint8_t* __restrict__ images = src.base;
+    const int sh = v.sh, sw = v.sw;
+    const long sstep = v.sstep, s0off = v.s0off, total = v.total;
     const uint8_t* S0 = images + s0off;
-    const long total = (long)n * h * sstep;          // bytes of the batch: bound of the 12-byte loads
     double M[6];
 #pragma unroll
     for (int q = 0; q < 6; ++q) M[q] = sM[q];
@@ -261,11 +298,10 @@ __device__ __forceinline__ uint8_t lerp2_f32(float p00, float p01, float p10, fl
 // The float32 family of cv::warpAffine(INTER_LINEAR) (the SIMD linear warp of newer OpenCV builds): source coordinates and
 // bilinear weights in float32, one rounding at the end.  Same launch geometry, un-padding, border handling and stores as
 // warp_affine_kernel; only the coordinate / weight arithmetic differs.
-template <int PX>
+template <int PX, class Src>
 __global__ void __launch_bounds__(256) warp_affine_float_kernel(
-    const uint8_t* __restrict__ images, int n, int h, int w, const int* __restrict__ img_idx,
-    const double* __restrict__ mat, const int* __restrict__ ok, const int* __restrict__ paddings,
-    int out_h, int out_w, int border, uint8_t* __restrict__ out) {
+    const Src src, const double* __restrict__ mat, const int* __restrict__ ok, int out_h, int out_w, int border,
+    uint8_t* __restrict__ out) {
   const int face = blockIdx.y;
   const int groups_per_row = (out_w + PX - 1) / PX;
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -297,14 +333,12 @@ __global__ void __launch_bounds__(256) warp_affine_float_kernel(
   __syncthreads();
   if (!active) return;
   if (valid) {
-    const int img = img_idx[face];
-    int pt = 0, pb = 0, pl = 0, pr = 0;
-    if (paddings != nullptr) { pt = paddings[img * 4]; pb = paddings[img * 4 + 1]; pl = paddings[img * 4 + 2]; pr = paddings[img * 4 + 3]; }
-    const int sh = h - pt - pb, sw = w - pl - pr;  // un-padded slice (cropper.py:538-539)
-    const long sstep = (long)w * 3;
-    const long s0off = ((long)img * h + pt) * sstep + (long)pl * 3;
+    SrcView v;
+    src.view(face, v);
+    const uint8_t* __restrict__ images = src.base;
+    const int sh = v.sh, sw = v.sw;
+    const long sstep = v.sstep, s0off = v.s0off, total = v.total;
     const uint8_t* S0 = images + s0off;
-    const long total = (long)n * h * sstep;          // bytes of the batch: bound of the 12-byte loads
     const float m0 = sM[0], m1 = sM[1], m2 = sM[2], m3 = sM[3], m4 = sM[4], m5 = sM[5];
     const float fy = (float)y;
     const float bx = fy * m1 + m2, by = fy * m4 + m5;     // the (y*m1 + m2) term of sx = x*m0 + (y*m1 + m2)
@@ -386,6 +420,49 @@ extern "C" int fcp_estimate_transform(const float* src, const float* dst, int f,
   return fcp_estimate_transform_counted(src, dst, f, k, allow_skew, nullptr, mat, ok, nullptr, stream);
 }
 
+namespace {
+
+// Groups of PX = 4 pixels, 256 per workgroup, one grid row (blockIdx.y) per face.
+template <class Src>
+int launch_fixed(const Src& src, const double* mat, const int32_t* ok, int f, int out_h, int out_w, int border, uint8_t* out,
+                 fcp_stream_t stream) {
+  const int groups = ((out_w + 3) / 4) * out_h;
+  hipLaunchKernelGGL((warp_affine_kernel<4, Src>), dim3(fcp_cdiv(groups, 256), f), dim3(256), 0, (hipStream_t)stream, src,
+                     mat, ok, out_h, out_w, border, out);
+  FCP_LAUNCH_OK();
+  return 0;
+}
+
+template <class Src>
+int launch_float(const Src& src, const double* mat, const int32_t* ok, int f, int out_h, int out_w, int border, uint8_t* out,
+                 fcp_stream_t stream) {
+  const int groups = ((out_w + 3) / 4) * out_h;
+  hipLaunchKernelGGL((warp_affine_float_kernel<4, Src>), dim3(fcp_cdiv(groups, 256), f), dim3(256), 0, (hipStream_t)stream,
+                     src, mat, ok, out_h, out_w, border, out);
+  FCP_LAUNCH_OK();
+  return 0;
+}
+
+// Checks of the ragged entry points: every descriptor inside the blob, each image at most 32767 px a side (the fixed
+// family saturates source coordinates to short, as cv::warpAffine does).
+int check_ragged(const char* what, const uint8_t* blob, int64_t blob_bytes, const fcp_warp_src* srcs_host,
+                 const fcp_warp_src* srcs_dev, const double* mat, int f, int out_h, int out_w, int border, uint8_t* out) {
+  FCP_REQUIRE(blob && srcs_host && srcs_dev && mat && out, "%s: null pointer", what);
+  FCP_REQUIRE(blob_bytes > 0 && f > 0 && out_h > 0 && out_w > 0, "%s: bad sizes", what);
+  FCP_REQUIRE(border >= 0 && border <= 4, "%s: unsupported border mode %d", what, border);
+  FCP_REQUIRE(f <= 65535, "%s: at most 65535 faces per call", what);
+  for (int i = 0; i < f; ++i) {
+    const fcp_warp_src& s = srcs_host[i];
+    FCP_REQUIRE(s.h > 0 && s.w > 0 && s.h <= 32767 && s.w <= 32767, "%s: face %d: source %dx%d (1..32767 a side)", what, i,
+                s.w, s.h);
+    FCP_REQUIRE(s.off >= 0 && s.off + (int64_t)s.h * s.w * 3 <= blob_bytes, "%s: face %d: source lies outside the blob", what,
+                i);
+  }
+  return 0;
+}
+
+}  // namespace
+
 extern "C" int fcp_warp_affine_u8(const uint8_t* images, int n, int h, int w, const int32_t* img_idx,
                                   const double* mat, const int32_t* ok, const int32_t* paddings, int f,
                                   int out_h, int out_w, int border, uint8_t* out, fcp_stream_t stream) {
@@ -393,12 +470,7 @@ extern "C" int fcp_warp_affine_u8(const uint8_t* images, int n, int h, int w, co
   FCP_REQUIRE(n > 0 && h > 0 && w > 0 && f > 0 && out_h > 0 && out_w > 0, "warp_affine: bad sizes");
   FCP_REQUIRE(border >= 0 && border <= 4, "warp_affine: unsupported border mode %d", border);
   FCP_REQUIRE(f <= 65535, "warp_affine: at most 65535 faces per call");
-  const int groups = ((out_w + 3) / 4) * out_h;
-  hipLaunchKernelGGL((warp_affine_kernel<4>), dim3(fcp_cdiv(groups, 256), f), dim3(256), 0,
-                     (hipStream_t)stream, images, n, h, w, img_idx, mat, ok, paddings, out_h, out_w, border,
-                     out);
-  FCP_LAUNCH_OK();
-  return 0;
+  return launch_fixed(BatchSource{images, n, h, w, img_idx, paddings}, mat, ok, f, out_h, out_w, border, out, stream);
 }
 
 extern "C" int fcp_warp_affine_u8_float(const uint8_t* images, int n, int h, int w, const int32_t* img_idx,
@@ -408,10 +480,22 @@ extern "C" int fcp_warp_affine_u8_float(const uint8_t* images, int n, int h, int
   FCP_REQUIRE(n > 0 && h > 0 && w > 0 && f > 0 && out_h > 0 && out_w > 0, "warp_affine_float: bad sizes");
   FCP_REQUIRE(border >= 0 && border <= 4, "warp_affine_float: unsupported border mode %d", border);
   FCP_REQUIRE(f <= 65535, "warp_affine_float: at most 65535 faces per call");
-  const int groups = ((out_w + 3) / 4) * out_h;
-  hipLaunchKernelGGL((warp_affine_float_kernel<4>), dim3(fcp_cdiv(groups, 256), f), dim3(256), 0,
-                     (hipStream_t)stream, images, n, h, w, img_idx, mat, ok, paddings, out_h, out_w, border,
-                     out);
-  FCP_LAUNCH_OK();
-  return 0;
+  return launch_float(BatchSource{images, n, h, w, img_idx, paddings}, mat, ok, f, out_h, out_w, border, out, stream);
+}
+
+extern "C" int fcp_warp_affine_u8_ragged(const uint8_t* blob, int64_t blob_bytes, const fcp_warp_src* srcs_host,
+                                         const fcp_warp_src* srcs_dev, const double* mat, const int32_t* ok, int f,
+                                         int out_h, int out_w, int border, uint8_t* out, fcp_stream_t stream) {
+  const int rc = check_ragged("warp_affine_ragged", blob, blob_bytes, srcs_host, srcs_dev, mat, f, out_h, out_w, border, out);
+  if (rc != 0) return rc;
+  return launch_fixed(RaggedSource{blob, (long)blob_bytes, srcs_dev}, mat, ok, f, out_h, out_w, border, out, stream);
+}
+
+extern "C" int fcp_warp_affine_u8_float_ragged(const uint8_t* blob, int64_t blob_bytes, const fcp_warp_src* srcs_host,
+                                               const fcp_warp_src* srcs_dev, const double* mat, const int32_t* ok, int f,
+                                               int out_h, int out_w, int border, uint8_t* out, fcp_stream_t stream) {
+  const int rc = check_ragged("warp_affine_float_ragged", blob, blob_bytes, srcs_host, srcs_dev, mat, f, out_h, out_w, border,
+                              out);
+  if (rc != 0) return rc;
+  return launch_float(RaggedSource{blob, (long)blob_bytes, srcs_dev}, mat, ok, f, out_h, out_w, border, out, stream);
 }

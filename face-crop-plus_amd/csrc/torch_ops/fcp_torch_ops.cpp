@@ -2,7 +2,8 @@
 // namespace ... stateless ops on the current HIP stream, tensors in/out, no hidden global state").
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
-//     warp_affine_u8 / warp_affine_u8_float / bicubic_down4_round / parse_argmax_hist
+//     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / resize_area_u8_ragged / bicubic_down4_round /
+//     parse_argmax_hist
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -292,6 +293,49 @@ Tensor warp_affine_u8_float(const Tensor& images, const Tensor& img_idx, const T
                           out_h, border);
 }
 
+// Host table of fixed-size records (fcp_warp_src / fcp_area_level) passed as a CPU int64 (n, words) tensor: validated by the
+// C entry point on the host, copied to the device of `like` for the kernel (stream-ordered behind any earlier work).
+const Tensor& host_table(const Tensor& t, const char* name, int64_t words) {
+  TORCH_CHECK(!t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous() && t.dim() == 2 && t.size(1) == words, name,
+              " must be a contiguous CPU int64 (n, ", words, ") tensor of records");
+  return t;
+}
+
+// crop_source="original": one source image per face in a byte blob (fcp_warp_src records: srcs (f,2) int64 on the host).
+// family 0 = fixed-point, 1 = float32 (align.WARP_FAMILIES).
+Tensor warp_affine_u8_ragged(const Tensor& blob, const Tensor& srcs, const Tensor& mat, const c10::optional<Tensor>& okf,
+                             int64_t out_w, int64_t out_h, int64_t border, int64_t family) {
+  dev(blob, "blob", at::kByte); dev(mat, "mat", at::kDouble); host_table(srcs, "srcs", 2);
+  FCP_DEVICE_GUARD(blob);
+  TORCH_CHECK(family == 0 || family == 1, "family must be 0 (fixed) or 1 (float32)");
+  const int64_t f = srcs.size(0);
+  TORCH_CHECK(mat.numel() == f * 6, "mat must hold (", f, ", 6) float64");
+  TORCH_CHECK(!okf.has_value() || !okf->defined() || okf->numel() == f, "ok must hold ", f, " flags");
+  Tensor srcs_dev = srcs.to(blob.device(), /*non_blocking=*/true);
+  Tensor out = at::empty({f, out_h, out_w, 3}, blob.options());
+  const auto* host = reinterpret_cast<const fcp_warp_src*>(srcs.data_ptr<int64_t>());
+  const auto* devp = reinterpret_cast<const fcp_warp_src*>(srcs_dev.data_ptr<int64_t>());
+  const auto fn = family == 0 ? fcp_warp_affine_u8_ragged : fcp_warp_affine_u8_float_ragged;
+  ok(fn(blob.data_ptr<uint8_t>(), blob.numel(), host, devp, mat.data_ptr<double>(), optp<int>(okf, "ok", at::kInt), (int)f,
+        (int)out_h, (int)out_w, (int)border, out.data_ptr<uint8_t>(), cur_stream()),
+     "fcp::warp_affine_u8_ragged");
+  return out;
+}
+
+// INTER_AREA levels of a ragged batch (fcp_area_level records: levels (n,4) int64 on the host), written into dst in place.
+void resize_area_u8_ragged(const Tensor& src, const Tensor& levels, const Tensor& dst) {
+  dev(src, "src", at::kByte); dev(dst, "dst", at::kByte); host_table(levels, "levels", 4);
+  FCP_DEVICE_GUARD(src);
+  const int64_t n = levels.size(0);
+  if (n == 0) return;
+  Tensor levels_dev = levels.to(src.device(), /*non_blocking=*/true);
+  ok(fcp_resize_area_ragged_u8(src.data_ptr<uint8_t>(), src.numel(),
+                               reinterpret_cast<const fcp_area_level*>(levels.data_ptr<int64_t>()),
+                               reinterpret_cast<const fcp_area_level*>(levels_dev.data_ptr<int64_t>()), (int)n,
+                               dst.data_ptr<uint8_t>(), dst.numel(), cur_stream()),
+     "fcp::resize_area_u8_ragged");
+}
+
 Tensor bicubic_down4_round(const Tensor& x4) {
   dev(x4, "x4", at::kFloat);
   FCP_DEVICE_GUARD(x4);
@@ -343,6 +387,9 @@ TORCH_LIBRARY(fcp, m) {
   m.def("warp_affine_u8(Tensor images, Tensor img_idx, Tensor mat, Tensor? ok, Tensor? paddings, int out_w, int out_h, int border) -> Tensor");
   m.def("warp_affine_u8_float(Tensor images, Tensor img_idx, Tensor mat, Tensor? ok, Tensor? paddings, int out_w, int out_h, "
         "int border) -> Tensor");
+  m.def("warp_affine_u8_ragged(Tensor blob, Tensor srcs, Tensor mat, Tensor? ok, int out_w, int out_h, int border, int family) "
+        "-> Tensor");
+  m.def("resize_area_u8_ragged(Tensor src, Tensor levels, Tensor(a!) dst) -> ()");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -362,6 +409,8 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("similarity_from_5pt", &similarity_from_5pt);
   m.impl("warp_affine_u8", &warp_affine_u8);
   m.impl("warp_affine_u8_float", &warp_affine_u8_float);
+  m.impl("warp_affine_u8_ragged", &warp_affine_u8_ragged);
+  m.impl("resize_area_u8_ragged", &resize_area_u8_ragged);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

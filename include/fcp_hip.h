@@ -357,6 +357,29 @@ int fcp_warp_affine_u8_float(const uint8_t* images, int n, int h, int w,
                              const int32_t* paddings, int f, int out_h, int out_w, int border,
                              uint8_t* out, fcp_stream_t stream);
 
+/* The same two warps with one source image per face, anywhere in one byte
+ * blob: crop_source="original", which crops from the decoded files (or from
+ * power-of-two INTER_AREA levels of them, fcp_resize_area_ragged_u8) instead of
+ * the resized batch.  Face i samples the (h,w,3) uint8 image at byte `off` of
+ * `blob` (blob_bytes bytes); borders act at that image's edge; the matrix
+ * inversion and the per-pixel arithmetic are those of fcp_warp_affine_u8 /
+ * fcp_warp_affine_u8_float.  srcs_host is validated here (each image inside the
+ * blob, 1..32767 px a side); srcs_dev is the caller's device copy of the same
+ * table.  mat (f,6) f64, ok (f) int32 or NULL, out (f,out_h,out_w,3) u8. */
+typedef struct fcp_warp_src {
+  int64_t off;        /* byte offset of the image inside the blob */
+  int32_t h, w;       /* image height, width */
+} fcp_warp_src;
+
+int fcp_warp_affine_u8_ragged(const uint8_t* blob, int64_t blob_bytes,
+                              const fcp_warp_src* srcs_host, const fcp_warp_src* srcs_dev,
+                              const double* mat, const int32_t* ok, int f, int out_h, int out_w,
+                              int border, uint8_t* out, fcp_stream_t stream);
+int fcp_warp_affine_u8_float_ragged(const uint8_t* blob, int64_t blob_bytes,
+                                    const fcp_warp_src* srcs_host, const fcp_warp_src* srcs_dev,
+                                    const double* mat, const int32_t* ok, int f, int out_h,
+                                    int out_w, int border, uint8_t* out, fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */
@@ -429,6 +452,25 @@ int fcp_build_batch_u8(const uint8_t* src_blob, int64_t blob_bytes,
                        const fcp_batch_item* items_host, const fcp_batch_item* items_dev,
                        int n, int out_h, int out_w, int border, uint8_t* out,
                        fcp_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Ragged INTER_AREA levels (crop_source="original"): cv2.resize(src, (dw,dh),
+ * interpolation=INTER_AREA) of n (source, destination) pairs, one launch, the
+ * arithmetic of fcp_build_batch_u8's INTER_AREA.  Sources are (sh,sw,3) uint8
+ * images at src_off of src_blob; destinations (dh,dw,3) at dst_off of dst_blob,
+ * dst_off a multiple of 4; dh <= sh and dw <= sw.  levels_host is validated
+ * here; levels_dev is the caller's device copy of the same table.
+ * ------------------------------------------------------------------------ */
+typedef struct fcp_area_level {
+  int64_t src_off;    /* byte offset of the source inside src_blob */
+  int32_t sh, sw;     /* source height, width */
+  int64_t dst_off;    /* byte offset of the level inside dst_blob (multiple of 4) */
+  int32_t dh, dw;     /* level height, width */
+} fcp_area_level;
+
+int fcp_resize_area_ragged_u8(const uint8_t* src_blob, int64_t src_bytes,
+                              const fcp_area_level* levels_host, const fcp_area_level* levels_dev,
+                              int n, uint8_t* dst_blob, int64_t dst_bytes, fcp_stream_t stream);
 
 #ifdef __cplusplus
 }
