@@ -10,28 +10,32 @@ strategy -> 5-point similarity -> warpAffine crops (uint8, on device).
 Workload at N=1 (and per rank at N>1) is the configuration north_star quotes the
 metric on: detect + align + crop on batch 32 of synthetic 1024x1024 RGB images
 (configs[3]'s per-GPU share: 256 / 8), strategy "largest", det_threshold 0.6,
-output 256x256, the detector on two HIP streams.  BASELINE configs[1] (batch 64
-@640x640) is measured in the same run and reported in `extra` and, as scalars,
-in `config` / `roofline` (`configs1_*`); `--batch 64 --size 640` makes it the
-headline.  Multi-GPU: every rank owns an independent batch (weak scaling, no
-data-path collective); weights are broadcast once from rank 0 over RCCL.
-`roofline.mean_sclk_mhz` / `mean_power_w` are sampled while the timed steps run
-(a slow box — lower clock at the socket power cap — reads differently from a
-regression).  `--dump-outputs DIR` writes what the last timed step returned as
-DIR/<name>.npy (inputs and weights are seeded: two builds can be compared
-output for output).
+output 256x256, the detector on two HIP streams.  `--batch 64 --size 640` makes
+BASELINE configs[1] (batch 64 @640x640) the headline.  Multi-GPU: every rank owns
+an independent batch (weak scaling, no data-path collective); weights are
+broadcast once from rank 0 over RCCL.  `--dump-outputs DIR` writes what the last
+timed step returned as DIR/<name>.npy (inputs and weights are seeded: two builds
+can be compared output for output).
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (conv
-engine), `cpu_baseline` (the oracle timed on the host cores) and — at N=1 —
-`extra`: the other BASELINE configurations / modes measured in the same run
-(configs[2] with and without RRDB enhancement, configs[4]'s 4K frames, the exact-fp32 mode), each with
-its own ms_per_step, steps and roofline sub-record.
+A plain run does only what the headline needs: set-up, the initialisation pass,
+the warm-up and timed steps, the dump, and ONE JSON line (rank 0) with the
+contract fields and `config`.  `--full` adds everything else the benchmark
+measures or checks, in the same process after the timed steps:
+`roofline` (conv engine), `hbm_kernels`, `cpu_baseline` (the oracle timed on the
+host cores) with `parity_check` (the timed batch against the oracle; the run
+fails on a mismatch) and — at N=1 — `extra`: the other BASELINE configurations /
+modes (configs[1] beside the 1024^2 headline, also as `configs1_*` scalars in
+`config` / `roofline`; configs[2] with and without RRDB enhancement, configs[4]'s
+4K frames, the exact-fp32 mode), each with its own ms_per_step, steps and
+roofline sub-record.  Under `--full`, `roofline.mean_sclk_mhz` / `mean_power_w`
+are sampled while the timed steps run (a slow box — lower clock at the socket
+power cap — reads differently from a regression).
 
 The detector is run the way the product runs it (`RetinaFace.streams` = 2: the
 two halves of the batch on two HIP streams).  Per-launch conv durations for the
 roofline are taken with HIP events in separate single-stream passes right after
 the timed region: launches that share the device would inflate each other's
-durations (`--streams 1` times them inside the timed region instead).
+durations (`--full --streams 1` times them inside the timed region instead).
 """
 from __future__ import annotations
 
@@ -69,6 +73,10 @@ def parse():
     ap.add_argument("--size", type=int, default=None, help="image side (default 1024)")
     ap.add_argument("--out-size", type=int, default=256)
     ap.add_argument("--strategy", default="largest")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: roofline, HBM kernel "
+                         "records, CPU baseline + oracle parity check, the `extra` configurations (not to be confused with "
+                         "--workload full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-autotune", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the `extra` workloads (configs[2], fp32 mode)")
@@ -94,6 +102,8 @@ def parse():
         ap.error("--steps must be >= 1")
     if args.warmup < 0:
         ap.error("--warmup must be >= 0")
+    if args.launch_table and not args.full:
+        ap.error("--launch-table needs --full (the table comes from the roofline passes)")
     return args
 
 
@@ -714,7 +724,7 @@ def main():
         from face_crop_plus_amd import engine as _E
         _E.Autotune.use_tables = False              # heuristic tiles: neither tuning launches nor the shipped / user tables
                                                     # (what FCP_TUNE_TABLES=0 does; FCP_AUTOTUNE=0 alone keeps the tables)
-    full = args.workload == "full"
+    workload_full = args.workload == "full"
     if args.batch is None:
         args.batch = 32
     if args.size is None:
@@ -748,7 +758,7 @@ def main():
     # weights + per-rank independent batches"; 228.9 MB for the three) — what the product's loader
     # (weights.load_state_dict) does inside a process group.  The other ranks' generated copies are only the key / shape
     # templates the flat buffer is cut by; broadcast_state_dict zeroes them before the collective.
-    names = ["retinaface"] + (["rrdb", "bisenet"] if full else [])
+    names = ["retinaface"] + (["rrdb", "bisenet"] if workload_full else [])
     sds = {k: weights.generate_state_dict(k) for k in names}
     broadcast = None
     if dist is not None:
@@ -763,11 +773,12 @@ def main():
         broadcast = {"networks": names, "bytes": int(nbytes), "ms": round((time.perf_counter() - tb) * 1e3, 2),
                      "note": "one flat fp32 RCCL broadcast per network from rank 0, incl. the host-side flatten / H2D / D2H / unflatten"}
     sd = sds["retinaface"]
-    p = Pipeline(dev, sd, full=full, batch=args.batch, size=args.size, out_size=args.out_size, strategy=args.strategy,
-                 precision=args.precision, enhance=args.enhance if full else "none", streams=args.streams,
+    p = Pipeline(dev, sd, full=workload_full, batch=args.batch, size=args.size, out_size=args.out_size, strategy=args.strategy,
+                 precision=args.precision, enhance=args.enhance if workload_full else "none", streams=args.streams,
                  seed=1234 + rank, graph=args.graph, sd_enh=sds.get("rrdb"), sd_par=sds.get("bisenet"))
-    live = rank == 0 and args.streams <= 1 and not args.graph
-    tele = Telemetry(local_rank) if rank == 0 else None
+    side = rank == 0 and args.full                 # --full: the records beside the headline (rank 0 writes the line)
+    live = side and args.streams <= 1 and not args.graph
+    tele = Telemetry(local_rank) if side else None
     elapsed, faces = time_pipeline(p, args.steps, args.warmup, autotune=not args.no_autotune, dist=dist, live_events=live,
                                    telemetry=tele)
     last_timed = p.last                            # outputs of the LAST TIMED step (the roofline passes below overwrite p.last)
@@ -783,12 +794,12 @@ def main():
 
     roofline = cpu_baseline = extra = parity_check = None
     hbm_kernels = None
-    if rank == 0:
+    if side:
         # committed PMC measurement of the same workload (profiles/): north-star geometry or configs[1]
         key = None
-        if not full and (args.batch, args.size) == (32, 1024) and args.precision == "f16x3":
+        if not workload_full and (args.batch, args.size) == (32, 1024) and args.precision == "f16x3":
             key = "c3det_pmc"
-        elif not full and (args.batch, args.size) == (64, 640):
+        elif not workload_full and (args.batch, args.size) == (64, 640):
             key = "f16x3_pmc_conv" if args.precision == "f16x3" else "f32_pmc_conv"
         roofline = conv_roofline(p, args.steps if live else args.roofline_steps, live,
                                  timed_ms=elapsed / args.steps * 1e3, traffic_key=key, table=True)
@@ -798,10 +809,10 @@ def main():
                 hbm_kernels = hbm_kernel_records(p)
             except Exception as e:                       # a side record must never take the headline line down
                 hbm_kernels = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if side and world == 1 and not args.no_cpu_baseline:
         cpu_baseline, parity_check = run_cpu_baseline(sd, p.images[:32].cpu(), args, p.tgt.cpu().numpy(), last_timed)
     describe = p.describe()
-    if rank == 0 and world == 1 and not args.no_extra and not full:
+    if side and world == 1 and not args.no_extra and not workload_full:
         del p
         gc.collect()
         torch.cuda.empty_cache()
@@ -820,9 +831,9 @@ def main():
                        "global_batch": args.batch * world, "image_size": args.size, "parallelism": f"dp{world}",
                        "faces_per_step": total_faces / max(args.steps, 1),
                        "images_per_s": round(args.batch * world * args.steps / elapsed, 2)},
-            "roofline": roofline, "hbm_kernels": hbm_kernels, "cpu_baseline": cpu_baseline,
-            "parity_check": parity_check,
         }
+        if args.full:
+            line.update(roofline=roofline, hbm_kernels=hbm_kernels, cpu_baseline=cpu_baseline, parity_check=parity_check)
         if dumped is not None:
             line["dumped_outputs"] = dumped
         if broadcast is not None:

@@ -245,3 +245,17 @@ def test_steps_and_warmup_are_checked(monkeypatch):
         monkeypatch.setattr(sys, "argv", ["bench.py", *bad])
         with pytest.raises(SystemExit):
             bench.parse()
+
+
+def test_full_is_off_by_default_and_the_launch_table_needs_it(monkeypatch):
+    """A plain run measures the headline only; the per-launch table comes from the roofline passes, which only `--full` runs."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--launch-table", "t.csv"])
+    args = bench.parse()
+    assert args.full and args.launch_table == "t.csv" and args.workload == "detect"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--launch-table", "t.csv"])
+    with pytest.raises(SystemExit):
+        bench.parse()

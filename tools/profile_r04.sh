@@ -11,6 +11,6 @@ cp $(find gpurun_out/prof_f16x3/trace -name "*kernel_stats.csv" | head -1) $O/r0
 python tools/summarize_trace2.py gpurun_out/prof_f16x3/trace2 $O/r04_f16x3_bench_step_trace_2streams.csv 2>&1 | tee $O/summarize_trace2.log
 python tools/summarize_pmc.py gpurun_out/prof_f16x3 $O/r04_f16x3_pmc_conv.json 53 2>&1 | tee $O/summarize_pmc.log
 cp gpurun_out/prof_f16x3/bench_line_under_trace.json $O/bench_line_under_trace.json
-python bench.py --launch-table $O/r04_f16x3_launch_table.csv > $O/bench_line.json 2> $O/bench.err
+python bench.py --full --launch-table $O/r04_f16x3_launch_table.csv > $O/bench_line.json 2> $O/bench.err
 rm -rf gpurun_out/prof_f16x3          # bulky raw traces: not needed once reduced
 ls -la $O

@@ -12,7 +12,7 @@ python tools/summarize_trace2.py gpurun_out/prof_f16x3/trace2 $O/r05_f16x3_bench
 L=$(python -c "import json;print(json.load(open('gpurun_out/prof_f16x3/bench_line_under_trace.json'))['roofline']['launches_per_step'])")
 python tools/summarize_pmc.py gpurun_out/prof_f16x3 $O/r05_f16x3_pmc_conv.json $L 2>&1 | tee $O/summarize_pmc.log
 cp gpurun_out/prof_f16x3/bench_line_under_trace.json $O/bench_line_under_trace.json
-python bench.py --launch-table $O/r05_f16x3_launch_table.csv > $O/bench_line.json 2> $O/bench.err
+python bench.py --full --launch-table $O/r05_f16x3_launch_table.csv > $O/bench_line.json 2> $O/bench.err
 rm -rf gpurun_out/prof_f16x3          # bulky raw traces: not needed once reduced
 # the north-star geometry (batch 32 @1024^2) and configs[2] without RRDB: counter passes only
 bash $R/tools/profile_workload.sh c3det pmc --workload detect --batch 32 --size 1024 > $O/profile_c3det.log 2>&1

@@ -43,8 +43,8 @@ rm -rf gpurun_out/prof_rrdb
 pmc f32_pmc_conv f32 64 640 "bench.py --batch 64 --size 640 --precision f32" --batch 64 --size 640 --precision f32
 rm -rf gpurun_out/prof_f32
 # ---- per-launch table (in-situ events + floors) of the headline and of configs[1]; the full bench line of this build
-python bench.py --launch-table $O/${TAG}_c3det_launch_table.csv > $O/bench_line.json 2> $O/bench.err
-python bench.py --batch 64 --size 640 --no-extra --no-cpu-baseline --launch-table $O/${TAG}_f16x3_launch_table.csv > $O/bench_line_c2.json 2> $O/bench_c2.err
+python bench.py --full --launch-table $O/${TAG}_c3det_launch_table.csv > $O/bench_line.json 2> $O/bench.err
+python bench.py --full --batch 64 --size 640 --no-extra --no-cpu-baseline --launch-table $O/${TAG}_f16x3_launch_table.csv > $O/bench_line_c2.json 2> $O/bench_c2.err
 # ---- per-launch ledger: every launch of the step alone in a steady loop, clock / power sampled -> W, MHz, joules, floors
 python tools/launch_ledger.py $O/${TAG}_c3det_launch_ledger.csv 32 1024 0.4 > $O/${TAG}_c3det_launch_ledger.txt 2>&1
 python tools/launch_ledger.py $O/${TAG}_f16x3_launch_ledger.csv 64 640 0.4 > $O/${TAG}_f16x3_launch_ledger.txt 2>&1

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
-BASE="python $R/bench.py --no-cpu-baseline --no-extra $*"
+BASE="python $R/bench.py --full --no-cpu-baseline --no-extra $*"
 if [ "$WHAT" = trace ] || [ "$WHAT" = all ]; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o b -- $BASE --steps 3 --warmup 2 --streams 1 > $O/bench_trace.log 2>&1
   grep '^{"metric"' $O/bench_trace.log | tail -1 > $O/bench_line_under_trace.json
