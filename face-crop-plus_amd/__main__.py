@@ -41,6 +41,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-cs", "--crop-source", type=str, default=argparse.SUPPRESS, choices=("batch", "original"),
                    help="sample crops from the resized batch (default 'batch', the reference's behaviour) or from the "
                         "full-resolution file ('original')")
+    p.add_argument("-ip", "--interpolation", type=str, default=argparse.SUPPRESS, choices=("linear", "cubic", "lanczos4"),
+                   help="filter of the crop warp: cv2 INTER_LINEAR (default 'linear', the reference's), INTER_CUBIC "
+                        "('cubic') or INTER_LANCZOS4 ('lanczos4')")
     return p
 
 

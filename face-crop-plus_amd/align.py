@@ -61,14 +61,42 @@ def _check_family(family):
         raise ValueError(f"unknown warpAffine family {family!r}: choose one of {WARP_FAMILIES}")
 
 
+# The warpAffine filters: "linear" (INTER_LINEAR, in either family) and OpenCV's fixed-point INTER_CUBIC / INTER_LANCZOS4
+# warps, which have one family only; the values are the cv2.INTER_* codes of the C ABI.
+INTERPOLATIONS = ("linear", "cubic", "lanczos4")
+_INTERP_CODE = {"cubic": 2, "lanczos4": 4}
+
+
+def check_interpolation(interpolation, family="fixed"):
+    """Raise ValueError for an unknown ``interpolation`` or for cubic / Lanczos-4 asked of the float32 family."""
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError(f"unknown interpolation {interpolation!r}: choose one of {INTERPOLATIONS}")
+    if interpolation != "linear" and family == "float32":
+        raise ValueError(f"interpolation={interpolation!r} has no float32 family: OpenCV warps cubic and Lanczos-4 with "
+                         f"fixed-point tables only (use warp_family 'fixed' or 'auto')")
+
+
 def warp_affine(images_u8: torch.Tensor, img_idx: torch.Tensor, mat: torch.Tensor, ok: torch.Tensor | None,
-                paddings: torch.Tensor | None, output_size, border: int = 0, family: str = "fixed") -> torch.Tensor:
-    """images (n,h,w,3) u8 device; output_size = (width, height) like cv2's dsize; ``family``: one of ``WARP_FAMILIES``."""
+                paddings: torch.Tensor | None, output_size, border: int = 0, family: str = "fixed",
+                interpolation: str = "linear") -> torch.Tensor:
+    """images (n,h,w,3) u8 device; output_size = (width, height) like cv2's dsize; ``family``: one of ``WARP_FAMILIES``;
+    ``interpolation``: one of ``INTERPOLATIONS`` ("cubic" / "lanczos4" only with the "fixed" family)."""
     _check_family(family)
+    check_interpolation(interpolation, family)
     assert images_u8.dtype == torch.uint8 and images_u8.is_contiguous() and images_u8.shape[3] == 3
     n, h, w, _ = images_u8.shape
     f = img_idx.shape[0]
     ow, oh = int(output_size[0]), int(output_size[1])
+    if interpolation != "linear":
+        code = _INTERP_CODE[interpolation]
+        if T.ENABLED:
+            return T.load().warp_affine_u8_interp(images_u8, img_idx, mat.contiguous().view(f, 2, 3), ok, paddings, ow, oh,
+                                                  int(border), code)
+        out = torch.empty((f, oh, ow, 3), dtype=torch.uint8, device=images_u8.device)
+        N.check(N.lib().fcp_warp_affine_u8_interp(N.ptr(images_u8), n, h, w, N.ptr(img_idx), N.ptr(mat), N.ptr(ok),
+                                                  N.ptr(paddings), f, oh, ow, int(border), code, N.ptr(out), N.stream_ptr()),
+                "fcp_warp_affine_u8_interp")
+        return out
     entry = _WARP_ENTRY[family]
     if T.ENABLED:
         return getattr(T.load(), entry)(images_u8, img_idx, mat.contiguous().view(f, 2, 3), ok, paddings, ow, oh, int(border))
@@ -139,11 +167,12 @@ def _auto_family(border, device) -> str:
 
 
 def crop_align(images_u8, img_idx, landmarks, target, output_size, border=0, allow_skew=False, paddings=None,
-               face_count=None, valid_total=None, family="fixed"):
+               face_count=None, valid_total=None, family="fixed", interpolation="linear"):
     """Device crop_align: -> (crops (F,oh,ow,3) u8, ok (F,) i32, mat (F,6) f64).  Faces
     with ok == 0 (degenerate transform) are dropped by the caller like cropper.py:529-531.
-    ``face_count`` / ``valid_total``: see ``estimate_transform``; ``family``: see ``warp_affine``."""
+    ``face_count`` / ``valid_total``: see ``estimate_transform``; ``family``, ``interpolation``: see ``warp_affine``."""
     _check_family(family)
+    check_interpolation(interpolation, family)
     dev = images_u8.device
     landmarks = landmarks.to(device=dev, dtype=torch.float32)
     if not isinstance(target, torch.Tensor):
@@ -153,7 +182,7 @@ def crop_align(images_u8, img_idx, landmarks, target, output_size, border=0, all
     if paddings is not None:
         paddings = paddings.to(device=dev, dtype=torch.int32).contiguous()
     mat, ok = estimate_transform(landmarks, target, allow_skew, face_count, valid_total)
-    crops = warp_affine(images_u8, img_idx, mat, ok, paddings, output_size, border, family)
+    crops = warp_affine(images_u8, img_idx, mat, ok, paddings, output_size, border, family, interpolation)
     return crops, ok, mat
 
 
@@ -213,10 +242,12 @@ def compose_level(mat, w: int, h: int, level: int) -> np.ndarray:
 
 
 def warp_affine_ragged(blob: torch.Tensor, srcs, mat: torch.Tensor, ok: torch.Tensor | None, output_size, border: int = 0,
-                       family: str = "fixed") -> torch.Tensor:
+                       family: str = "fixed", interpolation: str = "linear") -> torch.Tensor:
     """One crop per face from its own (h,w,3) image inside the device uint8 ``blob``: ``srcs`` (F,3) int64 host array of
-    (byte offset, h, w) per face; ``mat`` (F,6) f64 device forward transforms; -> (F,oh,ow,3) u8."""
+    (byte offset, h, w) per face; ``mat`` (F,6) f64 device forward transforms; -> (F,oh,ow,3) u8.  ``family``,
+    ``interpolation``: see ``warp_affine``."""
     _check_family(family)
+    check_interpolation(interpolation, family)
     assert blob.dtype == torch.uint8 and blob.is_contiguous() and blob.dim() == 1
     srcs = np.asarray(srcs, np.int64).reshape(-1, 3)
     f = srcs.shape[0]
@@ -224,6 +255,17 @@ def warp_affine_ragged(blob: torch.Tensor, srcs, mat: torch.Tensor, ok: torch.Te
     rec["off"], rec["h"], rec["w"] = srcs[:, 0], srcs[:, 1], srcs[:, 2]
     ow, oh = int(output_size[0]), int(output_size[1])
     mat = mat.contiguous()
+    if interpolation != "linear":
+        code = _INTERP_CODE[interpolation]
+        if T.ENABLED:
+            return T.load().warp_affine_u8_interp_ragged(blob, torch.from_numpy(rec.view(np.int64).reshape(f, 2)), mat, ok, ow,
+                                                         oh, int(border), code)
+        out = torch.empty((f, oh, ow, 3), dtype=torch.uint8, device=blob.device)
+        rec_dev = torch.from_numpy(rec.view(np.uint8)).to(blob.device)
+        N.check(N.lib().fcp_warp_affine_u8_interp_ragged(N.ptr(blob), blob.numel(), rec.ctypes.data, N.ptr(rec_dev), N.ptr(mat),
+                                                         N.ptr(ok), f, oh, ow, int(border), code, N.ptr(out), N.stream_ptr()),
+                "fcp_warp_affine_u8_interp_ragged")
+        return out
     if T.ENABLED:
         return T.load().warp_affine_u8_ragged(blob, torch.from_numpy(rec.view(np.int64).reshape(f, 2)), mat, ok, ow, oh,
                                               int(border), _WARP_FAMILY_CODE[family])
@@ -283,14 +325,16 @@ def plan_sources(table, idx, mats, ok):
 
 
 def crop_align_sources(blob: torch.Tensor, table, img_idx, landmarks, target, output_size, border=0, allow_skew=False,
-                       family="fixed"):
+                       family="fixed", interpolation="linear"):
     """Device crop_align from the decoded originals (crop_source="original").  ``blob``, ``table``: the sources as
     ``batch.upload_sources`` / ``build_batch(keep_sources=True)`` return them (the blob has room for the levels after the
     last source); ``img_idx`` (F,) image of each face; ``landmarks`` (F,k,2) in source pixel coordinates.
     -> (crops (F,oh,ow,3) u8, ok (F,) i32 device, mat_L (F,6) f64 device: the transform applied to each face's level,
     level (F,) int64 host).  The matrices come back to the host once (with ok) to pick the levels; the level images
-    are built in one launch, the crops in another."""
+    are built in one launch, the crops in another.  ``family``, ``interpolation``: see ``warp_affine``; the levels are the
+    same for every interpolation (they exist to shrink), the chosen filter then samples the level."""
     _check_family(family)
+    check_interpolation(interpolation, family)
     dev = blob.device
     table = np.asarray(table, np.int64).reshape(-1, 3)
     if len(table) and int(table[:, 1:].max()) > MAX_SOURCE_SIDE:
@@ -312,5 +356,5 @@ def crop_align_sources(blob: torch.Tensor, table, img_idx, landmarks, target, ou
                          f"upload the sources with batch.upload_sources or build_batch(keep_sources=True)")
     resize_area_ragged(blob, jobs, blob)
     mat_l_dev = torch.from_numpy(mat_l).to(dev)
-    crops = warp_affine_ragged(blob, srcs, mat_l_dev, ok, output_size, border, family)
+    crops = warp_affine_ragged(blob, srcs, mat_l_dev, ok, output_size, border, family, interpolation)
     return crops, ok, mat_l_dev, levels

@@ -52,6 +52,7 @@ class Cropper:
         precision: str | None = None,
         warp_family: str | None = None,
         crop_source: str = "batch",
+        interpolation: str = "linear",
     ):
         """Arguments as in the reference (cropper.py:139-156).  ``device`` must be a GPU
         (``"cuda:N"``); ``weights`` optionally maps "retinaface"/"rrdb"/"bisenet" to a
@@ -63,13 +64,20 @@ class Cropper:
         ``crop_source``: "batch" samples every crop from the resized batch image, as the reference does; "original" samples
         it from the decoded file, through a power-of-two INTER_AREA level of it when the crop minifies the file by 2 or more
         (``align.crop_align_sources``).  "original" cannot be combined with ``enh_threshold``: the enhancer works on the
-        resized batch, which this mode does not sample."""
+        resized batch, which this mode does not sample.
+        ``interpolation``: the filter of the crop warp — "linear" (cv2.INTER_LINEAR, the reference's), "cubic"
+        (INTER_CUBIC) or "lanczos4" (INTER_LANCZOS4), OpenCV's fixed-point warps, on every crop path.  Cubic and Lanczos-4
+        have no float32 family: combining them with an explicit ``warp_family="float32"`` (or ``$FCP_WARP_FAMILY``)
+        raises ValueError."""
+        explicit_family = warp_family if warp_family is not None else (os.environ.get("FCP_WARP_FAMILY") or None)
+        align.check_interpolation(interpolation, explicit_family)
         if crop_source not in ("batch", "original"):
             raise ValueError(f"unknown crop_source {crop_source!r}: choose 'batch' or 'original'")
         if crop_source == "original" and enh_threshold is not None:
             raise ValueError("crop_source='original' cannot be combined with enh_threshold: the enhancer works on the "
                              "resized batch, which this mode does not sample")
         self.crop_source = crop_source
+        self.interpolation = interpolation
         self.output_size = output_size
         self.output_format = output_format
         self.resize_size = resize_size
@@ -122,7 +130,13 @@ class Cropper:
 
         self._init_models()
         self._init_landmarks_target()
-        self.warp_family = align.resolve_warp_family(warp_family, self.padding, self.device)
+        if interpolation == "linear":
+            self.warp_family = align.resolve_warp_family(warp_family, self.padding, self.device)
+        else:
+            # cubic and Lanczos-4 exist in the fixed-point family only (whose coordinates they share): "auto" has nothing
+            # to pick, an unknown name still raises
+            self.warp_family = ("fixed" if explicit_family in (None, "auto")
+                                else align.resolve_warp_family(explicit_family, self.padding, self.device))
 
     # ------------------------------------------------------------------ init
     def _init_models(self):
@@ -160,7 +174,8 @@ class Cropper:
         pads = None if paddings is None else torch.as_tensor(np.asarray(paddings), dtype=torch.int32)
         idx = indices if isinstance(indices, torch.Tensor) else torch.as_tensor(np.asarray(indices), dtype=torch.int32)
         crops, ok, _ = align.crop_align(images_dev, idx, landmarks_dev, self.landmarks_target, self.output_size,
-                                        align.border_code(self.padding), self.allow_skew, pads, family=self.warp_family)
+                                        align.border_code(self.padding), self.allow_skew, pads, family=self.warp_family,
+                                        interpolation=self.interpolation)
         return crops, ok
 
     def _source_landmarks(self, images, paddings, indices, lm_batch):
@@ -354,7 +369,8 @@ class Cropper:
                             sources = upload_sources(images, self.device, pinned)
                         crops_dev, ok, _, _ = align.crop_align_sources(
                             *sources, indices, np.ascontiguousarray(landmarks, dtype=np.float32), self.landmarks_target,
-                            self.output_size, align.border_code(self.padding), self.allow_skew, self.warp_family)
+                            self.output_size, align.border_code(self.padding), self.allow_skew, self.warp_family,
+                            self.interpolation)
                     keep = ok.cpu().numpy() != 0
                     crops_dev = crops_dev[torch.from_numpy(keep).to(self.device)]
                     indices = [i for i, k in zip(indices, keep) if k]

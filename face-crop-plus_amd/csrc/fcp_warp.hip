@@ -15,8 +15,13 @@
 // warp (float family, opt-in): the float32 SIMD linear warp of newer OpenCV
 // builds — same inverse map rounded to float, sx = x*m0 + (y*m1 + m2) and the
 // bilinear blend in separately rounded float32 ops, rintf to uint8.
+//
+// warp (INTER_CUBIC / INTER_LANCZOS4, opt-in): the same coordinates as the fixed-point linear warp, a K x K neighbourhood
+// (K = 4 / 8) starting K/2 - 1 pixels before the tap, int16 weights from fcp_interp.h, out = (sum + 16384) >> 15
+// saturated to 0..255 (remapBicubic / remapLanczos4).
 #include "fcp_common.h"
 #include "fcp_hip.h"
+#include "fcp_interp.h"
 
 namespace {
 
@@ -402,6 +407,143 @@ __global__ void __launch_bounds__(256) warp_affine_float_kernel(
   }
 }
 
+// The 3K bytes of K consecutive RGB pixels at byte offset `off` of `base`, realigned into 3K/4 dwords: ND = 3K/4 + 1 aligned
+// dwords from (off & ~3), then a byte funnel shift.  The caller guarantees that (off & ~3) + 4 * ND stays inside the
+// allocation.
+template <int K>
+__device__ __forceinline__ void load_taps(const uint8_t* __restrict__ base, long off, unsigned (&e)[3 * K / 4]) {
+  constexpr int ND = 3 * K / 4 + 1;
+  const unsigned* q = reinterpret_cast<const unsigned*>(base + (off & ~3L));
+  const unsigned sh = (unsigned)(off & 3);
+  unsigned d[ND];
+#pragma unroll
+  for (int i = 0; i < ND; ++i) d[i] = q[i];
+#pragma unroll
+  for (int i = 0; i < ND - 1; ++i) e[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], sh);
+}
+
+// cv::warpAffine(INTER_CUBIC, K = 4 / INTER_LANCZOS4, K = 8) of uint8 RGB: the fixed-point linear warp's coordinates, launch
+// geometry, un-padding, source policies and packed store; the K x K int16 weights of each pixel are rebuilt from the float
+// 1-D table (copied to LDS once per workgroup) by fcp_interp::interp_weights_2d, and the taps are summed in int32.
+template <int K, int PX, class Src>
+__global__ void __launch_bounds__(256) warp_affine_interp_kernel(
+    const Src src, const fcp_interp::Tab1D<K> tab, const double* __restrict__ mat, const int* __restrict__ ok, int out_h,
+    int out_w, int border, uint8_t* __restrict__ out) {
+  const int face = blockIdx.y;
+  const int groups_per_row = (out_w + PX - 1) / PX;
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = g < groups_per_row * out_h;
+  const int y = active ? g / groups_per_row : 0;
+  const int x0 = active ? (g - y * groups_per_row) * PX : 0;
+  uint8_t* dst = out + (((long)face * out_h + y) * out_w + x0) * 3;
+  uint8_t px[PX * 3];
+#pragma unroll
+  for (int q = 0; q < PX * 3; ++q) px[q] = 0;
+
+  const bool valid = ok == nullptr || ok[face] != 0;       // uniform over the workgroup (one face per blockIdx.y)
+  __shared__ double sM[6];
+  __shared__ float sT[fcp_interp::TAB * K];
+  if (valid) {
+    for (int i = threadIdx.x; i < fcp_interp::TAB * K; i += blockDim.x) sT[i] = tab.c[i];
+    if (threadIdx.x == 0) {                                // inverse map: exactly warp_affine_kernel's
+      double M[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) M[q] = mat[(long)face * 6 + q];
+      double D = M[0] * M[4] - M[1] * M[3];
+      D = D != 0 ? 1. / D : 0;
+      const double A11 = M[4] * D, A22 = M[0] * D;
+      M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+      const double b1 = -M[0] * M[2] - M[1] * M[5];
+      const double b2 = -M[3] * M[2] - M[4] * M[5];
+      M[2] = b1; M[5] = b2;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) sM[q] = M[q];
+    }
+  }
+  __syncthreads();
+  if (!active) return;
+  if (valid) {
+    SrcView v;
+    src.view(face, v);
+    const uint8_t* __restrict__ images = src.base;
+    const int sh = v.sh, sw = v.sw;
+    const long sstep = v.sstep, s0off = v.s0off, total = v.total;
+    const uint8_t* S0 = images + s0off;
+    double M[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) M[q] = sM[q];
+    const int X0 = (int)((unsigned)cv_round((M[1] * y + M[2]) * 1024.0) + 16u);
+    const int Y0 = (int)((unsigned)cv_round((M[4] * y + M[5]) * 1024.0) + 16u);
+    const int width1 = sw - K + 1 > 0 ? sw - K + 1 : 0, height1 = sh - K + 1 > 0 ? sh - K + 1 : 0;
+    constexpr int ND = 3 * K / 4 + 1;
+#pragma unroll
+    for (int q = 0; q < PX; ++q) {
+      const int x = x0 + q;
+      if (x >= out_w) break;
+      const int ad = cv_round(M[0] * x * 1024.0), bd = cv_round(M[3] * x * 1024.0);
+      const int X = (int)((unsigned)X0 + (unsigned)ad) >> 5;
+      const int Y = (int)((unsigned)Y0 + (unsigned)bd) >> 5;
+      const int sx = sat_short(X >> 5) - (K / 2 - 1), sy = sat_short(Y >> 5) - (K / 2 - 1);
+      int w[K * K];
+      fcp_interp::interp_weights_2d<K>(sT + (Y & 31) * K, sT + (X & 31) * K, w);
+      int acc[3] = {0, 0, 0};
+      const long o0 = s0off + sy * sstep + sx * 3;
+      if ((unsigned)sx < (unsigned)width1 && (unsigned)sy < (unsigned)height1 &&
+          (((o0 + (K - 1) * sstep) & ~3L) + 4 * ND) <= total) {
+        // interior: each of the K rows is one run of 3K bytes, read as ND aligned dwords
+#pragma unroll
+        for (int r = 0; r < K; ++r) {
+          unsigned e[3 * K / 4];
+          load_taps<K>(images, o0 + r * sstep, e);
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const int b = k * 3 + c;
+              acc[c] += (int)((e[b >> 2] >> (8 * (b & 3))) & 255u) * w[r * K + k];
+            }
+          }
+        }
+      } else {
+        if (border == 0 && (sx >= sw || sx + K <= 0 || sy >= sh || sy + K <= 0)) continue;   // all-constant: 0
+        // replicate clamps inline, as the linear kernels do; border_interp then only ever sees the other borders, which also
+        // leaves the code generated for the linear kernels' calls of it unchanged
+        int xs[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) xs[k] = border == 1 ? min(max(sx + k, 0), sw - 1) : border_interp(sx + k, sw, border);
+#pragma unroll
+        for (int r = 0; r < K; ++r) {
+          const int yr = border == 1 ? min(max(sy + r, 0), sh - 1) : border_interp(sy + r, sh, border);
+          if (yr < 0) continue;                            // a constant-border tap outside the slice reads 0
+          const uint8_t* row = S0 + yr * sstep;
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            if (xs[k] < 0) continue;
+            const uint8_t* p = row + xs[k] * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += p[c] * w[r * K + k];
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int r = (acc[c] + (1 << 14)) >> 15;
+        px[q * 3 + c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
+      }
+    }
+  }
+  if (PX == 4 && x0 + 4 <= out_w && (out_w & 3) == 0) {
+    uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);  // 12 aligned bytes
+    d32[0] = px[0] | (px[1] << 8) | (px[2] << 16) | ((uint32_t)px[3] << 24);
+    d32[1] = px[4] | (px[5] << 8) | (px[6] << 16) | ((uint32_t)px[7] << 24);
+    d32[2] = px[8] | (px[9] << 8) | (px[10] << 16) | ((uint32_t)px[11] << 24);
+  } else {
+    for (int q = 0; q < PX && x0 + q < out_w; ++q) {
+      dst[q * 3] = px[q * 3]; dst[q * 3 + 1] = px[q * 3 + 1]; dst[q * 3 + 2] = px[q * 3 + 2];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int fcp_estimate_transform_counted(const float* src, const float* dst, int f, int k, int allow_skew,
@@ -443,6 +585,31 @@ int launch_float(const Src& src, const double* mat, const int32_t* ok, int f, in
   return 0;
 }
 
+// The float 1-D table of one method, built once per process on the host (thread-safe static initialisation).
+template <int K>
+const fcp_interp::Tab1D<K>& interp_tab() {
+  static const fcp_interp::Tab1D<K> t = [] {
+    fcp_interp::Tab1D<K> v;
+    fcp_interp::build_tab1d<K>(v);
+    return v;
+  }();
+  return t;
+}
+
+// interp: 2 = cv2.INTER_CUBIC (K = 4), 4 = cv2.INTER_LANCZOS4 (K = 8); checked by the caller.
+template <class Src>
+int launch_interp(const Src& src, int interp, const double* mat, const int32_t* ok, int f, int out_h, int out_w, int border,
+                  uint8_t* out, fcp_stream_t stream) {
+  const int groups = ((out_w + 3) / 4) * out_h;
+  if (interp == 2)
+    hipLaunchKernelGGL((warp_affine_interp_kernel<4, 4, Src>), dim3(fcp_cdiv(groups, 256), f), dim3(256), 0,
+                       (hipStream_t)stream, src, interp_tab<4>(), mat, ok, out_h, out_w, border, out);
+  else
+    hipLaunchKernelGGL((warp_affine_interp_kernel<8, 4, Src>), dim3(fcp_cdiv(groups, 256), f), dim3(256), 0,
+                       (hipStream_t)stream, src, interp_tab<8>(), mat, ok, out_h, out_w, border, out);
+  FCP_LAUNCH_OK();
+  return 0;
+}
 // Checks of the ragged entry points: every descriptor inside the blob, each image at most 32767 px a side (the fixed
 // family saturates source coordinates to short, as cv::warpAffine does).
 int check_ragged(const char* what, const uint8_t* blob, int64_t blob_bytes, const fcp_warp_src* srcs_host,
@@ -498,4 +665,43 @@ extern "C" int fcp_warp_affine_u8_float_ragged(const uint8_t* blob, int64_t blob
                               out);
   if (rc != 0) return rc;
   return launch_float(RaggedSource{blob, (long)blob_bytes, srcs_dev}, mat, ok, f, out_h, out_w, border, out, stream);
+}
+
+extern "C" int fcp_warp_affine_u8_interp(const uint8_t* images, int n, int h, int w, const int32_t* img_idx,
+                                         const double* mat, const int32_t* ok, const int32_t* paddings, int f,
+                                         int out_h, int out_w, int border, int interp, uint8_t* out, fcp_stream_t stream) {
+  FCP_REQUIRE(images && img_idx && mat && out, "warp_affine_interp: null pointer");
+  FCP_REQUIRE(n > 0 && h > 0 && w > 0 && f > 0 && out_h > 0 && out_w > 0, "warp_affine_interp: bad sizes");
+  FCP_REQUIRE(border >= 0 && border <= 4, "warp_affine_interp: unsupported border mode %d", border);
+  FCP_REQUIRE(fcp_interp::taps_of(interp) != 0, "warp_affine_interp: unsupported interpolation %d (2 cubic, 4 lanczos4)",
+              interp);
+  FCP_REQUIRE(f <= 65535, "warp_affine_interp: at most 65535 faces per call");
+  return launch_interp(BatchSource{images, n, h, w, img_idx, paddings}, interp, mat, ok, f, out_h, out_w, border, out, stream);
+}
+
+extern "C" int fcp_warp_affine_u8_interp_ragged(const uint8_t* blob, int64_t blob_bytes, const fcp_warp_src* srcs_host,
+                                                const fcp_warp_src* srcs_dev, const double* mat, const int32_t* ok, int f,
+                                                int out_h, int out_w, int border, int interp, uint8_t* out,
+                                                fcp_stream_t stream) {
+  FCP_REQUIRE(fcp_interp::taps_of(interp) != 0,
+              "warp_affine_interp_ragged: unsupported interpolation %d (2 cubic, 4 lanczos4)", interp);
+  const int rc = check_ragged("warp_affine_interp_ragged", blob, blob_bytes, srcs_host, srcs_dev, mat, f, out_h, out_w, border,
+                              out);
+  if (rc != 0) return rc;
+  return launch_interp(RaggedSource{blob, (long)blob_bytes, srcs_dev}, interp, mat, ok, f, out_h, out_w, border, out, stream);
+}
+
+extern "C" int fcp_warp_interp_weights(int interp, int16_t* out) {
+  FCP_REQUIRE(out, "warp_interp_weights: null pointer");
+  const int K = fcp_interp::taps_of(interp);
+  FCP_REQUIRE(K != 0, "warp_interp_weights: unsupported interpolation %d (2 cubic, 4 lanczos4)", interp);
+  const float* tab = K == 4 ? interp_tab<4>().c : interp_tab<8>().c;
+  int w[64];
+  for (int fy = 0; fy < fcp_interp::TAB; ++fy)
+    for (int fx = 0; fx < fcp_interp::TAB; ++fx) {
+      if (K == 4) fcp_interp::interp_weights_2d<4>(tab + fy * 4, tab + fx * 4, w);
+      else fcp_interp::interp_weights_2d<8>(tab + fy * 8, tab + fx * 8, w);
+      for (int k = 0; k < K * K; ++k) out[(fy * fcp_interp::TAB + fx) * K * K + k] = (int16_t)w[k];
+    }
+  return 0;
 }

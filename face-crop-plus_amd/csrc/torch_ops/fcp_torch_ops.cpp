@@ -2,8 +2,8 @@
 // namespace ... stateless ops on the current HIP stream, tensors in/out, no hidden global state").
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
-//     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / resize_area_u8_ragged / bicubic_down4_round /
-//     parse_argmax_hist
+//     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -263,11 +263,11 @@ std::tuple<Tensor, Tensor> similarity_from_5pt(const Tensor& src, const Tensor& 
   return {mat, okf};
 }
 
-// Both warpAffine families share parameters and checks; only the C entry point differs.
-using warp_fn = int (*)(const uint8_t*, int, int, int, const int32_t*, const double*, const int32_t*, const int32_t*, int, int,
-                        int, int, uint8_t*, fcp_stream_t);
+// Both warpAffine families and the cubic / Lanczos-4 warps share parameters and checks; only the C entry point differs
+// (`fn` takes fcp_warp_affine_u8's parameters).
 
-Tensor warp_affine_with(warp_fn fn, const char* what, const Tensor& images, const Tensor& img_idx, const Tensor& mat,
+template <class Fn>
+Tensor warp_affine_with(Fn fn, const char* what, const Tensor& images, const Tensor& img_idx, const Tensor& mat,
                         const c10::optional<Tensor>& okf, const c10::optional<Tensor>& paddings, int64_t out_w, int64_t out_h,
                         int64_t border) {
   dev(images, "images", at::kByte); dev(img_idx, "img_idx", at::kInt); dev(mat, "mat", at::kDouble);
@@ -293,6 +293,19 @@ Tensor warp_affine_u8_float(const Tensor& images, const Tensor& img_idx, const T
                           out_h, border);
 }
 
+// interp: cv2.INTER_CUBIC (2) or cv2.INTER_LANCZOS4 (4); anything else is refused by the C entry point.
+Tensor warp_affine_u8_interp(const Tensor& images, const Tensor& img_idx, const Tensor& mat, const c10::optional<Tensor>& okf,
+                             const c10::optional<Tensor>& paddings, int64_t out_w, int64_t out_h, int64_t border,
+                             int64_t interp) {
+  const int ip = (int)interp;
+  return warp_affine_with(
+      [ip](const uint8_t* im, int n, int h, int w, const int32_t* idx, const double* m, const int32_t* okp, const int32_t* pad,
+           int f, int oh, int ow, int b, uint8_t* out, fcp_stream_t st) {
+        return fcp_warp_affine_u8_interp(im, n, h, w, idx, m, okp, pad, f, oh, ow, b, ip, out, st);
+      },
+      "fcp::warp_affine_u8_interp", images, img_idx, mat, okf, paddings, out_w, out_h, border);
+}
+
 // Host table of fixed-size records (fcp_warp_src / fcp_area_level) passed as a CPU int64 (n, words) tensor: validated by the
 // C entry point on the host, copied to the device of `like` for the kernel (stream-ordered behind any earlier work).
 const Tensor& host_table(const Tensor& t, const char* name, int64_t words) {
@@ -302,12 +315,13 @@ const Tensor& host_table(const Tensor& t, const char* name, int64_t words) {
 }
 
 // crop_source="original": one source image per face in a byte blob (fcp_warp_src records: srcs (f,2) int64 on the host).
-// family 0 = fixed-point, 1 = float32 (align.WARP_FAMILIES).
-Tensor warp_affine_u8_ragged(const Tensor& blob, const Tensor& srcs, const Tensor& mat, const c10::optional<Tensor>& okf,
-                             int64_t out_w, int64_t out_h, int64_t border, int64_t family) {
+// `check` runs after the tensor checks; `fn` takes fcp_warp_affine_u8_ragged's parameters.
+template <class Check, class Fn>
+Tensor warp_affine_ragged_with(Check check, Fn fn, const char* what, const Tensor& blob, const Tensor& srcs, const Tensor& mat,
+                               const c10::optional<Tensor>& okf, int64_t out_w, int64_t out_h, int64_t border) {
   dev(blob, "blob", at::kByte); dev(mat, "mat", at::kDouble); host_table(srcs, "srcs", 2);
   FCP_DEVICE_GUARD(blob);
-  TORCH_CHECK(family == 0 || family == 1, "family must be 0 (fixed) or 1 (float32)");
+  check();
   const int64_t f = srcs.size(0);
   TORCH_CHECK(mat.numel() == f * 6, "mat must hold (", f, ", 6) float64");
   TORCH_CHECK(!okf.has_value() || !okf->defined() || okf->numel() == f, "ok must hold ", f, " flags");
@@ -315,11 +329,32 @@ Tensor warp_affine_u8_ragged(const Tensor& blob, const Tensor& srcs, const Tenso
   Tensor out = at::empty({f, out_h, out_w, 3}, blob.options());
   const auto* host = reinterpret_cast<const fcp_warp_src*>(srcs.data_ptr<int64_t>());
   const auto* devp = reinterpret_cast<const fcp_warp_src*>(srcs_dev.data_ptr<int64_t>());
-  const auto fn = family == 0 ? fcp_warp_affine_u8_ragged : fcp_warp_affine_u8_float_ragged;
   ok(fn(blob.data_ptr<uint8_t>(), blob.numel(), host, devp, mat.data_ptr<double>(), optp<int>(okf, "ok", at::kInt), (int)f,
         (int)out_h, (int)out_w, (int)border, out.data_ptr<uint8_t>(), cur_stream()),
-     "fcp::warp_affine_u8_ragged");
+     what);
   return out;
+}
+
+// family 0 = fixed-point, 1 = float32 (align.WARP_FAMILIES).
+Tensor warp_affine_u8_ragged(const Tensor& blob, const Tensor& srcs, const Tensor& mat, const c10::optional<Tensor>& okf,
+                             int64_t out_w, int64_t out_h, int64_t border, int64_t family) {
+  return warp_affine_ragged_with(
+      [family] { TORCH_CHECK(family == 0 || family == 1, "family must be 0 (fixed) or 1 (float32)"); },
+      family == 0 ? fcp_warp_affine_u8_ragged : fcp_warp_affine_u8_float_ragged, "fcp::warp_affine_u8_ragged", blob, srcs,
+      mat, okf, out_w, out_h, border);
+}
+
+// interp: cv2.INTER_CUBIC (2) or cv2.INTER_LANCZOS4 (4), as warp_affine_u8_interp.
+Tensor warp_affine_u8_interp_ragged(const Tensor& blob, const Tensor& srcs, const Tensor& mat, const c10::optional<Tensor>& okf,
+                                    int64_t out_w, int64_t out_h, int64_t border, int64_t interp) {
+  const int ip = (int)interp;
+  return warp_affine_ragged_with(
+      [] {},
+      [ip](const uint8_t* b, int64_t bytes, const fcp_warp_src* sh, const fcp_warp_src* sd, const double* m, const int32_t* okp,
+           int f, int oh, int ow, int bd, uint8_t* out, fcp_stream_t st) {
+        return fcp_warp_affine_u8_interp_ragged(b, bytes, sh, sd, m, okp, f, oh, ow, bd, ip, out, st);
+      },
+      "fcp::warp_affine_u8_interp_ragged", blob, srcs, mat, okf, out_w, out_h, border);
 }
 
 // INTER_AREA levels of a ragged batch (fcp_area_level records: levels (n,4) int64 on the host), written into dst in place.
@@ -389,6 +424,10 @@ TORCH_LIBRARY(fcp, m) {
         "int border) -> Tensor");
   m.def("warp_affine_u8_ragged(Tensor blob, Tensor srcs, Tensor mat, Tensor? ok, int out_w, int out_h, int border, int family) "
         "-> Tensor");
+  m.def("warp_affine_u8_interp(Tensor images, Tensor img_idx, Tensor mat, Tensor? ok, Tensor? paddings, int out_w, int out_h, "
+        "int border, int interp) -> Tensor");
+  m.def("warp_affine_u8_interp_ragged(Tensor blob, Tensor srcs, Tensor mat, Tensor? ok, int out_w, int out_h, int border, "
+        "int interp) -> Tensor");
   m.def("resize_area_u8_ragged(Tensor src, Tensor levels, Tensor(a!) dst) -> ()");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
@@ -410,6 +449,8 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("warp_affine_u8", &warp_affine_u8);
   m.impl("warp_affine_u8_float", &warp_affine_u8_float);
   m.impl("warp_affine_u8_ragged", &warp_affine_u8_ragged);
+  m.impl("warp_affine_u8_interp", &warp_affine_u8_interp);
+  m.impl("warp_affine_u8_interp_ragged", &warp_affine_u8_interp_ragged);
   m.impl("resize_area_u8_ragged", &resize_area_u8_ragged);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);

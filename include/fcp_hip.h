@@ -380,6 +380,29 @@ int fcp_warp_affine_u8_float_ragged(const uint8_t* blob, int64_t blob_bytes,
                                     const double* mat, const int32_t* ok, int f, int out_h,
                                     int out_w, int border, uint8_t* out, fcp_stream_t stream);
 
+/* cv2.warpAffine(image, M, dsize, flags=interp, borderMode) with interp a
+ * cv2.INTER_* code: 2 = INTER_CUBIC (4 x 4 taps), 4 = INTER_LANCZOS4 (8 x 8);
+ * any other value fails with a message.  Parameters, argument checks,
+ * un-padding and borders as fcp_warp_affine_u8 / fcp_warp_affine_u8_ragged.
+ * OpenCV's fixed-point remap: the coordinates of the linear warp (AB_BITS=10,
+ * INTER_BITS=5, sx0 = X >> 5), taps from sx0 - 1 (cubic) or sx0 - 3 (Lanczos)
+ * on, int16 weights of initInterTab2D (sum 32768), int32 sums,
+ * out = (sum + 16384) >> 15 saturated to 0..255. */
+int fcp_warp_affine_u8_interp(const uint8_t* images, int n, int h, int w,
+                              const int32_t* img_idx, const double* mat, const int32_t* ok,
+                              const int32_t* paddings, int f, int out_h, int out_w, int border,
+                              int interp, uint8_t* out, fcp_stream_t stream);
+int fcp_warp_affine_u8_interp_ragged(const uint8_t* blob, int64_t blob_bytes,
+                                     const fcp_warp_src* srcs_host, const fcp_warp_src* srcs_dev,
+                                     const double* mat, const int32_t* ok, int f, int out_h,
+                                     int out_w, int border, int interp, uint8_t* out,
+                                     fcp_stream_t stream);
+
+/* The fixed-point weight table those warps use, on the host (no device
+ * needed): 1024 * K * K int16 in [fy * 32 + fx][k1][k2] order, K = 4 for
+ * interp 2, 8 for interp 4. */
+int fcp_warp_interp_weights(int interp, int16_t* out);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */

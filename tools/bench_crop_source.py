@@ -1,14 +1,14 @@
 """crop_source="batch" against "original" on synthetic 12 MP photos (4000 x 3000) at resize_size 1024, batch 8 and 32.
 
-    python tools/bench_crop_source.py [--images 64] [--out FILE]
+    python tools/bench_crop_source.py [--images 64] [--interpolation linear|cubic|lanczos4] [--out FILE]
 
 Prints one JSON line per measurement:
   * device time of the crop stage per batch (CUDA events, median of 20): batch mode = the warp on the resized batch;
     original mode = the INTER_AREA level build plus the ragged warp.  Three faces per image, at crop scales 0.67, 0.25 and
-    0.1 (levels 0, 2 and 3), 256^2 crops;
+    0.1 (levels 0, 2 and 3), 256^2 crops; and the warps alone for the first 32 of those faces (batch and ragged sources);
   * end-to-end Cropper.process_dir images/s on a directory of JPEGs (generated RetinaFace weights, strategy "largest"),
-    second of two runs.
-Nothing is gated on these numbers.
+    second of two runs (skipped with --images 0).
+``--interpolation`` picks the filter of every warp (Cropper(interpolation=...)).  Nothing is gated on these numbers.
 """
 from __future__ import annotations
 
@@ -65,7 +65,7 @@ def _time(fn, reps=20):
     return float(np.median(times))
 
 
-def device_times(n, dev):
+def device_times(n, dev, interp="linear"):
     imgs = _images(n)
     batch, unscales, pads, (blob, table) = build_batch(imgs, RS, "constant", dev, keep_sources=True)
     mats, idx = _faces(n)
@@ -82,20 +82,26 @@ def device_times(n, dev):
     pads_d = torch.from_numpy(pads.astype(np.int32)).to(dev)
     ok_d = torch.ones(len(idx), dtype=torch.int32, device=dev)
     mat_ld = torch.from_numpy(mat_l).to(dev)
-    t_batch = _time(lambda: align.warp_affine(batch, idx_d, mat_b, ok_d, pads_d, OUT, 0))
+    ip = {"interpolation": interp}
+    t_batch = _time(lambda: align.warp_affine(batch, idx_d, mat_b, ok_d, pads_d, OUT, 0, **ip))
     t_levels = _time(lambda: align.resize_area_ragged(blob, jobs, blob))
-    t_warp = _time(lambda: align.warp_affine_ragged(blob, srcs, mat_ld, ok_d, OUT, 0))
-    t_orig = _time(lambda: (align.resize_area_ragged(blob, jobs, blob), align.warp_affine_ragged(blob, srcs, mat_ld, ok_d, OUT, 0)))
+    t_warp = _time(lambda: align.warp_affine_ragged(blob, srcs, mat_ld, ok_d, OUT, 0, **ip))
+    t_orig = _time(lambda: (align.resize_area_ragged(blob, jobs, blob),
+                            align.warp_affine_ragged(blob, srcs, mat_ld, ok_d, OUT, 0, **ip)))
+    f32 = min(32, len(idx))
+    t_batch32 = _time(lambda: align.warp_affine(batch, idx_d[:f32], mat_b[:f32], ok_d[:f32], pads_d, OUT, 0, **ip))
+    t_warp32 = _time(lambda: align.warp_affine_ragged(blob, srcs[:f32], mat_ld[:f32], ok_d[:f32], OUT, 0, **ip))
     level_bytes = sum(j[4] * j[5] * 3 for j in jobs)
     read_bytes = sum(j[1] * j[2] * 3 for j in jobs)
-    return {"metric": "crop_stage_device_ms", "batch": n, "faces": len(idx), "levels": sorted(set(levels.tolist())),
-            "batch_mode_warp_ms": round(t_batch, 4), "original_levels_ms": round(t_levels, 4),
+    return {"metric": "crop_stage_device_ms", "interpolation": interp, "batch": n, "faces": len(idx),
+            "levels": sorted(set(levels.tolist())), "batch_mode_warp_ms": round(t_batch, 4),
+            f"batch_mode_warp_{f32}_faces_ms": round(t_batch32, 4), f"original_warp_{f32}_faces_ms": round(t_warp32, 4), "original_levels_ms": round(t_levels, 4),
             "original_warp_ms": round(t_warp, 4), "original_total_ms": round(t_orig, 4),
             "level_jobs": len(jobs), "level_source_gb_read": round(read_bytes / 1e9, 3),
             "level_gb_written": round(level_bytes / 1e9, 3)}
 
 
-def end_to_end(n_images, bs, dev, tmp):
+def end_to_end(n_images, bs, dev, tmp, interp="linear"):
     from PIL import Image
     from face_crop_plus_amd import Cropper
     src = os.path.join(tmp, "in")
@@ -103,10 +109,10 @@ def end_to_end(n_images, bs, dev, tmp):
         os.makedirs(src)
         for i, im in enumerate(_images(n_images, seed=1)):
             Image.fromarray(im).save(os.path.join(src, f"{i:04d}.jpg"), quality=90)
-    res = {"metric": "process_dir_images_per_s", "batch": bs, "images": n_images}
+    res = {"metric": "process_dir_images_per_s", "interpolation": interp, "batch": bs, "images": n_images}
     for mode in ("batch", "original"):
         c = Cropper(output_size=OUT, resize_size=RS, strategy="largest", det_threshold=0.6, batch_size=bs, device=dev,
-                    weights={"retinaface": "generated"}, crop_source=mode)
+                    weights={"retinaface": "generated"}, crop_source=mode, interpolation=interp)
         rates = []
         for run in range(2):
             out = os.path.join(tmp, f"out_{mode}_{bs}_{run}")
@@ -124,15 +130,17 @@ def end_to_end(n_images, bs, dev, tmp):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=64)
+    ap.add_argument("--interpolation", choices=align.INTERPOLATIONS, default="linear")
     ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    lines = [device_times(n, dev) for n in (8, 32)]
-    tmp = tempfile.mkdtemp(prefix="fcp_crop_source_")
-    try:
-        lines += [end_to_end(a.images, bs, dev, tmp) for bs in (8, 32)]
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+    lines = [device_times(n, dev, a.interpolation) for n in (8, 32)]
+    if a.images > 0:
+        tmp = tempfile.mkdtemp(prefix="fcp_crop_source_")
+        try:
+            lines += [end_to_end(a.images, bs, dev, tmp, a.interpolation) for bs in (8, 32)]
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
     for line in lines:
         print(json.dumps(line), flush=True)
     if a.out:

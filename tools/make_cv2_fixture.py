@@ -7,13 +7,15 @@ kernels to them.
 
     pip install opencv-python torchvision          # anywhere with a network
     python tools/make_cv2_fixture.py                # writes tests/golden/opencv_align.npz, opencv_batch.npz,
-                                                    #        tests/golden/torchvision_resnet50.npz
+                                                    #        opencv_interp.npz, tests/golden/torchvision_resnet50.npz
     python -m pytest tests/test_third_party_pins.py            # oracle vs the pins (CPU)
     python -m pytest tests/test_third_party_pins.py -m gpu     # kernels vs the pins (MI355X)
+    python -m pytest tests/test_warp_interp_pins.py            # cubic / Lanczos-4 restatement (and, -m gpu, kernels)
 
 Everything is called exactly the way the reference calls it:
   cropper.py:515-527   cv2.estimateAffinePartial2D / estimateAffine2D(src, dst, ransacReprojThreshold=np.inf)[0]
   cropper.py:542-547   cv2.warpAffine(image, M, dsize, borderMode=cv2.BORDER_*)          (flags default INTER_LINEAR)
+                       and the same call with flags=INTER_CUBIC / INTER_LANCZOS4 (Cropper(interpolation=...))
   utils.py:320-335     cv2.resize(image, (ww, hh), interpolation=INTER_AREA | INTER_CUBIC) + cv2.copyMakeBorder
   retinaface.py:93-99  torchvision.models.resnet50() + _utils.IntermediateLayerGetter(layer2, layer3, layer4)
 Only data is stored (inputs, outputs, library versions): no third-party source.
@@ -151,6 +153,39 @@ def make_batch(cv2):
     print("wrote opencv_batch.npz")
 
 
+def make_interp(cv2):
+    """cv2.warpAffine(flags=INTER_CUBIC | INTER_LANCZOS4) on 8UC3 for tests/test_warp_interp_pins.py: random and gradient
+    images of 48x64 and 7x9, matrices with rotations, scales 0.3x to 5x, fractional shifts and sources partly or fully
+    outside the crop, every border mode."""
+    rng = np.random.default_rng(500)
+    out = describe_cv2(cv2)
+    out["cv2_ipp"] = np.array(" | ".join(ln.strip() for ln in cv2.getBuildInformation().splitlines() if "IPP" in ln))
+    k = 0
+    for (h, w), (ow, oh) in (((48, 64), (24, 20)), ((7, 9), (20, 16))):
+        yy, xx = np.mgrid[0:h, 0:w]
+        grad = np.stack([(xx * 255) // max(w - 1, 1), (yy * 255) // max(h - 1, 1), ((xx + yy) * 9) % 256], -1).astype(np.uint8)
+        for img in (rng.integers(0, 256, (h, w, 3), dtype=np.uint8), grad):
+            mats = []
+            for j, s in enumerate((0.3, 0.8, 1.0, 1.7, 3.2, 5.0)):
+                th = rng.uniform(-np.pi, np.pi) if j % 2 else rng.uniform(-0.3, 0.3)
+                a, b = s * np.cos(th), s * np.sin(th)
+                c = np.array([(w - 1) / 2, (h - 1) / 2]) + rng.uniform(-0.5, 0.5, 2) * np.array([w, h])
+                tx, ty = np.array([(ow - 1) / 2, (oh - 1) / 2]) - np.array([a * c[0] - b * c[1], b * c[0] + a * c[1]])
+                mats.append([[a, -b, tx + rng.uniform(-1, 1)], [b, a, ty + rng.uniform(-1, 1)]])
+            mats.append([[1.1, 0.2, 3.0 * ow], [-0.2, 1.1, -2.0 * oh]])                # the source fully outside the crop
+            mats = np.array(mats, np.float64)
+            out[f"interp{k}_img"], out[f"interp{k}_mat"], out[f"interp{k}_dsize"] = img, mats, np.array([ow, oh])
+            for name, flag in (("cubic", cv2.INTER_CUBIC), ("lanczos4", cv2.INTER_LANCZOS4)):
+                for b in BORDERS:
+                    mode = getattr(cv2, f"BORDER_{b.upper()}")
+                    out[f"interp{k}_{name}_{b}"] = np.stack([cv2.warpAffine(img, m, (ow, oh), flags=flag, borderMode=mode)
+                                                             for m in mats])
+            k += 1
+    out["interp_cases"] = np.array(k)
+    np.savez_compressed(os.path.join(GOLDEN, "opencv_interp.npz"), **out)
+    print("wrote opencv_interp.npz")
+
+
 def make_resnet():
     """retinaface.py:93-99 with the build's generated `body.*` weights: the three feature maps torchvision's own
     ResNet-50 + IntermediateLayerGetter return for one seeded 96x128 input."""
@@ -186,6 +221,7 @@ def main():
         else:
             make_align(cv2)
             make_batch(cv2)
+            make_interp(cv2)
     if args.only != "cv2":
         try:
             import torchvision  # noqa: F401
