@@ -13,8 +13,10 @@ namespace {
 constexpr int DEC_THREADS = 1024;
 constexpr int NMS_THREADS = 1024;
 constexpr int SORT_LDS_KEYS = 8192;  // 64 KiB of 8-byte keys
-constexpr int NMS_ALIVE_WORDS = SORT_LDS_KEYS - 256;   // alive bitmap of the greedy pass: 64 candidates per word
-constexpr int NMS_MAX_CAP = NMS_ALIVE_WORDS * 64;      // 507 904 candidates per image (a 2800^2 frame has 322 k priors)
+constexpr int NMS_ALIVE_WORDS = SORT_LDS_KEYS - 256;   // alive bitmap of the greedy pass in LDS: 64 candidates per word
+constexpr int NMS_LDS_CAP = NMS_ALIVE_WORDS * 64;      // 507 904 candidates per image keep the bitmap in LDS (3512^2 frame);
+                                                       // more (4096^2: 688 128 priors) keep it in the workspace
+constexpr int NMS_MAX_CAP = 1 << 26;                   // 32-bit index arithmetic of the sort and the box workspace
 
 struct Levels {
   int h[3], w[3], start[4];
@@ -195,17 +197,87 @@ __device__ __forceinline__ bool suppressed(float kx1, float ky1, float kx2, floa
   return !(ovr <= thr);
 }
 
+// Tiled greedy NMS over the K sorted boxes.  LDS reuse: the alive bitmap (ceil(K/64) words; in the workspace instead when
+// kGlobalAlive) then the kept-box tile.  Inlined twice, so each copy addresses its bitmap in its own address space.
+template <bool kGlobalAlive>
+__device__ __forceinline__ void greedy_nms(unsigned long long* alive, unsigned long long* lkeys, const float* sbox,
+                                           const unsigned long long* gkeys, int* kpos, int K, float thr, int& s_kc,
+                                           int tid, int lane, int wave) {
+  float* tile = reinterpret_cast<float*>(lkeys + NMS_ALIVE_WORDS);     // 64 * 5 floats
+  int* tile_n = reinterpret_cast<int*>(tile + 64 * 5);
+  const int nwords = (K + 63) >> 6;
+  for (int wd = tid; wd < nwords; wd += NMS_THREADS) {
+    const int lo = wd << 6;
+    unsigned long long m = 0ull;
+    if (lo + 64 <= K) m = ~0ull;
+    else if (lo < K) m = (1ull << (K - lo)) - 1ull;
+    alive[wd] = m;
+  }
+  if (tid == 0) s_kc = 0;
+  if (kGlobalAlive) __threadfence_block();
+  __syncthreads();
+
+  const int ntiles = (K + 63) >> 6;
+  for (int t = 0; t < ntiles; ++t) {
+    if (wave == 0) {
+      const int c = (t << 6) + lane;
+      float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, area = 0.f;
+      if (c < K) { x1 = sbox[c * 5]; y1 = sbox[c * 5 + 1]; x2 = sbox[c * 5 + 2]; y2 = sbox[c * 5 + 3]; area = sbox[c * 5 + 4]; }
+      bool me = (alive[t] >> lane) & 1ull;
+      for (int b = 0; b < 64; ++b) {
+        const unsigned long long m = __ballot(me);
+        if (!((m >> b) & 1ull)) continue;  // wave-uniform
+        const float kx1 = __shfl(x1, b), ky1 = __shfl(y1, b), kx2 = __shfl(x2, b), ky2 = __shfl(y2, b);
+        const float ka = __shfl(area, b);
+        if (lane > b && me && suppressed(kx1, ky1, kx2, ky2, ka, x1, y1, x2, y2, area, thr)) me = false;
+      }
+      const unsigned long long m = __ballot(me);
+      const int rank = __popcll(m & ((1ull << lane) - 1ull));
+      const int kc = s_kc;
+      if (me) {
+        kpos[kc + rank] = (int)(unsigned)(gkeys[c] & 0xffffffffull);
+        tile[rank * 5 + 0] = x1; tile[rank * 5 + 1] = y1; tile[rank * 5 + 2] = x2; tile[rank * 5 + 3] = y2;
+        tile[rank * 5 + 4] = area;
+      }
+      if (lane == 0) { *tile_n = __popcll(m); s_kc = kc + __popcll(m); }
+    }
+    __syncthreads();
+    const int nk = *tile_n;
+    if (nk > 0) {
+      for (int wd = t + 1 + wave; wd < nwords && (wd << 6) < K; wd += NMS_THREADS / 64) {
+        const unsigned long long m = alive[wd];
+        if (m == 0ull) continue;  // wave-uniform
+        bool me = (m >> lane) & 1ull;
+        if (me) {
+          const int c = (wd << 6) + lane;
+          const float x1 = sbox[c * 5], y1 = sbox[c * 5 + 1], x2 = sbox[c * 5 + 2], y2 = sbox[c * 5 + 3];
+          const float area = sbox[c * 5 + 4];
+          for (int q = 0; q < nk; ++q) {
+            if (suppressed(tile[q * 5], tile[q * 5 + 1], tile[q * 5 + 2], tile[q * 5 + 3], tile[q * 5 + 4], x1,
+                           y1, x2, y2, area, thr)) { me = false; break; }
+          }
+        }
+        const unsigned long long nm = __ballot(me);
+        if (lane == 0) alive[wd] = nm;
+      }
+    }
+    if (kGlobalAlive) __threadfence_block();
+    __syncthreads();
+  }
+}
+
 __global__ void __launch_bounds__(NMS_THREADS) retina_nms_kernel(
     const float* __restrict__ cand_score, const float* __restrict__ cand_box,
     const int* __restrict__ cand_count, int cap, int cap_p2, float thr, int strategy,
-    unsigned long long* __restrict__ ws_keys, float* __restrict__ ws_box, int* __restrict__ keep_pos,
+    unsigned long long* __restrict__ ws_keys, float* __restrict__ ws_box, unsigned long long* __restrict__ ws_alive,
+    int alive_stride, int* __restrict__ keep_pos,
     int* __restrict__ keep_count, int* __restrict__ sel_pos, int* __restrict__ sel_count) {
   __shared__ unsigned long long lkeys[SORT_LDS_KEYS];  // sort scratch, later alive bitmap + kept boxes
   __shared__ int s_kc;
   __shared__ float s_best_area[NMS_THREADS / 64];
   __shared__ int s_best_rank[NMS_THREADS / 64];
   const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = cand_count[img];
+  const int K = min(cand_count[img], cap);
   const float* score = cand_score + (long)img * cap;
   const float4* box = reinterpret_cast<const float4*>(cand_box) + (long)img * cap;
   int* kpos = keep_pos + (long)img * cap;
@@ -216,6 +288,7 @@ __global__ void __launch_bounds__(NMS_THREADS) retina_nms_kernel(
   }
   int Kp = 64;
   while (Kp < K) Kp <<= 1;
+  const int nwords = (K + 63) >> 6;
   unsigned long long* gkeys = ws_keys + (long)img * cap_p2;
   float* sbox = ws_box + (long)img * cap_p2 * 5;  // x1,y1,x2,y2,area in sorted order
 
@@ -268,67 +341,11 @@ __global__ void __launch_bounds__(NMS_THREADS) retina_nms_kernel(
   __threadfence_block();
   __syncthreads();
 
-  // ---- 4. tiled greedy NMS.  LDS reuse: alive bitmap (Kp/64 words) then kept-box tile.
-  unsigned long long* alive = lkeys;                                   // up to NMS_ALIVE_WORDS words
-  float* tile = reinterpret_cast<float*>(lkeys + NMS_ALIVE_WORDS);     // 64 * 5 floats
-  int* tile_n = reinterpret_cast<int*>(tile + 64 * 5);
-  const int nwords = (K + 63) >> 6;
-  for (int wd = tid; wd < nwords; wd += NMS_THREADS) {
-    const int lo = wd << 6;
-    unsigned long long m = 0ull;
-    if (lo + 64 <= K) m = ~0ull;
-    else if (lo < K) m = (1ull << (K - lo)) - 1ull;
-    alive[wd] = m;
-  }
-  if (tid == 0) s_kc = 0;
-  __syncthreads();
-
-  const int ntiles = (K + 63) >> 6;
-  for (int t = 0; t < ntiles; ++t) {
-    if (wave == 0) {
-      const int c = (t << 6) + lane;
-      float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, area = 0.f;
-      if (c < K) { x1 = sbox[c * 5]; y1 = sbox[c * 5 + 1]; x2 = sbox[c * 5 + 2]; y2 = sbox[c * 5 + 3]; area = sbox[c * 5 + 4]; }
-      bool me = (alive[t] >> lane) & 1ull;
-      for (int b = 0; b < 64; ++b) {
-        const unsigned long long m = __ballot(me);
-        if (!((m >> b) & 1ull)) continue;  // wave-uniform
-        const float kx1 = __shfl(x1, b), ky1 = __shfl(y1, b), kx2 = __shfl(x2, b), ky2 = __shfl(y2, b);
-        const float ka = __shfl(area, b);
-        if (lane > b && me && suppressed(kx1, ky1, kx2, ky2, ka, x1, y1, x2, y2, area, thr)) me = false;
-      }
-      const unsigned long long m = __ballot(me);
-      const int rank = __popcll(m & ((1ull << lane) - 1ull));
-      const int kc = s_kc;
-      if (me) {
-        kpos[kc + rank] = (int)(unsigned)(gkeys[c] & 0xffffffffull);
-        tile[rank * 5 + 0] = x1; tile[rank * 5 + 1] = y1; tile[rank * 5 + 2] = x2; tile[rank * 5 + 3] = y2;
-        tile[rank * 5 + 4] = area;
-      }
-      if (lane == 0) { *tile_n = __popcll(m); s_kc = kc + __popcll(m); }
-    }
-    __syncthreads();
-    const int nk = *tile_n;
-    if (nk > 0) {
-      for (int wd = t + 1 + wave; wd < nwords && (wd << 6) < K; wd += NMS_THREADS / 64) {
-        const unsigned long long m = alive[wd];
-        if (m == 0ull) continue;  // wave-uniform
-        bool me = (m >> lane) & 1ull;
-        if (me) {
-          const int c = (wd << 6) + lane;
-          const float x1 = sbox[c * 5], y1 = sbox[c * 5 + 1], x2 = sbox[c * 5 + 2], y2 = sbox[c * 5 + 3];
-          const float area = sbox[c * 5 + 4];
-          for (int q = 0; q < nk; ++q) {
-            if (suppressed(tile[q * 5], tile[q * 5 + 1], tile[q * 5 + 2], tile[q * 5 + 3], tile[q * 5 + 4], x1,
-                           y1, x2, y2, area, thr)) { me = false; break; }
-          }
-        }
-        const unsigned long long nm = __ballot(me);
-        if (lane == 0) alive[wd] = nm;
-      }
-    }
-    __syncthreads();
-  }
+  // ---- 4. tiled greedy NMS: the alive bitmap in LDS for K <= NMS_LDS_CAP (every frame up to 3512^2), else in the workspace
+  if (nwords <= NMS_ALIVE_WORDS)
+    greedy_nms<false>(lkeys, lkeys, sbox, gkeys, kpos, K, thr, s_kc, tid, lane, wave);
+  else
+    greedy_nms<true>(ws_alive + (long)img * alive_stride, lkeys, sbox, gkeys, kpos, K, thr, s_kc, tid, lane, wave);
   const int kc = s_kc;
   if (tid == 0) keep_count[img] = kc;
 
@@ -428,8 +445,11 @@ inline int pow2_ceil(int v) { int p = 64; while (p < v) p <<= 1; return p; }
 
 }  // namespace
 
+// sort keys (8 B) and sorted boxes + areas (20 B) per candidate slot; above NMS_LDS_CAP also the alive bitmap (1 bit)
 extern "C" int64_t fcp_retina_nms_workspace_bytes(int n, int cap) {
-  return (int64_t)n * pow2_ceil(cap) * (8 + 5 * 4);
+  if (n <= 0 || cap <= 0 || cap > NMS_MAX_CAP) return 0;
+  const int64_t cap_p2 = pow2_ceil(cap);
+  return (int64_t)n * cap_p2 * (8 + 5 * 4) + (cap > NMS_LDS_CAP ? (int64_t)n * (cap_p2 / 64) * 8 : 0);
 }
 
 extern "C" int fcp_retina_decode(const float* head0, const float* head1, const float* head2, int n,
@@ -470,8 +490,9 @@ extern "C" int fcp_retina_nms_select(const float* cand_score, const float* cand_
   const int cap_p2 = pow2_ceil(cap);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(workspace);
   float* sbox = reinterpret_cast<float*>(keys + (size_t)n * cap_p2);
+  unsigned long long* alive = cap > NMS_LDS_CAP ? reinterpret_cast<unsigned long long*>(sbox + (size_t)n * cap_p2 * 5) : nullptr;
   hipLaunchKernelGGL(retina_nms_kernel, dim3(n), dim3(NMS_THREADS), 0, (hipStream_t)stream, cand_score,
-                     cand_box, cand_count, cap, cap_p2, nms_threshold, strategy, keys, sbox, keep_pos,
+                     cand_box, cand_count, cap, cap_p2, nms_threshold, strategy, keys, sbox, alive, cap_p2 / 64, keep_pos,
                      keep_count, sel_pos, sel_count);
   FCP_LAUNCH_OK();
   return 0;
