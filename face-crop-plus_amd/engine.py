@@ -447,6 +447,29 @@ class Autotune:
         return path
 
     @classmethod
+    def choose(cls, key, candidates, trial_desc):
+        """The tile ``conv`` launches shape ``key`` with, or None for the heuristic one: the cached pick (a shape tuned once keeps
+        its tile after tuning is switched off; a pick this build no longer offers is dropped), else — while tuning is on — the
+        winner of ``pick``.  ``trial_desc()``: the ``ConvDesc`` the timing launches run, built only when the shape is tuned."""
+        cls.ensure_loaded()
+        if not (cls.enabled or cls.cache):
+            return None
+        best = cls.cache.get(key)
+        if best is not None and tuple(best) not in candidates:
+            with cls._lock:                  # (save() walks the cache under the same lock in another GPU worker thread)
+                cls.cache.pop(key, None)     # a pick from an older table that this build no longer offers
+            best = None
+        if best is None and cls.enabled:
+            d = trial_desc()
+            base_flags = d.flags
+
+            def trial(t):
+                d.tile_m, d.tile_n, d.flags = t[0], t[1], base_flags | (t[2] if len(t) > 2 else 0)
+                _c_launch("fcp_conv2d_nhwc_f32", C.byref(d))
+            best = cls.pick(key, candidates, trial)
+        return best
+
+    @classmethod
     def pick(cls, key, candidates, launch):
         best = cls.cache.get(key)
         if best is not None:
@@ -511,29 +534,13 @@ class Autotune:
 
 
 class ConvStats:
-    """Algorithmic-FLOP accounting of conv launches (bench / roofline)."""
-    enabled = False
-    flops = 0
-    launches = 0
+    """Per-launch accounting of the conv engine (``conv``, ``bottleneck_chain``, the fused stems), filled by ``_accounted``."""
     timing = None  # list of (start_event, end_event, flops, label, algorithmic bytes) when per-launch timing is on
-    # list of (label, flops, algorithmic bytes, relaunch) when capture is on: ``relaunch()`` enqueues the very same launch again
-    # (same descriptor, same tensors — kept alive by the closure) on the current stream.  tools/launch_ledger.py loops each
-    # launch of a step on its own while clock / power are sampled (ctypes boundary only: the registered ops build no descriptor).
+    # list of (label, flops, algorithmic bytes, relaunch) when capture is on: ``relaunch()`` enqueues the same launch again through
+    # the C ABI (same descriptor, same tensors — kept alive by the closure) on the current stream, whichever boundary the live
+    # launch took; an output that overlaps one of the launch's inputs is written to a scratch tensor instead, so a relaunch is
+    # idempotent.  tools/launch_ledger.py loops each launch of a step on its own while clock / power are sampled.
     replay = None
-
-    @classmethod
-    def note(cls, timing, e0, e1, flops, label, byts, relaunch=None):
-        if timing is not None:
-            e1.record()
-            timing.append((e0, e1, flops, label, byts))
-        if cls.replay is not None and relaunch is not None:
-            cls.replay.append((label, flops, byts, relaunch))
-
-    @classmethod
-    def reset(cls):
-        cls.flops, cls.launches = 0, 0
-        if cls.timing is not None:
-            cls.timing = []
 
 
 class RangeMonitor:
@@ -632,12 +639,88 @@ def selfcheck_at_load(model, sd, weights, precision, repack_f32):
         model.selfcheck_report = {"fallback": "f32", "reason": str(e)}
 
 
-def _monitor(label, *outs):
+def _c_launch(fn: str, *args):
+    """Enqueue the C-ABI entry point ``fn(*args)`` on the current stream."""
+    N.check(getattr(N.lib(), fn)(*args, N.stream_ptr()), fn)
+
+
+def _filter(pc: PackedConv | None):
+    """(w, wscale, bias) of an optional packed filter."""
+    return (None, None, None) if pc is None else (pc.w, pc.wscale, pc.bias)
+
+
+def _alias_safe_out(out: Act, *ins: Act | None) -> Act:
+    """The view a repeated launch may write in place of ``out``.  A launch whose output overlaps one of its inputs (RRDB's last
+    dense-block conv writes the buffer its second residual is read from) is not idempotent: a scratch tensor of the output
+    view's geometry (its own pixel pitch, not a copy of the whole buffer) is returned then.  Only a real overlap counts:
+    reading and writing disjoint channel slices of one buffer (RRDB's dense-block convs, SSH's concat) is idempotent."""
+    st = out.buf.untyped_storage().data_ptr()
+    if any(t is not None and t.buf.untyped_storage().data_ptr() == st and t.c0 < out.c0 + out.c and out.c0 < t.c0 + t.c
+           for t in ins):
+        return Act.empty(out.n, out.h, out.w, out.c, out.buf.device, out.fmt)
+    return out
+
+
+def _accounted(go, describe, relaunch):
+    """One conv-engine launch and its accounting.  ``go()`` enqueues the launch (registered op or C ABI) and returns its output
+    views (a tuple; None for an absent one).  While per-launch timing, capture or a ``RangeMonitor`` is on, ``describe()`` ->
+    (label, monitor label, algorithmic FLOP, algorithmic bytes) feeds ``ConvStats.timing`` (HIP events around the launch),
+    ``ConvStats.replay`` and the monitor.  ``relaunch(*outputs)`` -> (C entry point, its arguments, the tensors they point
+    into) of the same launch: only called while capture is on; the replay closure keeps those tensors alive."""
+    timing, replay = ConvStats.timing, ConvStats.replay
+    if timing is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    outs = go()
+    if timing is None and replay is None and RangeMonitor.active is None:
+        return outs
+    label, mon_label, flops, byts = describe()
+    if timing is not None:
+        e1.record()
+        timing.append((e0, e1, flops, label, byts))
+    if replay is not None:
+        fn, args, keep = relaunch(*outs)
+        replay.append((label, flops, byts, lambda keep=keep: _c_launch(fn, *args)))
     mon = RangeMonitor.active
     if mon is not None:
         for i, t in enumerate(outs):
             if t is not None and t.c % 8 == 0:
-                mon.see(label if i == 0 else f"{label} [output {i}]", t)
+                mon.see(mon_label if i == 0 else f"{mon_label} [output {i}]", t)
+    return outs
+
+
+def _conv_desc(pc: PackedConv, x: Act, out: Act, x2, x2_stride, res1, res1_pre, res2, alpha, alpha2, act_slope, in_up2, band,
+               tile_m, tile_n, flags, cu_budget) -> N.ConvDesc:
+    """The ``fcp_conv_desc`` of one ``conv`` launch (arguments as ``conv`` takes them, tile and flags resolved)."""
+    in_h, in_w = (x.h * 2, x.w * 2) if in_up2 else (x.h, x.w)
+    d = N.ConvDesc()
+    d.in_, d.w, d.out = x.ptr(), N.ptr(pc.w), out.ptr()
+    if x2 is not None:
+        d.in2, d.cin2, d.in2_ld, d.in2_h, d.in2_w, d.in2_stride = x2.ptr(), x2.c, x2.ld, x2.h, x2.w, x2_stride
+    d.bias = N.ptr(pc.bias)
+    d.wscale = N.ptr(pc.wscale)
+    d.precision = pc.precision
+    d.in_fmt, d.out_fmt = x.fmt, out.fmt
+    d.res1_fmt = res1.fmt if res1 is not None else 0
+    d.res2_fmt = res2.fmt if res2 is not None else 0
+    d.res1 = res1.ptr() if res1 is not None else None
+    d.res2 = res2.ptr() if res2 is not None else None
+    d.n, d.in_h, d.in_w = x.n, in_h, in_w
+    d.cin, d.in_ld, d.in_up2 = pc.cin, x.ld, int(in_up2)
+    d.cout, d.kh, d.kw, d.stride, d.pad = pc.cout, pc.kh, pc.kw, pc.stride, pc.pad
+    d.out_h, d.out_w, d.out_ld = out.h, out.w, out.ld
+    d.tile_m, d.tile_n = tile_m, tile_n
+    d.cin4 = int(pc.cin4)
+    d.act_slope, d.alpha, d.alpha2 = act_slope, alpha, alpha2
+    d.res1_pre = int(res1_pre)
+    d.flags = flags
+    d.cu_budget = cu_budget
+    d.band_top, d.band_bottom = band
+    if res1 is not None:
+        d.res1_ld, d.res1_h, d.res1_w = res1.ld, res1.h, res1.w
+    if res2 is not None:
+        d.res2_ld = res2.ld
+    return d
 
 
 def conv(pc: PackedConv, x: Act, out: Act | None = None, *, act_slope: float = 1.0,
@@ -663,38 +746,15 @@ def conv(pc: PackedConv, x: Act, out: Act | None = None, *, act_slope: float = 1
     assert (out.n, out.h, out.w, out.c) == (x.n, oh, ow, pc.cout), "conv: bad output view"
     if (x.fmt or out.fmt or (res1 is not None and res1.fmt) or (res2 is not None and res2.fmt)) and pc.precision != 1:
         raise ValueError("split32 tensors can only be used with filters packed for the fp16x3 path")
+    assert x2 is None or (x2.fmt == 1 and x.fmt == 1 and x2.n == x.n), "two-source convs take split32 tensors"
+    assert res1 is None or (res1.c == pc.cout and res1.n == x.n)
+    assert res2 is None or (res2.n, res2.h, res2.w, res2.c) == (x.n, oh, ow, pc.cout)
     m = x.n * oh * ow
-    d = N.ConvDesc()
-    d.in_, d.w, d.out = x.ptr(), N.ptr(pc.w), out.ptr()
-    if x2 is not None:
-        assert x2.fmt == 1 and x.fmt == 1 and x2.n == x.n, "two-source convs take split32 tensors"
-        d.in2, d.cin2, d.in2_ld, d.in2_h, d.in2_w, d.in2_stride = x2.ptr(), x2.c, x2.ld, x2.h, x2.w, x2_stride
-    d.bias = N.ptr(pc.bias)
-    d.wscale = N.ptr(pc.wscale)
-    d.precision = pc.precision
-    d.in_fmt, d.out_fmt = x.fmt, out.fmt
-    d.res1_fmt = res1.fmt if res1 is not None else 0
-    d.res2_fmt = res2.fmt if res2 is not None else 0
-    d.res1 = res1.ptr() if res1 is not None else None
-    d.res2 = res2.ptr() if res2 is not None else None
-    d.n, d.in_h, d.in_w = x.n, in_h, in_w
-    d.cin, d.in_ld, d.in_up2 = pc.cin, x.ld, int(in_up2)
-    d.cout, d.kh, d.kw, d.stride, d.pad = pc.cout, pc.kh, pc.kw, pc.stride, pc.pad
-    d.out_h, d.out_w, d.out_ld = oh, ow, out.ld
-    d.tile_n = tile_n or _pick_tile_n(pc.cout, m)
-    d.tile_m = tile_m or 128
-    d.cin4 = int(pc.cin4)
-    d.act_slope, d.alpha, d.alpha2 = act_slope, alpha, alpha2
-    d.res1_pre = int(res1_pre)
-    d.flags = (N.CONV_FLAT_ADDR if flat else 0) | (N.CONV_BALANCE_TAIL if balance_tail else 0)
-    d.cu_budget = getattr(_budget, "cus", 0)
-    d.band_top, d.band_bottom = band
-    if res1 is not None:
-        assert res1.c == pc.cout and res1.n == x.n
-        d.res1_ld, d.res1_h, d.res1_w = res1.ld, res1.h, res1.w
-    if res2 is not None:
-        assert (res2.n, res2.h, res2.w, res2.c) == (x.n, oh, ow, pc.cout)
-        d.res2_ld = res2.ld
+    tm, tn = tile_m or 128, tile_n or _pick_tile_n(pc.cout, m)
+    flags = (N.CONV_FLAT_ADDR if flat else 0) | (N.CONV_BALANCE_TAIL if balance_tail else 0)
+    cu = getattr(_budget, "cus", 0)
+    desc = lambda o: _conv_desc(pc, x, o, x2, x2_stride, res1, res1_pre, res2, alpha, alpha2, act_slope, in_up2, band,
+                                tm, tn, flags, cu)
     big_ok = (pc.precision == 1 and x.fmt == 1 and not pc.cin4 and not in_up2 and pc.cout % 8 == 0
               and pc.cout >= 128 and m >= 256 * 64)
     halo_ok = (pc.precision == 1 and x.fmt == 1 and not pc.cin4 and (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1)
@@ -704,71 +764,40 @@ def conv(pc: PackedConv, x: Act, out: Act | None = None, *, act_slope: float = 1
     wide_ok = (pc.precision == 1 and x.fmt == 1 and not pc.cin4 and (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1)
                and pc.cout % 8 == 0 and pc.cin % 64 == 0 and x2 is None and 64 < pc.cout <= 128 and res1 is None and res2 is None)
     if tile_n is None and tile_m is None and (pc.cout > 64 or halo_ok):
-        Autotune.ensure_loaded()
-    if tile_n is None and tile_m is None and (pc.cout > 64 or halo_ok) and (Autotune.enabled or Autotune.cache):
         key = (pc.cin, pc.cout, pc.kh, pc.kw, pc.stride, m, int(in_up2), res1 is not None, res2 is not None,
-               pc.precision, x.fmt, out.fmt, None if x2 is None else (x2.c, x2_stride), d.cu_budget)
-        cands = tile_candidates(pc.cout, halo_ok, wide_ok, big_ok)
-        best = Autotune.cache.get(key)          # a tuned shape keeps its tile after tuning is switched off
-        if best is not None and tuple(best) not in cands:
-            with Autotune._lock:                # (save() walks the cache under the same lock in another GPU worker thread)
-                Autotune.cache.pop(key, None)   # a pick from an older table that this build no longer offers
-            best = None
-        if best is None and Autotune.enabled:
-            # Tuning launches the op several times.  An op whose output aliases one of its inputs (RRDB's last dense-block
-            # conv writes the buffer its second residual is read from) is not idempotent: its trial launches write a
-            # scratch tensor of the same geometry instead, and only the final launch below touches the real output.
-            # Only a real overlap counts: reading and writing disjoint channel slices of one buffer (RRDB's dense-block
-            # convs, SSH's concat) is idempotent.  The scratch holds just the output view (its own pixel pitch), not a
-            # copy of the whole buffer.
-            real_out, real_ld = d.out, d.out_ld
-            same = lambda t: t is not None and t.buf.untyped_storage().data_ptr() == out.buf.untyped_storage().data_ptr()
-            aliased = any(same(t) and t.c0 < out.c0 + out.c and out.c0 < t.c0 + t.c for t in (x, x2, res1, res2))
-            scratch = torch.empty((out.n, out.h, out.w, out.c), dtype=torch.float32, device=out.buf.device) if aliased else None
-
-            base_flags = d.flags
-
-            def _launch(t):
-                d.tile_m, d.tile_n = t[0], t[1]
-                d.flags = base_flags | (t[2] if len(t) > 2 else 0)
-                if scratch is not None:
-                    d.out, d.out_ld = N.ptr(scratch), out.c
-                N.check(N.lib().fcp_conv2d_nhwc_f32(C.byref(d), N.stream_ptr()), "fcp_conv2d_nhwc_f32")
-                d.out, d.out_ld = real_out, real_ld
-            best = Autotune.pick(key, cands, _launch)
-            d.flags = base_flags
+               pc.precision, x.fmt, out.fmt, None if x2 is None else (x2.c, x2_stride), cu)
+        # the tuner launches the op several times: its trials write where a relaunch would (_alias_safe_out)
+        best = Autotune.choose(key, tile_candidates(pc.cout, halo_ok, wide_ok, big_ok),
+                               lambda: desc(_alias_safe_out(out, x, x2, res1, res2)))
         if best is not None:
-            d.tile_m, d.tile_n = best[0], best[1]
-            d.flags |= best[2] if len(best) > 2 else 0
-    timing = ConvStats.timing
-    if timing is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if T.ENABLED:            # FCP_BOUNDARY=torch: the same launch through the registered PyTorch custom op (out variant)
-        T.load().conv2d_out(x.buf, x.c0, pc.cin, pc.w, pc.bias, pc.wscale, None if res1 is None else res1.buf,
-                            0 if res1 is None else res1.c0, None if res2 is None else res2.buf, 0 if res2 is None else res2.c0,
-                            out.buf, out.c0, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, float(act_slope), float(alpha), float(alpha2),
-                            bool(res1_pre), pc.precision, x.fmt, out.fmt, d.res1_fmt, d.res2_fmt, bool(in_up2), bool(pc.cin4),
-                            int(d.tile_m), int(d.tile_n), None if x2 is None else x2.buf, 0 if x2 is None else x2.c0,
-                            0 if x2 is None else x2.c, int(x2_stride), int(d.flags), int(d.cu_budget), int(band[0]), int(band[1]))
-    else:
-        N.check(N.lib().fcp_conv2d_nhwc_f32(C.byref(d), N.stream_ptr()), "fcp_conv2d_nhwc_f32")
-    if timing is not None or ConvStats.replay is not None:
+            tm, tn = best[0], best[1]
+            flags |= best[2] if len(best) > 2 else 0
+
+    def go():
+        if T.ENABLED:        # FCP_BOUNDARY=torch: the same launch through the registered PyTorch custom op (out variant)
+            T.load().conv2d_out(x.buf, x.c0, pc.cin, pc.w, pc.bias, pc.wscale, None if res1 is None else res1.buf,
+                                0 if res1 is None else res1.c0, None if res2 is None else res2.buf, 0 if res2 is None else res2.c0,
+                                out.buf, out.c0, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, float(act_slope), float(alpha),
+                                float(alpha2), bool(res1_pre), pc.precision, x.fmt, out.fmt, 0 if res1 is None else res1.fmt,
+                                0 if res2 is None else res2.fmt, bool(in_up2), bool(pc.cin4), int(tm), int(tn),
+                                None if x2 is None else x2.buf, 0 if x2 is None else x2.c0, 0 if x2 is None else x2.c,
+                                int(x2_stride), int(flags), int(cu), int(band[0]), int(band[1]))
+        else:
+            _c_launch("fcp_conv2d_nhwc_f32", C.byref(desc(out)))
+        return (out,)
+
+    def describe():
         byts = 4 * (m * (pc.cout + (pc.cout if res1 is not None else 0) + (pc.cout if res2 is not None else 0))
                     + x.n * in_h * in_w * x.c // (4 if in_up2 else 1) + (m * x2.c if x2 is not None else 0)
                     + pc.cout * pc.cin * pc.kh * pc.kw)
-        keep = (pc, x, x2, res1, res2, out)
-        ConvStats.note(timing, e0 if timing is not None else None, e1 if timing is not None else None, pc.flops_per_pixel * m,
-                       f"conv {pc.kh}x{pc.kw} s{pc.stride} {pc.cin}->{pc.cout} @{oh}x{ow} tile {d.tile_m}x{d.tile_n}"
-                       f"{' bal' if d.flags & N.CONV_BALANCE_TAIL else ''}{' +res' if res1 is not None else ''}", byts,
-                       lambda d=d, keep=keep: N.check(N.lib().fcp_conv2d_nhwc_f32(C.byref(d), N.stream_ptr()), "fcp_conv2d_nhwc_f32"))
-    if ConvStats.enabled:
-        ConvStats.flops += pc.flops_per_pixel * m
-        ConvStats.launches += 1
-    if RangeMonitor.active is not None:
-        _monitor(f"conv {pc.kh}x{pc.kw} s{pc.stride} {pc.cin}->{pc.cout} @{oh}x{ow}", out)
-    return out
+        head = f"conv {pc.kh}x{pc.kw} s{pc.stride} {pc.cin}->{pc.cout} @{oh}x{ow}"
+        return (f"{head} tile {tm}x{tn}{' bal' if flags & N.CONV_BALANCE_TAIL else ''}{' +res' if res1 is not None else ''}",
+                head, pc.flops_per_pixel * m, byts)
+
+    def relaunch(o):
+        o = _alias_safe_out(o, x, x2, res1, res2)
+        return "fcp_conv2d_nhwc_f32", (C.byref(desc(o)),), (pc, x, x2, res1, res2, o)
+    return _accounted(go, describe, relaunch)[0]
 
 
 def tile_candidates(cout: int, halo_ok: bool, wide_ok: bool, big_ok: bool):
@@ -816,6 +845,24 @@ def chain_supported(pc2: PackedConv | None, pc3: PackedConv, pc1n: PackedConv | 
 
 
 
+def _chain_desc(pc2, pc3, pc1n, t1, res, out, t1n, tile_m, flags, t1b, t1b_stride) -> N.ChainDesc:
+    """The ``fcp_chain_desc`` of one ``bottleneck_chain`` launch (``pc1n`` None: the expand form, cn = 0)."""
+    d = N.ChainDesc()
+    d.t1, d.res, d.out = t1.ptr(), (res.ptr() if res is not None else None), out.ptr()
+    d.t1n = t1n.ptr() if t1n is not None else None
+    d.w2, d.ws2, d.b2 = map(N.ptr, _filter(pc2))
+    d.w3, d.ws3, d.b3 = map(N.ptr, _filter(pc3))
+    d.w1n, d.ws1n, d.b1n = map(N.ptr, _filter(pc1n))
+    d.n, d.h, d.w, d.c, d.nout = t1.n, t1.h, t1.w, pc3.cin, pc3.cout    # c: all of conv3's input channels
+    d.cn = pc1n.cout if pc1n is not None else 0
+    d.t1_ld, d.res_ld, d.out_ld = t1.ld, (res.ld if res is not None else 0), out.ld
+    d.t1n_ld = t1n.ld if t1n is not None else 0
+    d.tile_m, d.flags = tile_m, flags
+    if t1b is not None:
+        d.t1b, d.cb, d.t1b_ld, d.t1b_h, d.t1b_w, d.t1b_stride = t1b.ptr(), t1b.c, t1b.ld, t1b.h, t1b.w, t1b_stride
+    return d
+
+
 def bottleneck_chain(pc2: PackedConv | None, pc3: PackedConv, pc1n: PackedConv, t1: Act, res: Act | None,
                      out: Act | None = None, t1n: Act | None = None, tile_m: int = 0, out_even_only: bool = False,
                      t1b: Act | None = None, t1b_stride: int = 1):
@@ -827,107 +874,53 @@ def bottleneck_chain(pc2: PackedConv | None, pc3: PackedConv, pc1n: PackedConv, 
     ``out``, for the pair forms or where a ``RangeMonitor`` wants to see the whole tensor.  ``tile_m``: the descriptor's tile
     hint, passed through (the library picks the form by shape and may ignore it; every value gives the same bits).  ``t1b`` (two-source
     pair): the trailing ``t1b.c`` input channels of conv3 are read from ``t1b`` at ``(y * t1b_stride, x * t1b_stride)`` —
-    what ``conv(..., x2=, x2_stride=)`` does for the stand-alone two-source conv."""
+    what ``conv(..., x2=, x2_stride=)`` does for the stand-alone two-source conv.  ``pc1n`` None: the expand form (cn = 0),
+    out = relu(conv3(t1) + res), bit-identical to ``conv(pc3, t1, act_slope=0, res1=res, res1_pre=True, out_fmt=1)``;
+    returns (out, None)."""
     cb = t1b.c if t1b is not None else 0
     assert chain_supported(pc2, pc3, pc1n, res is not None, cb), "bottleneck_chain: unsupported shapes"
-    if pc1n is None:
-        return _expand_conv3(pc3, t1, res, out)
     assert t1.fmt == 1 and t1.c + cb == pc3.cin and (res is None or (res.fmt == 1 and res.c == pc3.cout))
     assert t1b is None or (t1b.fmt == 1 and t1b.n == t1.n and (t1.h - 1) * t1b_stride < t1b.h and (t1.w - 1) * t1b_stride < t1b.w)
     assert res is None or (t1.n, t1.h, t1.w) == (res.n, res.h, res.w)
-    dev = t1.buf.device
-    m = t1.n * t1.h * t1.w
-    flops = ((pc2.flops_per_pixel if pc2 is not None else 0) + pc3.flops_per_pixel + pc1n.flops_per_pixel) * m
-    timing = ConvStats.timing
-    if timing is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    opt = lambda pc, f: None if pc is None else getattr(pc, f)
+    c, nout, cn = pc3.cin, pc3.cout, (pc1n.cout if pc1n is not None else 0)
     flags = N.CHAIN_OUT_EVEN_ONLY if (out_even_only and pc2 is not None and RangeMonitor.active is None) else 0
-    d = None
-    if T.ENABLED and out is None and t1n is None:
-        # FCP_BOUNDARY=torch: the registered custom op allocates and returns both tensors
-        o, t = T.load().bottleneck_chain(t1.buf, t1.c0, None if res is None else res.buf, 0 if res is None else res.c0,
-                                         opt(pc2, "w"), opt(pc2, "wscale"), opt(pc2, "bias"), pc3.w, pc3.wscale, pc3.bias,
-                                         pc1n.w, pc1n.wscale, pc1n.bias, pc3.cin, pc3.cout, pc1n.cout, tile_m, flags,
-                                         None if t1b is None else t1b.buf, 0 if t1b is None else t1b.c0, cb, int(t1b_stride))
-        out, t1n = Act(o, fmt=1), Act(t, fmt=1)
-    else:
+    via_op = T.ENABLED and out is None and t1n is None     # the registered op allocates its outputs; explicit views go through the C ABI
+    if not via_op:
         if out is None:
-            out = Act.empty(t1.n, t1.h, t1.w, pc3.cout, dev, 1)
-        if t1n is None:
-            t1n = Act.empty(t1.n, t1.h, t1.w, pc1n.cout, dev, 1)
-        assert out.fmt == 1 and t1n.fmt == 1 and (out.n, out.h, out.w, out.c) == (t1.n, t1.h, t1.w, pc3.cout)
-        assert (t1n.n, t1n.h, t1n.w, t1n.c) == (t1.n, t1.h, t1.w, pc1n.cout)
-        d = N.ChainDesc()
-        d.t1, d.res, d.out, d.t1n = t1.ptr(), (res.ptr() if res is not None else None), out.ptr(), t1n.ptr()
-        d.w2, d.ws2, d.b2 = N.ptr(opt(pc2, "w")), N.ptr(opt(pc2, "wscale")), N.ptr(opt(pc2, "bias"))
-        d.w3, d.ws3, d.b3 = N.ptr(pc3.w), N.ptr(pc3.wscale), N.ptr(pc3.bias)
-        d.w1n, d.ws1n, d.b1n = N.ptr(pc1n.w), N.ptr(pc1n.wscale), N.ptr(pc1n.bias)
-        d.n, d.h, d.w, d.c, d.cn, d.nout = t1.n, t1.h, t1.w, pc3.cin, pc1n.cout, pc3.cout    # c: all of conv3's input channels
-        d.t1_ld, d.res_ld, d.out_ld, d.t1n_ld = t1.ld, (res.ld if res is not None else 0), out.ld, t1n.ld
-        d.tile_m, d.flags = tile_m, flags
-        if t1b is not None:
-            d.t1b, d.cb, d.t1b_ld, d.t1b_h, d.t1b_w, d.t1b_stride = t1b.ptr(), cb, t1b.ld, t1b.h, t1b.w, t1b_stride
-        N.check(N.lib().fcp_bottleneck_chain_f16x3(C.byref(d), N.stream_ptr()), "fcp_bottleneck_chain_f16x3")
-    if timing is not None or ConvStats.replay is not None:
-        c, nout, cn = pc3.cin, pc3.cout, pc1n.cout
+            out = Act.empty(t1.n, t1.h, t1.w, nout, t1.buf.device, 1)
+        if t1n is None and pc1n is not None:
+            t1n = Act.empty(t1.n, t1.h, t1.w, cn, t1.buf.device, 1)
+        assert out.fmt == 1 and (out.n, out.h, out.w, out.c) == (t1.n, t1.h, t1.w, nout)
+        assert pc1n is None or (t1n.fmt == 1 and (t1n.n, t1n.h, t1n.w, t1n.c) == (t1.n, t1.h, t1.w, cn))
+    desc = lambda o, o1n: _chain_desc(pc2, pc3, pc1n, t1, res, o, o1n, tile_m, flags, t1b, t1b_stride)
+
+    def go():
+        if not via_op:
+            _c_launch("fcp_bottleneck_chain_f16x3", C.byref(desc(out, t1n)))
+            return out, t1n
+        o, t = T.load().bottleneck_chain(t1.buf, t1.c0, None if res is None else res.buf, 0 if res is None else res.c0,
+                                         *_filter(pc2), *_filter(pc3), *_filter(pc1n), c, nout, cn, tile_m, flags,
+                                         None if t1b is None else t1b.buf, 0 if t1b is None else t1b.c0, cb, int(t1b_stride))
+        return Act(o, fmt=1), (Act(t, fmt=1) if pc1n is not None else None)
+
+    def describe():
+        m = t1.n * t1.h * t1.w
+        flops = ((pc2.flops_per_pixel if pc2 is not None else 0) + pc3.flops_per_pixel
+                 + (pc1n.flops_per_pixel if pc1n is not None else 0)) * m
         byts = 4 * (m * (c + (nout if not flags else nout // 4) + (nout if res is not None else 0) + cn) + (0 if pc2 is None else 9 * c * c)
                     + c * nout + nout * cn)
-        relaunch = None
-        if d is not None:
-            keep = (pc2, pc3, pc1n, t1, res, out, t1n, t1b)
-            relaunch = lambda d=d, keep=keep: N.check(N.lib().fcp_bottleneck_chain_f16x3(C.byref(d), N.stream_ptr()), "fcp_bottleneck_chain_f16x3")
-        ConvStats.note(timing, e0 if timing is not None else None, e1 if timing is not None else None, flops,
-                       f"chain {'3x3 ' if pc2 is not None else ''}{c}->{nout}->{cn} @{t1.h}x{t1.w}"
-                       f"{' +res' if res is not None else ''}{' out@even' if flags else ''}{' two-source' if t1b is not None else ''}", byts, relaunch)
-    if ConvStats.enabled:
-        ConvStats.flops += flops
-        ConvStats.launches += 1
-    if RangeMonitor.active is not None:
-        _monitor(f"chain {'3x3 ' if pc2 is not None else ''}{pc3.cin}->{pc3.cout}->{pc1n.cout} @{t1.h}x{t1.w}", out, t1n)
-    return out, t1n
+        if pc1n is None:
+            head = f"expand {c}->{nout} @{t1.h}x{t1.w}"
+            return f"{head} +res", head, flops, byts
+        head = f"chain {'3x3 ' if pc2 is not None else ''}{c}->{nout}->{cn} @{t1.h}x{t1.w}"
+        return (f"{head}{' +res' if res is not None else ''}{' out@even' if flags else ''}{' two-source' if t1b is not None else ''}",
+                head, flops, byts)
 
-
-def _expand_conv3(pc3: PackedConv, t1: Act, res: Act, out: Act | None):
-    """The expand form of ``fcp_bottleneck_chain_f16x3`` (cn = 0, no conv1' filter): out = relu(conv3(t1) + res), bit-identical to
-    ``conv(pc3, t1, act_slope=0, res1=res, res1_pre=True, out_fmt=1)``.  Returns (out, None)."""
-    assert t1.fmt == 1 and res is not None and res.fmt == 1 and (t1.n, t1.h, t1.w) == (res.n, res.h, res.w)
-    m = t1.n * t1.h * t1.w
-    via_op = T.ENABLED and out is None        # the registered op allocates its output; an explicit view goes through the C ABI
-    if out is None and not via_op:
-        out = Act.empty(t1.n, t1.h, t1.w, pc3.cout, t1.buf.device, 1)
-    assert out is None or (out.fmt == 1 and (out.n, out.h, out.w, out.c) == (t1.n, t1.h, t1.w, pc3.cout))
-    timing = ConvStats.timing
-    if timing is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if via_op:
-        # FCP_BOUNDARY=torch: the same registered op as the other chain forms (no next-conv1 filter, cn = 0)
-        o, _ = T.load().bottleneck_chain(t1.buf, t1.c0, res.buf, res.c0, None, None, None, pc3.w, pc3.wscale, pc3.bias,
-                                         None, None, None, pc3.cin, pc3.cout, 0, 0, 0, None, 0, 0, 1)
-        out = Act(o, fmt=1)
-    else:
-        d = N.ChainDesc()
-        d.t1, d.res, d.out = t1.ptr(), res.ptr(), out.ptr()
-        d.w3, d.ws3, d.b3 = N.ptr(pc3.w), N.ptr(pc3.wscale), N.ptr(pc3.bias)
-        d.n, d.h, d.w, d.c, d.cn, d.nout = t1.n, t1.h, t1.w, pc3.cin, 0, pc3.cout
-        d.t1_ld, d.res_ld, d.out_ld = t1.ld, res.ld, out.ld
-        N.check(N.lib().fcp_bottleneck_chain_f16x3(C.byref(d), N.stream_ptr()), "fcp_bottleneck_chain_f16x3")
-    flops = pc3.flops_per_pixel * m
-    if timing is not None or ConvStats.replay is not None:
-        relaunch = None
-        if not via_op:
-            keep = (pc3, t1, res, out)
-            relaunch = lambda d=d, keep=keep: N.check(N.lib().fcp_bottleneck_chain_f16x3(C.byref(d), N.stream_ptr()), "fcp_bottleneck_chain_f16x3")
-        ConvStats.note(timing, e0 if timing is not None else None, e1 if timing is not None else None, flops,
-                       f"expand {pc3.cin}->{pc3.cout} @{t1.h}x{t1.w} +res", 4 * (m * (pc3.cin + 2 * pc3.cout) + pc3.cin * pc3.cout), relaunch)
-    if ConvStats.enabled:
-        ConvStats.flops += flops
-        ConvStats.launches += 1
-    if RangeMonitor.active is not None:
-        _monitor(f"expand {pc3.cin}->{pc3.cout} @{t1.h}x{t1.w}", out)
-    return out, None
+    def relaunch(o, o1n):
+        o = _alias_safe_out(o, t1, res, t1b)
+        o1n = o1n if o1n is None else _alias_safe_out(o1n, t1, res, t1b)
+        return "fcp_bottleneck_chain_f16x3", (C.byref(desc(o, o1n)),), (pc2, pc3, pc1n, t1, res, o, o1n, t1b)
+    return _accounted(go, describe, relaunch)
 
 
 def u8_to_nhwc4(images_u8: torch.Tensor, sub=(0.0, 0.0, 0.0), div: float = 1.0) -> Act:
@@ -1003,35 +996,30 @@ def stem_relu_pool_u8(ps: PackedStem, images_u8: torch.Tensor, out: Act | None =
         out = Act.empty(n, hp, wp, 64, images_u8.device, out_fmt)
     assert (out.n, out.h, out.w, out.c) == (n, hp, wp, 64), "stem: bad output view"
     mean = (C.c_int32 * 3)(*[int(m) for m in mean_rgb])
-    timing = ConvStats.timing
-    if timing is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    flops = ps.flops_per_pixel * n * hs * ws
     if conv1 is not None:
         assert stem_conv1_supported(conv1) and out.fmt == 1, "stem + conv1: 1x1 64 -> 64 fp16x3 conv on a split32 pooled map"
         if t1 is None:
             t1 = Act.empty(n, hp, wp, 64, images_u8.device, 1)
         assert t1.fmt == 1 and (t1.n, t1.h, t1.w, t1.c) == (n, hp, wp, 64)
-        flops += conv1.flops_per_pixel * n * hp * wp
-        N.check(N.lib().fcp_stem7x7s2_relu_pool_conv1_u8(N.ptr(images_u8), n, h, w, mean, N.ptr(ps.wfrag), N.ptr(ps.bias),
-                                                         N.ptr(ps.wscale), out.ptr(), out.ld, out.fmt, N.ptr(conv1.w),
-                                                         N.ptr(conv1.wscale), N.ptr(conv1.bias), t1.ptr(), t1.ld, N.stream_ptr()),
-                "fcp_stem7x7s2_relu_pool_conv1_u8")
-    else:
-        N.check(N.lib().fcp_stem7x7s2_relu_pool_u8(N.ptr(images_u8), n, h, w, mean, N.ptr(ps.wfrag), N.ptr(ps.bias),
-                                                   N.ptr(ps.wscale), out.ptr(), out.ld, out.fmt, N.stream_ptr()),
-                "fcp_stem7x7s2_relu_pool_u8")
-    if timing is not None or ConvStats.replay is not None:
+
+    def args(o, o1):        # (C entry point, its arguments before the stream)
+        a = (N.ptr(images_u8), n, h, w, mean, N.ptr(ps.wfrag), N.ptr(ps.bias), N.ptr(ps.wscale), o.ptr(), o.ld, o.fmt)
+        if conv1 is None:
+            return "fcp_stem7x7s2_relu_pool_u8", a
+        return "fcp_stem7x7s2_relu_pool_conv1_u8", a + (N.ptr(conv1.w), N.ptr(conv1.wscale), N.ptr(conv1.bias), o1.ptr(), o1.ld)
+
+    def go():
+        fn, a = args(out, t1)
+        _c_launch(fn, *a)
+        return out, t1
+
+    def describe():
+        flops = ps.flops_per_pixel * n * hs * ws + (conv1.flops_per_pixel * n * hp * wp if conv1 is not None else 0)
         byts = n * h * w * 3 + 4 * n * hp * wp * 64 * (2 if conv1 is not None else 1)
-        ConvStats.note(timing, e0 if timing is not None else None, e1 if timing is not None else None, flops,
-                       f"stem 7x7 s2 + pool{' + conv1' if conv1 is not None else ''} @{hp}x{wp}", byts,
-                       lambda: stem_relu_pool_u8(ps, images_u8, out, mean_rgb, out_fmt, conv1, t1))   # (replayed with capture switched off)
-    if ConvStats.enabled:
-        ConvStats.flops += flops
-        ConvStats.launches += 1
-    if RangeMonitor.active is not None:
-        _monitor(f"stem 7x7 s2 + pool @{hp}x{wp}", out, t1)
+        return (f"stem 7x7 s2 + pool{' + conv1' if conv1 is not None else ''} @{hp}x{wp}", f"stem 7x7 s2 + pool @{hp}x{wp}",
+                flops, byts)
+    relaunch = lambda o, o1: (*args(o, o1), (ps, images_u8, o, conv1, o1))
+    _accounted(go, describe, relaunch)
     return out if conv1 is None else (out, t1)
 
 
@@ -1047,21 +1035,20 @@ def stem_relu_pool_f32(ps: PackedStem, x4: Act, out: Act | None = None, out_fmt:
     if out is None:
         out = Act.empty(n, hp, wp, 64, x4.buf.device, out_fmt)
     assert (out.n, out.h, out.w, out.c) == (n, hp, wp, 64), "stem: bad output view"
-    timing = ConvStats.timing
-    if timing is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    N.check(N.lib().fcp_stem7x7s2_relu_pool_f32(x4.ptr(), n, h, w, N.ptr(ps.wfrag), N.ptr(ps.bias), N.ptr(ps.wscale),
-                                                out.ptr(), out.ld, out.fmt, N.stream_ptr()), "fcp_stem7x7s2_relu_pool_f32")
-    flops = ps.flops_per_pixel * n * hs * ws
-    if timing is not None:
-        ConvStats.note(timing, e0, e1, flops, f"stem(f32) 7x7 s2 + pool @{hp}x{wp}", n * h * w * 16 + 4 * n * hp * wp * 64)
-    if ConvStats.enabled:
-        ConvStats.flops += flops
-        ConvStats.launches += 1
-    if RangeMonitor.active is not None:
-        _monitor(f"stem(f32) 7x7 s2 + pool @{hp}x{wp}", out)
-    return out
+    args = lambda o: (x4.ptr(), n, h, w, N.ptr(ps.wfrag), N.ptr(ps.bias), N.ptr(ps.wscale), o.ptr(), o.ld, o.fmt)
+
+    def go():
+        _c_launch("fcp_stem7x7s2_relu_pool_f32", *args(out))
+        return (out,)
+
+    def describe():
+        label = f"stem(f32) 7x7 s2 + pool @{hp}x{wp}"
+        return label, label, ps.flops_per_pixel * n * hs * ws, n * h * w * 16 + 4 * n * hp * wp * 64
+
+    def relaunch(o):
+        o = _alias_safe_out(o, x4)
+        return "fcp_stem7x7s2_relu_pool_f32", args(o), (ps, x4, o)
+    return _accounted(go, describe, relaunch)[0]
 
 
 def f32nchw_to_nhwc4(images: torch.Tensor, sub=(0.0, 0.0, 0.0), div: float = 1.0) -> Act:

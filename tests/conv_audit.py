@@ -228,7 +228,7 @@ def _clone_view(a):
 
 
 def _overlaps(t, out) -> bool:
-    """The overlap test ``engine.conv``'s autotuner applies: same storage and intersecting channel ranges."""
+    """The overlap test of ``engine._alias_safe_out`` (tuner trials, relaunches): same storage and intersecting channel ranges."""
     return (t is not None and t.buf.untyped_storage().data_ptr() == out.buf.untyped_storage().data_ptr()
             and t.c0 < out.c0 + out.c and out.c0 < t.c0 + t.c)
 
@@ -324,11 +324,12 @@ class Auditor:
             raise AuditError(f"{label} ({family}): max |kernel - float64 reference| = {err:.4g} > tol {tol:.4g} over {got.shape[0]} "
                              f"sampled pixels")
 
-    def _label(self, default):
+    def _label(self):
+        """The label the engine captured for the launch just audited (``ConvStats.replay`` was emptied before it)."""
         rep = self.E.ConvStats.replay
-        lab = rep[-1][0] if rep else default
+        assert len(rep) == 1, f"the engine captured {len(rep)} launches for one call"
         self.E.ConvStats.replay = []
-        return lab
+        return rep[0][0]
 
     def families(self):
         return {fam for _, fam, _, _ in self.rows}
@@ -359,7 +360,7 @@ class Auditor:
             E.ConvStats.replay = []
             out = orig["conv"](*args, **kw)
             torch.cuda.synchronize()
-            lab = self._label("conv")
+            lab = self._label()
             w, b = self._w(pc, out.buf.device)
             oh, ow = out.h, out.w
             mi = self._sample(out.n, oh, ow, out.buf.device)
@@ -376,12 +377,7 @@ class Auditor:
             E.ConvStats.replay = []
             out, t1n = orig["bottleneck_chain"](*args, **kw)
             torch.cuda.synchronize()
-            E.ConvStats.replay = []
-            # the label engine.bottleneck_chain notes, built here: the registered-op path (FCP_BOUNDARY=torch) notes none
-            even_only = a["out_even_only"] and pc2 is not None and pc1n is not None and E.RangeMonitor.active is None
-            lab = (f"expand {pc3.cin}->{pc3.cout} @{t1.h}x{t1.w} +res" if pc1n is None else
-                   f"chain {'3x3 ' if pc2 is not None else ''}{pc3.cin}->{pc3.cout}->{pc1n.cout} @{t1.h}x{t1.w}"
-                   f"{' +res' if res is not None else ''}{' out@even' if even_only else ''}{' two-source' if t1b is not None else ''}")
+            lab = self._label()
             fam = chain_family(lab)
             dev = out.buf.device
             W = {}
@@ -406,15 +402,15 @@ class Auditor:
         def stem_relu_pool_u8(*args, **kw):
             a = bound("stem_relu_pool_u8", args, kw)
             ps, images, conv1 = a["ps"], a["images_u8"], a["conv1"]
+            E.ConvStats.replay = []
             res = orig["stem_relu_pool_u8"](*args, **kw)
             torch.cuda.synchronize()
-            E.ConvStats.replay = [] if E.ConvStats.replay is not None else None
+            lab = self._label()
             out, t1 = (res, None) if conv1 is None else res
             dev = out.buf.device
             w, b = self._w(ps, dev)
             pi = self._sample(out.n, out.h, out.w, dev)
             ni, py, px = split_m(pi, out.h, out.w)
-            lab = f"stem 7x7 s2 + pool{' + conv1' if conv1 is not None else ''} @{out.h}x{out.w}"
             fam = "stem + conv1" if conv1 is not None else "stem"
             got = gather_act(out, ni, py, px)
             self._check(lab + " [pooled]", fam, got, ref_stem(w, b, images, pi, out.h, out.w, mean=a["mean_rgb"]))
@@ -426,12 +422,14 @@ class Auditor:
         def stem_relu_pool_f32(*args, **kw):
             a = bound("stem_relu_pool_f32", args, kw)
             ps, x4 = a["ps"], a["x4"]
+            E.ConvStats.replay = []
             out = orig["stem_relu_pool_f32"](*args, **kw)
             torch.cuda.synchronize()
+            lab = self._label()
             w, b = self._w(ps, out.buf.device)
             pi = self._sample(out.n, out.h, out.w, out.buf.device)
             got = gather_act(out, *split_m(pi, out.h, out.w))
-            self._check(f"stem(f32) 7x7 s2 + pool @{out.h}x{out.w}", "stem f32", got, ref_stem(w, b, x4.buf, pi, out.h, out.w))
+            self._check(lab, "stem f32", got, ref_stem(w, b, x4.buf, pi, out.h, out.w))
             return out
 
         def maxpool3x3s2(*args, **kw):

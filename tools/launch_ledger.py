@@ -8,7 +8,7 @@ and priced against two floors:  floor_hbm_us = algorithmic HBM bytes / 6.3 TB/s 
 floor_mfma_us = EXECUTED matrix FLOP (3 MFMAs per product on the fp16x3 path) / (2.5 PFLOP/s x mean sclk of its loop / 2400 MHz);
 floor_max = max of the two (perfect overlap), floor_sum = their sum (none: joules add at the socket power cap).
 
-    python tools/launch_ledger.py OUT.csv [batch size secs]          (GPU box; FCP_BOUNDARY=ctypes is forced)
+    python tools/launch_ledger.py OUT.csv [batch size secs]          (GPU box)
 
 A launch whose in-situ time is <= 1.15 x floor_sum is physics on this socket; above that it is a kernel problem."""
 import csv
@@ -16,7 +16,6 @@ import os
 import sys
 import time
 
-os.environ["FCP_BOUNDARY"] = "ctypes"            # the replay closures re-enqueue C-ABI descriptors
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
