@@ -44,6 +44,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-ip", "--interpolation", type=str, default=argparse.SUPPRESS, choices=("linear", "cubic", "lanczos4"),
                    help="filter of the crop warp: cv2 INTER_LINEAR (default 'linear', the reference's), INTER_CUBIC "
                         "('cubic') or INTER_LANCZOS4 ('lanczos4')")
+    p.add_argument("-ms", "--min_sharpness", "--min-sharpness", type=float, default=argparse.SUPPRESS,
+                   help="drop crops whose variance of the Laplacian (cv2.Laplacian(gray, cv2.CV_64F).var()) is below this "
+                        "value; by default nothing is scored or dropped")
     return p
 
 

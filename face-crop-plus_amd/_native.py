@@ -87,6 +87,7 @@ SIGNATURES = {
     "fcp_warp_affine_u8_interp": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "fcp_warp_affine_u8_interp_ragged": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "fcp_warp_interp_weights": [_I, _P],
+    "fcp_crop_sharpness_u8": [_P, _I, _I, _I, _P, _P, _P],
 }
 EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes"] + list(SIGNATURES)
 

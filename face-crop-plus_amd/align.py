@@ -186,6 +186,34 @@ def crop_align(images_u8, img_idx, landmarks, target, output_size, border=0, all
     return crops, ok, mat
 
 
+# ------------------------------------------------------------------ sharpness (Cropper(min_sharpness=...))
+# Variance of the Laplacian of the crops' gray image, cv2.Laplacian(cv2.cvtColor(crop, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var(),
+# from exact integer sums: the device adds, the host divides once.
+
+def sharpness_sums(crops_dev: torch.Tensor, ok: torch.Tensor | None = None) -> torch.Tensor:
+    """crops (F,H,W,3) u8 device -> (F,2) int64 device: S1 = sum L and S2 = sum L*L of every crop's Laplacian L (gray
+    ``(9798 R + 19235 G + 3735 B + 16384) >> 15``, 4-neighbour kernel, BORDER_REFLECT_101).  Crops with ``ok == 0`` are
+    skipped, their sums are 0.  One launch; W <= 8192."""
+    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
+    if T.ENABLED:
+        return T.load().crop_sharpness(crops_dev, ok)
+    f, h, w, _ = crops_dev.shape
+    sums = torch.empty((f, 2), dtype=torch.int64, device=crops_dev.device)
+    N.check(N.lib().fcp_crop_sharpness_u8(N.ptr(crops_dev), f, h, w, N.ptr(ok), N.ptr(sums), N.stream_ptr()),
+            "fcp_crop_sharpness_u8")
+    return sums
+
+
+def sharpness_score(sums, n_pixels: int) -> np.ndarray:
+    """(F,2) sums of ``sharpness_sums`` (a host array, or a device tensor, read back once) and N = H*W -> (F,) float64
+    population variance ``(N*S2 - S1*S1) / (N*N)``: the numerator in Python integers (it passes 2^63 beyond 1024^2
+    crops), then one correctly rounded division, so the score does not depend on any summation order."""
+    if isinstance(sums, torch.Tensor):
+        sums = sums.cpu().numpy()
+    n = int(n_pixels)
+    return np.array([(n * int(s2) - int(s1) * int(s1)) / (n * n) for s1, s2 in np.asarray(sums).reshape(-1, 2)], np.float64)
+
+
 # ------------------------------------------------------------------ crop_source="original"
 # Crops sampled from the decoded files instead of the resized batch.  A face whose crop would minify the file by 2 or more
 # is sampled from a power-of-two INTER_AREA level of it instead (cv2.resize(O, (w >> L, h >> L), INTER_AREA)), so that the

@@ -53,6 +53,7 @@ class Cropper:
         warp_family: str | None = None,
         crop_source: str = "batch",
         interpolation: str = "linear",
+        min_sharpness: float | None = None,
     ):
         """Arguments as in the reference (cropper.py:139-156).  ``device`` must be a GPU
         (``"cuda:N"``); ``weights`` optionally maps "retinaface"/"rrdb"/"bisenet" to a
@@ -68,7 +69,13 @@ class Cropper:
         ``interpolation``: the filter of the crop warp — "linear" (cv2.INTER_LINEAR, the reference's), "cubic"
         (INTER_CUBIC) or "lanczos4" (INTER_LANCZOS4), OpenCV's fixed-point warps, on every crop path.  Cubic and Lanczos-4
         have no float32 family: combining them with an explicit ``warp_family="float32"`` (or ``$FCP_WARP_FAMILY``)
-        raises ValueError."""
+        raises ValueError.
+        ``min_sharpness``: drop blurry crops — a face is kept when the variance of the Laplacian of its crop,
+        ``cv2.Laplacian(cv2.cvtColor(crop, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var()`` computed exactly on the device
+        (``align.sharpness_sums`` / ``sharpness_score``), is at least this value; dropped faces are neither parsed nor
+        written.  None (the default) scores nothing.  It needs aligned crops, so it cannot be combined with "no alignment"
+        (``det_threshold=None`` and ``landmarks=None``); useful values depend on ``output_size`` and the content:
+        calibrate with ``Cropper.sharpness``."""
         explicit_family = warp_family if warp_family is not None else (os.environ.get("FCP_WARP_FAMILY") or None)
         align.check_interpolation(interpolation, explicit_family)
         if crop_source not in ("batch", "original"):
@@ -76,6 +83,16 @@ class Cropper:
         if crop_source == "original" and enh_threshold is not None:
             raise ValueError("crop_source='original' cannot be combined with enh_threshold: the enhancer works on the "
                              "resized batch, which this mode does not sample")
+        if min_sharpness is not None:
+            if isinstance(min_sharpness, bool) or not isinstance(min_sharpness, (int, float, np.integer, np.floating)):
+                raise ValueError(f"min_sharpness must be a number or None, not {min_sharpness!r}")
+            if not np.isfinite(min_sharpness) or min_sharpness < 0:
+                raise ValueError(f"min_sharpness must be finite and >= 0 (a variance), not {min_sharpness!r}")
+            if det_threshold is None and landmarks is None:
+                raise ValueError("min_sharpness needs aligned crops: it cannot be combined with det_threshold=None and "
+                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            min_sharpness = float(min_sharpness)
+        self.min_sharpness = min_sharpness
         self.crop_source = crop_source
         self.interpolation = interpolation
         self.output_size = output_size
@@ -213,6 +230,18 @@ class Cropper:
                         res[li] = c
             outs = [res[li] for li in sorted(res)]
         return np.stack(outs) if len(outs) > 0 else np.array(outs)
+
+    def sharpness(self, crops: np.ndarray) -> np.ndarray:
+        """The score ``min_sharpness`` is compared with, for crops one already has: (F,H,W,3) uint8 RGB -> (F,) float64
+        variance of the Laplacian (``align.sharpness_score``)."""
+        crops = np.ascontiguousarray(crops)
+        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
+            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
+        if crops.shape[0] == 0:
+            return np.zeros(0, np.float64)
+        with torch.cuda.device(self.device):
+            sums = align.sharpness_sums(torch.from_numpy(crops).to(self.device))
+            return align.sharpness_score(sums, crops.shape[1] * crops.shape[2])
 
     # ----------------------------------------------------------------- saving
     MAX_PENDING_WRITES = 256     # encode / write tasks in flight before a GPU worker waits (process_dir)
@@ -393,6 +422,14 @@ class Cropper:
                 # decode worker's shared-memory ring, which is recycled as soon as this call returns, while the encode
                 # tasks run later: they get their own copies
                 faces, faces_dev = ([np.array(im) for im in images] if pinned is not None else images), None
+            if self.min_sharpness is not None and landmarks is not None and len(faces) > 0:
+                with trace.range("fcp:sharpness"):
+                    if faces_dev is None:
+                        faces_dev = torch.from_numpy(np.ascontiguousarray(faces)).to(self.device)
+                    score = align.sharpness_score(align.sharpness_sums(faces_dev), faces_dev.shape[1] * faces_dev.shape[2])
+                keep = score >= self.min_sharpness
+                faces, faces_dev = faces[keep], faces_dev[torch.from_numpy(keep).to(self.device)]
+                indices = [i for i, k in zip(indices, keep) if k]
             if self.par_model is not None and len(faces) > 0:
                 if faces_dev is None:
                     faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]

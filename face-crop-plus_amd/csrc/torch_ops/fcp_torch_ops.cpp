@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -15,6 +15,7 @@
 #include <c10/core/DeviceGuard.h>
 #include <torch/library.h>
 
+#include <climits>
 #include <tuple>
 
 #include "fcp_hip.h"
@@ -371,6 +372,21 @@ void resize_area_u8_ragged(const Tensor& src, const Tensor& levels, const Tensor
      "fcp::resize_area_u8_ragged");
 }
 
+// Laplacian-variance sums of crops (f,h,w,3) uint8: (f,2) int64 {S1, S2} (fcp_crop_sharpness_u8; the host divides).
+Tensor crop_sharpness(const Tensor& crops, const c10::optional<Tensor>& okf) {
+  dev(crops, "crops", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
+  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
+  TORCH_CHECK(!okf.has_value() || !okf->defined() || okf->numel() == f, "ok must hold ", f, " flags");
+  Tensor sums = at::empty({f, 2}, crops.options().dtype(at::kLong));
+  ok(fcp_crop_sharpness_u8(crops.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, optp<int>(okf, "ok", at::kInt),
+                           sums.data_ptr<int64_t>(), cur_stream()),
+     "fcp::crop_sharpness");
+  return sums;
+}
+
 Tensor bicubic_down4_round(const Tensor& x4) {
   dev(x4, "x4", at::kFloat);
   FCP_DEVICE_GUARD(x4);
@@ -429,6 +445,7 @@ TORCH_LIBRARY(fcp, m) {
   m.def("warp_affine_u8_interp_ragged(Tensor blob, Tensor srcs, Tensor mat, Tensor? ok, int out_w, int out_h, int border, "
         "int interp) -> Tensor");
   m.def("resize_area_u8_ragged(Tensor src, Tensor levels, Tensor(a!) dst) -> ()");
+  m.def("crop_sharpness(Tensor crops, Tensor? ok) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -452,6 +469,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("warp_affine_u8_interp", &warp_affine_u8_interp);
   m.impl("warp_affine_u8_interp_ragged", &warp_affine_u8_interp_ragged);
   m.impl("resize_area_u8_ragged", &resize_area_u8_ragged);
+  m.impl("crop_sharpness", &crop_sharpness);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

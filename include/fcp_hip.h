@@ -406,6 +406,19 @@ int fcp_warp_affine_u8_interp_ragged(const uint8_t* blob, int64_t blob_bytes,
  * interp 2, 8 for interp 4. */
 int fcp_warp_interp_weights(int interp, int16_t* out);
 
+/* Sharpness of crops (f,h,w,3) uint8 RGB: the integer sums behind
+ * cv2.Laplacian(cv2.cvtColor(crop, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var()
+ * (INTEGRATION.md 2e).  g = (9798 R + 19235 G + 3735 B + 16384) >> 15;
+ * L = g(y-1,x) + g(y+1,x) + g(y,x-1) + g(y,x+1) - 4 g(y,x) with
+ * BORDER_REFLECT_101 (a dimension of size 1 maps every neighbour to index 0);
+ * sums[i] = {S1 = sum L, S2 = sum L*L} over crop i, exact.  The variance is
+ * (N S2 - S1^2) / N^2 with N = h*w, left to the host.  sums (f,2) is zeroed on
+ * the stream first; crops with ok[i] == 0 are skipped (their sums stay 0), ok
+ * may be NULL.  One launch.  f == 0 is a no-op; h < 1, w < 1, w > 8192,
+ * h > 1048576 or f > 65535 fail with a message. */
+int fcp_crop_sharpness_u8(const uint8_t* crops, int f, int h, int w, const int32_t* ok,
+                          int64_t* sums, fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */

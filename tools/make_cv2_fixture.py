@@ -7,16 +7,19 @@ kernels to them.
 
     pip install opencv-python torchvision          # anywhere with a network
     python tools/make_cv2_fixture.py                # writes tests/golden/opencv_align.npz, opencv_batch.npz,
-                                                    #        opencv_interp.npz, tests/golden/torchvision_resnet50.npz
+                                                    #        opencv_interp.npz, opencv_sharpness.npz,
+                                                    #        tests/golden/torchvision_resnet50.npz
     python -m pytest tests/test_third_party_pins.py            # oracle vs the pins (CPU)
     python -m pytest tests/test_third_party_pins.py -m gpu     # kernels vs the pins (MI355X)
     python -m pytest tests/test_warp_interp_pins.py            # cubic / Lanczos-4 restatement (and, -m gpu, kernels)
+    python -m pytest tests/test_sharpness_pins.py              # RGB2GRAY + Laplacian restatement (and, -m gpu, the kernel)
 
 Everything is called exactly the way the reference calls it:
   cropper.py:515-527   cv2.estimateAffinePartial2D / estimateAffine2D(src, dst, ransacReprojThreshold=np.inf)[0]
   cropper.py:542-547   cv2.warpAffine(image, M, dsize, borderMode=cv2.BORDER_*)          (flags default INTER_LINEAR)
                        and the same call with flags=INTER_CUBIC / INTER_LANCZOS4 (Cropper(interpolation=...))
   utils.py:320-335     cv2.resize(image, (ww, hh), interpolation=INTER_AREA | INTER_CUBIC) + cv2.copyMakeBorder
+  (not in the reference) cv2.Laplacian(cv2.cvtColor(crop, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var()   (Cropper(min_sharpness=...))
   retinaface.py:93-99  torchvision.models.resnet50() + _utils.IntermediateLayerGetter(layer2, layer3, layer4)
 Only data is stored (inputs, outputs, library versions): no third-party source.
 """
@@ -186,6 +189,30 @@ def make_interp(cv2):
     print("wrote opencv_interp.npz")
 
 
+def make_sharpness(cv2):
+    """cv2.Laplacian(cv2.cvtColor(crop, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var() on seeded 8UC3 crops for
+    tests/test_sharpness_pins.py: noise, photo-like content, a 0/255 checkerboard, the eight corners of the RGB cube (and
+    every single-channel ramp: the rounding of each gray coefficient), sizes with a dimension of 1 and odd sizes."""
+    rng = np.random.default_rng(600)
+    out = describe_cv2(cv2)
+    yy, xx = np.mgrid[0:32, 0:32]
+    ramps = np.zeros((3 * 8, 32, 3), np.uint8)                             # channel c takes every value 0..255, the others 0
+    for c in range(3):
+        ramps[8 * c:8 * c + 8, :, c] = np.arange(256, dtype=np.uint8).reshape(8, 32)
+    crops = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in ((1, 1), (1, 7), (5, 1), (2, 2), (17, 23), (64, 48))]
+    crops += [photo_like(96, 80, 601), photo_like(57, 131, 602),
+              np.repeat((((yy + xx) & 1) * 255).astype(np.uint8)[..., None], 3, -1),
+              np.array([[[r, g, b] for g in (0, 255) for b in (0, 255)] for r in (0, 255)], np.uint8), ramps]
+    for k, crop in enumerate(crops):
+        g = cv2.cvtColor(crop, cv2.COLOR_RGB2GRAY)
+        lap = cv2.Laplacian(g, cv2.CV_64F)
+        out[f"sharp{k}_crop"], out[f"sharp{k}_gray"], out[f"sharp{k}_laplacian"] = crop, g, lap
+        out[f"sharp{k}_var"] = np.array(lap.var())
+    out["sharp_cases"] = np.array(len(crops))
+    np.savez_compressed(os.path.join(GOLDEN, "opencv_sharpness.npz"), **out)
+    print("wrote opencv_sharpness.npz")
+
+
 def make_resnet():
     """retinaface.py:93-99 with the build's generated `body.*` weights: the three feature maps torchvision's own
     ResNet-50 + IntermediateLayerGetter return for one seeded 96x128 input."""
@@ -222,6 +249,7 @@ def main():
             make_align(cv2)
             make_batch(cv2)
             make_interp(cv2)
+            make_sharpness(cv2)
     if args.only != "cv2":
         try:
             import torchvision  # noqa: F401
