@@ -637,6 +637,7 @@ extern "C" int fcp_warp_affine_u8(const uint8_t* images, int n, int h, int w, co
   FCP_REQUIRE(n > 0 && h > 0 && w > 0 && f > 0 && out_h > 0 && out_w > 0, "warp_affine: bad sizes");
   FCP_REQUIRE(border >= 0 && border <= 4, "warp_affine: unsupported border mode %d", border);
   FCP_REQUIRE(f <= 65535, "warp_affine: at most 65535 faces per call");
+  FCP_REQUIRE(h <= 32767 && w <= 32767, "warp_affine: images of %dx%d (at most 32767 px a side: source coordinates saturate to short)", w, h);
   return launch_fixed(BatchSource{images, n, h, w, img_idx, paddings}, mat, ok, f, out_h, out_w, border, out, stream);
 }
 
@@ -647,6 +648,7 @@ extern "C" int fcp_warp_affine_u8_float(const uint8_t* images, int n, int h, int
   FCP_REQUIRE(n > 0 && h > 0 && w > 0 && f > 0 && out_h > 0 && out_w > 0, "warp_affine_float: bad sizes");
   FCP_REQUIRE(border >= 0 && border <= 4, "warp_affine_float: unsupported border mode %d", border);
   FCP_REQUIRE(f <= 65535, "warp_affine_float: at most 65535 faces per call");
+  FCP_REQUIRE(h <= 32767 && w <= 32767, "warp_affine_float: images of %dx%d (at most 32767 px a side: source coordinates saturate to short)", w, h);
   return launch_float(BatchSource{images, n, h, w, img_idx, paddings}, mat, ok, f, out_h, out_w, border, out, stream);
 }
 
@@ -676,6 +678,7 @@ extern "C" int fcp_warp_affine_u8_interp(const uint8_t* images, int n, int h, in
   FCP_REQUIRE(fcp_interp::taps_of(interp) != 0, "warp_affine_interp: unsupported interpolation %d (2 cubic, 4 lanczos4)",
               interp);
   FCP_REQUIRE(f <= 65535, "warp_affine_interp: at most 65535 faces per call");
+  FCP_REQUIRE(h <= 32767 && w <= 32767, "warp_affine_interp: images of %dx%d (at most 32767 px a side: source coordinates saturate to short)", w, h);
   return launch_interp(BatchSource{images, n, h, w, img_idx, paddings}, interp, mat, ok, f, out_h, out_w, border, out, stream);
 }
 

@@ -337,7 +337,16 @@ int fcp_estimate_transform_counted(const float* src, const float* dst, int f, in
  * fixed-point algorithm (AB_BITS=10, INTER_BITS=5, 15-bit weights).
  * images (n,h,w,3) u8; img_idx (f) int32; mat (f,6) f64 forward transforms;
  * paddings (n,4) int32 (t,b,l,r) or NULL; border: 0 constant(0), 1 replicate,
- * 2 reflect, 3 wrap, 4 reflect_101 (= cv2.BORDER_*); out (f,out_h,out_w,3) u8. */
+ * 2 reflect, 3 wrap, 4 reflect_101 (= cv2.BORDER_*); out (f,out_h,out_w,3) u8.
+ * h and w are at most 32767 (source coordinates saturate to short, as in
+ * cv::warpAffine); larger batches fail with a message, like the ragged entry
+ * points below.  `images` (`blob` for the ragged entry points) and `out` are
+ * expected 4-byte aligned: the interior taps are read and whole groups of four
+ * output pixels are written as aligned dwords.  This holds for every warp below.
+ * A matrix with ok == NULL (or ok = 1) is used as it is: a singular one inverts
+ * to all zeros, and in this family and the cubic / Lanczos-4 warps a non-finite
+ * coefficient goes through cvRound (INT_MIN) and int32 wrap-around exactly as in
+ * cv::warpAffine, so the result is defined. */
 int fcp_warp_affine_u8(const uint8_t* images, int n, int h, int w,
                        const int32_t* img_idx, const double* mat, const int32_t* ok,
                        const int32_t* paddings, int f, int out_h, int out_w, int border,
@@ -354,7 +363,10 @@ int fcp_warp_affine_u8(const uint8_t* images, int n, int h, int w,
  *   [-32768, 32767] in float, then converted: they select the taps and the
  *   all-outside test of the constant border (a constant-border tap reads 0);
  *   v0 = p00 + ax*(p01 - p00), v1 = p10 + ax*(p11 - p10), v = v0 + ay*(v1 - v0);
- *   out = round-half-even(v) saturated to 0..255. */
+ *   out = round-half-even(v) saturated to 0..255.
+ * The result of this family is unspecified for a matrix with a non-finite
+ * coefficient (float-to-int conversion of NaN); the pipeline never passes one
+ * with ok = 1, fcp_estimate_transform clears ok for such a face. */
 int fcp_warp_affine_u8_float(const uint8_t* images, int n, int h, int w,
                              const int32_t* img_idx, const double* mat, const int32_t* ok,
                              const int32_t* paddings, int f, int out_h, int out_w, int border,
