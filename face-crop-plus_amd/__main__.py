@@ -47,6 +47,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-ms", "--min_sharpness", "--min-sharpness", type=float, default=argparse.SUPPRESS,
                    help="drop crops whose variance of the Laplacian (cv2.Laplacian(gray, cv2.CV_64F).var()) is below this "
                         "value; by default nothing is scored or dropped")
+    p.add_argument("-enc", "--encoder", type=str, default=argparse.SUPPRESS, choices=("host", "device"),
+                   help="where output files are compressed: 'host' (default, Pillow on the I/O pool) or 'device' (JPEG "
+                        "files of aligned crops and masks are encoded on the GPU, byte for byte the same files)")
     return p
 
 

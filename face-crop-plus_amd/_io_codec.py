@@ -70,3 +70,17 @@ def write_image(path: str, image: np.ndarray) -> bool:
         if os.path.exists(tmp):
             os.remove(tmp)
     return True
+
+
+def write_bytes(path: str, data) -> bool:
+    """An already encoded file (``Cropper(encoder="device")``: header + the stream the GPU wrote) -> disk, through a
+    temporary name so that a failed write never leaves a truncated image behind."""
+    tmp = f"{path}.part{os.getpid()}"
+    try:
+        with open(tmp, "wb") as fh:
+            fh.write(data)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return True

@@ -38,7 +38,7 @@ RING_MB = int(os.environ.get("FCP_IO_RING_MB", "128"))
 
 def _serve(conn, ring, ring_bytes: int, ctl, slot: int):
     """Worker process: serve requests until the socket closes."""
-    from ._io_codec import read_image, write_image
+    from ._io_codec import read_image, write_bytes, write_image
     consumed = np.frombuffer(ctl, dtype=np.int64)          # consumed[slot]: bytes the parent has given back (monotonic)
     produced = 0                                            # bytes handed out so far, incl. skipped ring tails (monotonic)
     while True:
@@ -79,6 +79,9 @@ def _serve(conn, ring, ring_bytes: int, ctl, slot: int):
                     _, path, shape = msg
                     pixels = np.frombuffer(conn.recv_bytes(), dtype=np.uint8).reshape(shape)
                     ok = write_image(path, pixels)
+                    conn.send(("done", bool(ok), [str(w.message) for w in caught]))
+                elif kind == "bytes":                       # a file encoded elsewhere (on the GPU): only written here
+                    ok = write_bytes(msg[1], conn.recv_bytes())
                     conn.send(("done", bool(ok), [str(w.message) for w in caught]))
                 else:
                     conn.send(("error", f"unknown request {kind!r}"))
@@ -199,6 +202,14 @@ class _Worker:
             warnings.warn(note)
         return rep[1]
 
+    def write_bytes(self, path, data) -> bool:
+        self._io(self.conn.send, ("bytes", path))
+        self._io(self.conn.send_bytes, data)
+        rep = self._reply()
+        for note in rep[2]:
+            warnings.warn(note)
+        return rep[1]
+
     def close(self):
         try:
             self.conn.send(None)
@@ -293,6 +304,9 @@ class IOProcesses:
 
     def write(self, path, pixels):
         return self._mine("w", self._free_w).write(path, pixels)
+
+    def write_bytes(self, path, data):
+        return self._mine("w", self._free_w).write_bytes(path, data)
 
     @staticmethod
     def pinned_flags(tokens):

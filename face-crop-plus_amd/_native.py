@@ -88,8 +88,9 @@ SIGNATURES = {
     "fcp_warp_affine_u8_interp_ragged": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "fcp_warp_interp_weights": [_I, _P],
     "fcp_crop_sharpness_u8": [_P, _I, _I, _I, _P, _P, _P],
+    "fcp_jpeg_encode_u8": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _P, _P, _L, _P],
 }
-EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes"] + list(SIGNATURES)
+EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes", "fcp_jpeg_workspace_bytes"] + list(SIGNATURES)
 
 
 def lib():
@@ -108,6 +109,8 @@ def lib():
         raise RuntimeError(f"libfcp_hip.so ABI {l.fcp_abi_version()} != expected {ABI_VERSION}; rebuild")
     l.fcp_retina_nms_workspace_bytes.argtypes = [C.c_int, C.c_int]
     l.fcp_retina_nms_workspace_bytes.restype = C.c_int64
+    l.fcp_jpeg_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    l.fcp_jpeg_workspace_bytes.restype = C.c_int64
     for name, args in SIGNATURES.items():
         fn = getattr(l, name)
         fn.argtypes = args

@@ -256,7 +256,8 @@ class BiSeNet:
                 m = torch.empty_like(sel)
                 N.check(N.lib().fcp_label_mask_u8(N.ptr(sel), sel.numel(), bits, N.ptr(m), N.stream_ptr()),
                         "fcp_label_mask_u8")
-                masks = m.cpu().numpy()
+                # Cropper(encoder="device") encodes the masks where they are; everyone else gets them on the host
+                masks = m if getattr(self, "masks_on_device", False) else m.cpu().numpy()
             out[k] = (inds, masks)
         return out
 

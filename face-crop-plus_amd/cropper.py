@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import align, trace
+from ._io_codec import write_bytes
 from .batch import batch_geometry, build_batch, upload_sources
 from .utils import get_ldm_slices, parse_landmarks_file, read_image, read_images, write_image
 
@@ -52,6 +53,7 @@ class Cropper:
         precision: str | None = None,
         warp_family: str | None = None,
         crop_source: str = "batch",
+        encoder: str = "host",
         interpolation: str = "linear",
         min_sharpness: float | None = None,
     ):
@@ -75,7 +77,15 @@ class Cropper:
         (``align.sharpness_sums`` / ``sharpness_score``), is at least this value; dropped faces are neither parsed nor
         written.  None (the default) scores nothing.  It needs aligned crops, so it cannot be combined with "no alignment"
         (``det_threshold=None`` and ``landmarks=None``); useful values depend on ``output_size`` and the content:
-        calibrate with ``Cropper.sharpness``."""
+        calibrate with ``Cropper.sharpness``.
+        ``encoder``: "host" (the default) compresses every output file with Pillow on the I/O pool; "device" compresses
+        the JPEG files (.jpg / .jpeg / .jpe) of aligned crops and parse masks on the GPU (``jpegenc.encode_jpeg``) — the
+        same files byte for byte — so that the lengths and the compressed streams come back instead of the pixels and the
+        I/O pool only writes.  Every other file (other formats, the images of "no alignment", a crop whose stream
+        outgrows its slot) is encoded on the host as before."""
+        if encoder not in ("host", "device"):
+            raise ValueError(f"unknown encoder {encoder!r}: choose 'host' or 'device'")
+        self.encoder = encoder
         explicit_family = warp_family if warp_family is not None else (os.environ.get("FCP_WARP_FAMILY") or None)
         align.check_interpolation(interpolation, explicit_family)
         if crop_source not in ("batch", "original"):
@@ -178,6 +188,7 @@ class Cropper:
             from .bise import BiSeNet
             self.par_model = BiSeNet(self.attr_groups, self.mask_groups, self.batch_size)
             self.par_model.load(self.device, self.weights.get("bisenet"), self.precision)
+            self.par_model.masks_on_device = self.encoder == "device"
 
     def _init_landmarks_target(self):
         if self.num_std_landmarks != 5:
@@ -243,6 +254,18 @@ class Cropper:
             sums = align.sharpness_sums(torch.from_numpy(crops).to(self.device))
             return align.sharpness_score(sums, crops.shape[1] * crops.shape[2])
 
+    def encode_jpeg(self, crops: np.ndarray) -> list:
+        """What ``encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F JPEG files as
+        bytes, each equal to the file the host encoder writes for those pixels (``jpegenc.encode_jpeg``)."""
+        from . import jpegenc
+        crops = np.ascontiguousarray(crops)
+        if crops.dtype != np.uint8 or not (crops.ndim == 3 or (crops.ndim == 4 and crops.shape[3] == 3)):
+            raise ValueError(f"crops must be (F,H,W,3) or (F,H,W) uint8, not {crops.dtype} {crops.shape}")
+        if crops.shape[0] == 0:
+            return []
+        with torch.cuda.device(self.device):
+            return jpegenc.encode_jpeg(torch.from_numpy(crops).to(self.device))
+
     # ----------------------------------------------------------------- saving
     MAX_PENDING_WRITES = 256     # encode / write tasks in flight before a GPU worker waits (process_dir)
 
@@ -262,14 +285,16 @@ class Cropper:
             paths.append(os.path.join(output_dir, stem + ext))
         return paths
 
-    def _emit(self, path: str, pixels: np.ndarray):
-        """Write one file: inline, or — inside process_dir — as a task on the I/O pool.  At most
+    def _emit(self, path: str, pixels):
+        """Write one file — pixels to encode, or the bytes of a file the GPU has encoded — inline, or — inside
+        process_dir — as a task on the I/O pool.  At most
         MAX_PENDING_WRITES tasks are in flight: a slow disk stalls the GPU worker here instead of piling uint8
         crops up in host memory, and a failed write surfaces at the next batch, not at the end of the run."""
         # Locals: process_dir resets the attributes when it unwinds, while tasks of a failed run may still be in flight.
         writer, writes, slots = getattr(self, "_io", None) or (None, None, None)      # ONE read: never a torn triple
+        encoded = isinstance(pixels, bytes)
         if writer is None:
-            write_image(path, pixels)
+            write_bytes(path, pixels) if encoded else write_image(path, pixels)
             return
         slots.acquire()
         procs = getattr(self, "_io_procs_active", None)       # encode in the thread's worker process, or on the thread
@@ -277,9 +302,9 @@ class Cropper:
         def task():
             try:
                 if procs is not None:
-                    procs.write(path, pixels)
+                    procs.write_bytes(path, pixels) if encoded else procs.write(path, pixels)
                 else:
-                    write_image(path, pixels)
+                    write_bytes(path, pixels) if encoded else write_image(path, pixels)
             finally:
                 slots.release()
         with self._write_lock:
@@ -300,7 +325,7 @@ class Cropper:
             return
         os.makedirs(output_dir, exist_ok=True)
         for path, pixels in zip(self._target_paths(file_names, output_dir), faces):
-            self._emit(path, np.asarray(pixels))
+            self._emit(path, pixels if isinstance(pixels, bytes) else np.asarray(pixels))
 
     def save_groups(self, faces, file_names, output_dir, attr_groups, mask_groups):
         """Directory tree ``output_dir/<attr group>/<mask group>[_mask]`` — reference ``save_groups``,
@@ -320,7 +345,32 @@ class Cropper:
                 row_of = {}
                 for row, face in enumerate(in_mask):
                     row_of.setdefault(face, row)
-                self.save_group(mask_rows[[row_of[i] for i in cell]], sources, cell_dir + "_mask")
+                self.save_group([mask_rows[row_of[i]] for i in cell], sources, cell_dir + "_mask")
+
+    def _is_jpeg_target(self, file_names):
+        """Per source file name: whether the face cut from it is written as a JPEG (``_target_paths``' extension rule)."""
+        from .jpegenc import JPEG_EXTENSIONS
+        if self.output_format is not None:
+            return np.full(len(file_names), ("." + self.output_format).lower() in JPEG_EXTENSIONS)
+        return np.array([os.path.splitext(str(n))[1].lower() in JPEG_EXTENSIONS for n in file_names], bool)
+
+    def _encode_on_device(self, pixels_dev, pixels, names):
+        """``encoder="device"``: (F,H,W[,3]) u8 device pixels (and their host copy, if one exists already) of the faces
+        or masks cut from ``names`` -> a list with the JPEG file (bytes) of every face that becomes one and the host
+        pixels of every other.  The pixels are read back only when some target is not a JPEG."""
+        from . import jpegenc
+        jpeg = self._is_jpeg_target(names)
+        out = [None] * len(names)
+        if jpeg.any():
+            with trace.range("fcp:jpeg"):
+                rows = pixels_dev if jpeg.all() else pixels_dev[torch.from_numpy(jpeg).to(pixels_dev.device)].contiguous()
+                for i, data in zip(np.nonzero(jpeg)[0], jpegenc.encode_jpeg(rows)):
+                    out[i] = data
+        if not jpeg.all():
+            host = pixels if pixels is not None else pixels_dev.cpu().numpy()
+            for i in np.nonzero(~jpeg)[0]:
+                out[i] = host[i]
+        return out
 
     # ------------------------------------------------------------- processing
     def _landmark_rows(self, table_names):
@@ -403,7 +453,8 @@ class Cropper:
                     keep = ok.cpu().numpy() != 0
                     crops_dev = crops_dev[torch.from_numpy(keep).to(self.device)]
                     indices = [i for i, k in zip(indices, keep) if k]
-                    faces_dev, faces = crops_dev, crops_dev.cpu().numpy()
+                    # encoder="device": the pixels stay where they are; what is read back is decided when they are saved
+                    faces_dev, faces = crops_dev, (None if self.encoder == "device" else crops_dev.cpu().numpy())
                 elif images_dev is not None:
                     with trace.range("fcp:align"):
                         crops_dev, ok = self._crop_align_device(
@@ -412,7 +463,8 @@ class Cropper:
                     keep = ok.cpu().numpy() != 0
                     crops_dev = crops_dev[torch.from_numpy(keep).to(self.device)]
                     indices = [i for i, k in zip(indices, keep) if k]
-                    faces_dev, faces = crops_dev, crops_dev.cpu().numpy()
+                    # encoder="device": the pixels stay where they are; what is read back is decided when they are saved
+                    faces_dev, faces = crops_dev, (None if self.encoder == "device" else crops_dev.cpu().numpy())
                 else:
                     with trace.range("fcp:align"):
                         faces = self.crop_align(images, paddings, indices, landmarks)
@@ -422,19 +474,30 @@ class Cropper:
                 # decode worker's shared-memory ring, which is recycled as soon as this call returns, while the encode
                 # tasks run later: they get their own copies
                 faces, faces_dev = ([np.array(im) for im in images] if pinned is not None else images), None
-            if self.min_sharpness is not None and landmarks is not None and len(faces) > 0:
+            if self.min_sharpness is not None and landmarks is not None and len(indices) > 0:
                 with trace.range("fcp:sharpness"):
                     if faces_dev is None:
                         faces_dev = torch.from_numpy(np.ascontiguousarray(faces)).to(self.device)
                     score = align.sharpness_score(align.sharpness_sums(faces_dev), faces_dev.shape[1] * faces_dev.shape[2])
                 keep = score >= self.min_sharpness
-                faces, faces_dev = faces[keep], faces_dev[torch.from_numpy(keep).to(self.device)]
+                faces, faces_dev = (None if faces is None else faces[keep]), faces_dev[torch.from_numpy(keep).to(self.device)]
                 indices = [i for i, k in zip(indices, keep) if k]
-            if self.par_model is not None and len(faces) > 0:
+            if self.par_model is not None and len(indices) > 0:
                 if faces_dev is None:
                     faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]
                 with trace.range("fcp:parse"):
                     groups = self.par_model.predict(faces_dev)
+            if self.encoder == "device" and isinstance(faces_dev, torch.Tensor):
+                # aligned crops (and their masks): same size, on the device.  Faces and mask rows become lists that hold
+                # the encoded file of every JPEG target, in the order save_groups indexes them
+                names = file_names[indices]
+                faces = self._encode_on_device(faces_dev, faces, names) if len(indices) > 0 else []
+                if groups[1] is not None:
+                    groups = (groups[0], {k: (rows_of, self._encode_on_device(m, None, names[rows_of]))
+                                          for k, (rows_of, m) in groups[1].items()})
+            elif groups[1] is not None:          # no aligned crops to encode here: the masks go to the host encoder as well
+                groups = (groups[0], {k: (rows_of, m.cpu().numpy() if isinstance(m, torch.Tensor) else m)
+                                      for k, (rows_of, m) in groups[1].items()})
         with trace.range("fcp:save"):
             self.save_groups(faces, file_names[indices], output_dir, *groups)
 

@@ -1,0 +1,488 @@
+// Baseline JPEG entropy-coded segments of uint8 crops (f,h,w,c), c = 3 (RGB, 4:2:0) or 1 (gray), on the device:
+// byte for byte what libjpeg-turbo's default compressor writes between the SOS header and the end of the file
+// (the header itself is jpegenc.jpeg_header, on the host).  Four kernels after one memset:
+//
+//   transform   one lane per 8x8 block, blocks in scan (MCU) order: 16-bit scaled RGB -> YCbCr, edge replication, 2x2 chroma
+//               average with the alternating 1, 2 bias, the 13-bit integer forward DCT ("islow", output scaled by 8),
+//               division by 8 Q rounding half away from zero; 64 int16 per block, zig-zag order, to the workspace
+//   count_scan  one workgroup per face: Huffman bit count of every block (DC difference against the block before it of
+//               the same component), exclusive scan over the face -> the bit offset of every block
+//   emit        one lane per block: the block's code bits, shifted to its offset, into 32-bit big-endian words; words a
+//               block owns alone are stored, the two it may share with its neighbours are OR-ed with ordinary global
+//               atomics (OR commutes: the words do not depend on the order), the last block adds the 1-bits of the pad
+//   stuff       one workgroup per face: FF -> FF 00 with output positions from a scan of per-lane FF counts, then EOI
+//               and the length; every store is checked against the caller's capacity
+//
+// An MCU that overhangs an odd Y block grid carries dummy blocks: all AC zero and the DC of the block before them, i.e. a
+// zero DC difference and an end-of-block, and the DC prediction passes through them unchanged.  They are never transformed.
+#include "fcp_common.h"
+#include "fcp_hip.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxSide = 8192;          // 6 * 512 * 512 blocks * 1658 bits < 2^32: bit offsets of a face fit 32 bits
+constexpr int kMaxBlockBits = 20 + 63 * 26;   // DC: 9-bit code + 11 bits; 63 x (16-bit code + 10 bits); no ZRL can join them
+
+// zig-zag position -> natural (row-major) index
+constexpr int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// T.81 Annex K.1 quantisation tables (natural order) and K.3 Huffman tables (codes per length, symbols in code order)
+const uint8_t kQuantBase[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61,  12, 12, 14, 19, 26, 58, 60, 55,  14, 13, 16, 24, 40, 57, 69, 56,  14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77,  24, 35, 55, 64, 81, 104, 113, 92,  49, 64, 78, 87, 103, 121, 120, 101,
+     72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99,  18, 21, 26, 66, 99, 99, 99, 99,  24, 26, 56, 99, 99, 99, 99, 99,  47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99,  99, 99, 99, 99, 99, 99, 99, 99,  99, 99, 99, 99, 99, 99, 99, 99,  99, 99, 99, 99, 99, 99, 99, 99}};
+const uint8_t kDcCounts[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kAcCounts[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+const uint8_t kAcSymbols[2][162] = {
+    {1,   2,   3,   0,   4,   17,  5,   18,  33,  49,  65,  6,   19,  81,  97,  7,   34,  113, 20,  50,  129, 145, 161, 8,
+     35,  66,  177, 193, 21,  82,  209, 240, 36,  51,  98,  114, 130, 9,   10,  22,  23,  24,  25,  26,  37,  38,  39,  40,
+     41,  42,  52,  53,  54,  55,  56,  57,  58,  67,  68,  69,  70,  71,  72,  73,  74,  83,  84,  85,  86,  87,  88,  89,
+     90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133, 134, 135, 136, 137,
+     138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182,
+     183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 225, 226,
+     227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250},
+    {0,   1,   2,   3,   17,  4,   5,   33,  49,  6,   18,  65,  81,  7,   97,  113, 19,  34,  50,  129, 8,   20,  66,  145,
+     161, 177, 193, 9,   35,  51,  82,  240, 21,  98,  114, 209, 10,  22,  36,  52,  225, 37,  241, 23,  24,  25,  26,  38,
+     39,  40,  41,  42,  53,  54,  55,  56,  57,  58,  67,  68,  69,  70,  71,  72,  73,  74,  83,  84,  85,  86,  87,  88,
+     89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 130, 131, 132, 133, 134, 135,
+     136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180,
+     181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218,
+     226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250}};
+
+struct QuantArg {
+  uint16_t div[2][64];          // 8 * Q per zig-zag position: the DCT's output carries a factor of 8
+};
+struct HuffArg {
+  uint32_t dc[2][12];           // code | length << 16, by size category
+  uint32_t ac[2][256];          // code | length << 16, by run << 4 | size
+};
+
+// Where the blocks of a face are.  One component: blocks row by row.  Three: MCUs of Y00 Y01 Y10 Y11 Cb Cr.
+struct Geometry {
+  int h, w, c;
+  int ybw, ybh;                 // Y block grid: ceil(w / 8), ceil(h / 8)
+  int mw;                       // MCUs (c == 3) or blocks (c == 1) per row
+  int nblk;                     // blocks of a face in the scan, dummies included
+};
+
+struct BlockPos {
+  int comp, by, bx;
+  bool real;
+};
+
+__device__ __forceinline__ BlockPos block_pos(const Geometry& g, int b) {
+  BlockPos p;
+  if (g.c == 1) {
+    p.comp = 0, p.by = b / g.mw, p.bx = b - p.by * g.mw, p.real = true;
+    return p;
+  }
+  const int m = b / 6, k = b - 6 * m;
+  const int my = m / g.mw, mx = m - my * g.mw;
+  if (k < 4) {
+    p.comp = 0, p.by = 2 * my + (k >> 1), p.bx = 2 * mx + (k & 1);
+    p.real = p.by < g.ybh && p.bx < g.ybw;
+  } else {
+    p.comp = k - 3, p.by = my, p.bx = mx, p.real = true;
+  }
+  return p;
+}
+
+// ------------------------------------------------------------------------------------------------ transform
+__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// One pass of the integer DCT over d[0], d[S], .. d[7 S].  The first pass leaves its output scaled up by 4.
+template <int S, bool FIRST>
+__device__ __forceinline__ void dct8(int* d) {
+  constexpr int N = FIRST ? 11 : 15;
+  const int t0 = d[0] + d[7 * S], t7 = d[0] - d[7 * S], t1 = d[S] + d[6 * S], t6 = d[S] - d[6 * S];
+  const int t2 = d[2 * S] + d[5 * S], t5 = d[2 * S] - d[5 * S], t3 = d[3 * S] + d[4 * S], t4 = d[3 * S] - d[4 * S];
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  d[0] = FIRST ? (t10 + t11) * 4 : descale(t10 + t11, 2);
+  d[4 * S] = FIRST ? (t10 - t11) * 4 : descale(t10 - t11, 2);
+  int z1 = (t12 + t13) * 4433;
+  d[2 * S] = descale(z1 + t13 * 6270, N);
+  d[6 * S] = descale(z1 - t12 * 15137, N);
+  z1 = t4 + t7;
+  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int z5 = (z3 + z4) * 9633;
+  const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+  z1 *= -7373, z2 *= -20995;
+  z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+  d[7 * S] = descale(a4 + z1 + z3, N);
+  d[5 * S] = descale(a5 + z2 + z4, N);
+  d[3 * S] = descale(a6 + z2 + z3, N);
+  d[S] = descale(a7 + z1 + z4, N);
+}
+
+__device__ __forceinline__ int chroma_of(const uint8_t* p, int comp) {
+  const int r = p[0], g = p[1], b = p[2];
+  constexpr int kOffset = (128 << 16) + 32767;
+  return comp == 1 ? (-11059 * r - 21709 * g + 32768 * b + kOffset) >> 16 : (32768 * r - 27439 * g - 5329 * b + kOffset) >> 16;
+}
+
+__global__ void __launch_bounds__(kThreads) jpeg_transform_kernel(const uint8_t* __restrict__ crops, Geometry g, QuantArg q,
+                                                                  int16_t* __restrict__ coefs) {
+  const int b = blockIdx.x * kThreads + threadIdx.x;
+  if (b >= g.nblk) return;
+  const BlockPos pos = block_pos(g, b);
+  if (!pos.real) return;                                     // dummy blocks have no coefficients: nothing reads theirs
+  const uint8_t* face = crops + (size_t)blockIdx.y * g.h * g.w * g.c;
+  int d[64];
+  if (pos.comp == 0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int y = min(pos.by * 8 + i, g.h - 1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int x = min(pos.bx * 8 + j, g.w - 1);
+        const uint8_t* p = face + ((size_t)y * g.w + x) * g.c;
+        d[8 * i + j] = (g.c == 1 ? (int)p[0] : (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16) - 128;
+      }
+    }
+  } else {
+    const int rows = (g.h + 1) >> 1;                         // averaged rows that exist; the ones below repeat the last
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int r = min(pos.by * 8 + i, rows - 1);
+      const size_t y0 = 2 * r, y1 = min(2 * r + 1, g.h - 1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int xo = pos.bx * 8 + j;
+        const size_t x0 = min(2 * xo, g.w - 1), x1 = min(2 * xo + 1, g.w - 1);
+        const int sum = chroma_of(face + (y0 * g.w + x0) * 3, pos.comp) + chroma_of(face + (y0 * g.w + x1) * 3, pos.comp) +
+                        chroma_of(face + (y1 * g.w + x0) * 3, pos.comp) + chroma_of(face + (y1 * g.w + x1) * 3, pos.comp);
+        d[8 * i + j] = ((sum + 1 + (j & 1)) >> 2) - 128;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) dct8<1, true>(d + 8 * i);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) dct8<8, false>(d + j);
+
+  const int tbl = pos.comp == 0 ? 0 : 1;
+  uint32_t packed[32];
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {
+    const int v = d[kZigzag[k]];
+    const uint32_t div = q.div[tbl][k];
+    const uint32_t mag = ((uint32_t)abs(v) + (div >> 1)) / div;
+    const uint32_t s = (uint32_t)(v < 0 ? -(int)mag : (int)mag) & 0xffffu;
+    if (k & 1) packed[k >> 1] |= s << 16; else packed[k >> 1] = s;
+  }
+  uint4* dst = reinterpret_cast<uint4*>(coefs + ((size_t)blockIdx.y * g.nblk + b) * 64);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) dst[k] = make_uint4(packed[4 * k], packed[4 * k + 1], packed[4 * k + 2], packed[4 * k + 3]);
+}
+
+// ------------------------------------------------------------------------------------------------ entropy coding
+// DC of the block the difference of block b is taken against: the nearest earlier block of the component that holds samples
+// (dummies repeat the DC before them), 0 at the start of the face.
+__device__ __forceinline__ int dc_before(const Geometry& g, const int16_t* face_coefs, int b) {
+  if (g.c == 1) return b == 0 ? 0 : face_coefs[(size_t)(b - 1) * 64];
+  const int k = b % 6;
+  if (k >= 4) return b < 6 ? 0 : face_coefs[(size_t)(b - 6) * 64];
+  for (int p = (k == 0 ? b - 3 : b - 1); p >= 0; p = (p % 6 == 0 ? p - 3 : p - 1))    // Y blocks are k = 0..3 of every MCU
+    if (block_pos(g, p).real) return face_coefs[(size_t)p * 64];
+  return 0;
+}
+
+__device__ __forceinline__ int size_of(int v) { return 32 - __clz(abs(v)); }             // bits of |v|; 0 for 0
+
+// Walk one block's symbols; sink.put(bits, length) gets every code with its appended value bits (length <= 26).
+template <typename Sink>
+__device__ __forceinline__ void code_block(const Geometry& g, const int16_t* face_coefs, int b, const uint32_t* dc_tab,
+                                           const uint32_t* ac_tab, Sink& sink) {
+  const BlockPos pos = block_pos(g, b);
+  const uint32_t* dc = dc_tab + (pos.comp == 0 ? 0 : 12);
+  const uint32_t* ac = ac_tab + (pos.comp == 0 ? 0 : 256);
+  if (!pos.real) {
+    sink.put(dc[0] & 0xffffu, dc[0] >> 16);
+    sink.put(ac[0] & 0xffffu, ac[0] >> 16);
+    return;
+  }
+  const uint4* src = reinterpret_cast<const uint4*>(face_coefs + (size_t)b * 64);
+  int run = 0;
+  for (int k8 = 0; k8 < 8; ++k8) {
+    const uint4 v4 = src[k8];
+    const uint32_t words[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      int v = (int)(int16_t)(words[j >> 1] >> (16 * (j & 1)));
+      if (k8 == 0 && j == 0) {
+        v -= dc_before(g, face_coefs, b);
+        const int s = size_of(v);
+        const uint32_t e = dc[s];
+        sink.put(((e & 0xffffu) << s) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u)), (e >> 16) + s);
+        continue;
+      }
+      if (v == 0) {
+        ++run;
+        continue;
+      }
+      while (run > 15) {
+        sink.put(ac[0xF0] & 0xffffu, ac[0xF0] >> 16);
+        run -= 16;
+      }
+      const int s = size_of(v);
+      const uint32_t e = ac[(run << 4) | s];
+      sink.put(((e & 0xffffu) << s) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u)), (e >> 16) + s);
+      run = 0;
+    }
+  }
+  if (run > 0) sink.put(ac[0] & 0xffffu, ac[0] >> 16);
+}
+
+struct CountSink {
+  uint32_t bits = 0;
+  __device__ __forceinline__ void put(uint32_t, uint32_t n) { bits += n; }
+};
+
+// Bits go out most significant first.  `acc` holds the `n` (< 32) bits not yet written of the word `word` points at; the
+// first word starts with the bits of the block before (zeros here: OR leaves them alone).
+struct EmitSink {
+  uint32_t* word;
+  uint64_t acc = 0;
+  uint32_t n;
+  bool shared;                  // the word `word` points at may also hold bits of the block before this one
+  __device__ __forceinline__ void put(uint32_t code, uint32_t len) {
+    acc = (acc << len) | code;
+    n += len;
+    if (n >= 32) {
+      n -= 32;
+      const uint32_t full = (uint32_t)(acc >> n);
+      if (shared) atomicOr(word, full); else *word = full;
+      shared = false;
+      ++word;
+      acc &= (1ull << n) - 1ull;
+    }
+  }
+  __device__ __forceinline__ void finish() {                   // the tail shares its word with the block after this one
+    if (n > 0) atomicOr(word, (uint32_t)(acc << (32 - n)));
+  }
+};
+
+__device__ __forceinline__ void load_tables(const HuffArg& hf, uint32_t* dc_tab, uint32_t* ac_tab) {
+  const uint32_t* dc = &hf.dc[0][0];
+  const uint32_t* ac = &hf.ac[0][0];
+  for (int i = threadIdx.x; i < 24; i += kThreads) dc_tab[i] = dc[i];
+  for (int i = threadIdx.x; i < 512; i += kThreads) ac_tab[i] = ac[i];
+  __syncthreads();
+}
+
+// Exclusive scan of one value per lane over the workgroup; *total (same for every lane) is the sum.
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wave_sums, uint32_t* total) {
+  uint32_t incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t up = __shfl_up(incl, off, 64);
+    if ((threadIdx.x & 63) >= off) incl += up;
+  }
+  __syncthreads();                                             // wave_sums may still be read from the round before
+  if ((threadIdx.x & 63) == 63) wave_sums[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < kThreads / 64; ++k) {
+    if (k < (int)(threadIdx.x >> 6)) before += wave_sums[k];
+    all += wave_sums[k];
+  }
+  *total = all;
+  return before + incl - v;
+}
+
+__global__ void __launch_bounds__(kThreads) jpeg_count_scan_kernel(const int16_t* __restrict__ coefs, Geometry g, HuffArg hf,
+                                                                   uint32_t* __restrict__ bitoff) {
+  __shared__ uint32_t dc_tab[24], ac_tab[512], wave_sums[kThreads / 64];
+  load_tables(hf, dc_tab, ac_tab);
+  const int16_t* face_coefs = coefs + (size_t)blockIdx.x * g.nblk * 64;
+  uint32_t* off = bitoff + (size_t)blockIdx.x * (g.nblk + 1);
+  uint32_t carry = 0;
+  for (int base = 0; base < g.nblk; base += kThreads) {        // uniform trip count: every lane reaches the barriers
+    const int b = base + threadIdx.x;
+    CountSink sink;
+    if (b < g.nblk) code_block(g, face_coefs, b, dc_tab, ac_tab, sink);
+    uint32_t total;
+    const uint32_t excl = block_exclusive_scan(sink.bits, wave_sums, &total);
+    if (b < g.nblk) off[b] = carry + excl;
+    carry += total;
+  }
+  if (threadIdx.x == 0) off[g.nblk] = carry;
+}
+
+__global__ void __launch_bounds__(kThreads) jpeg_emit_kernel(const int16_t* __restrict__ coefs, Geometry g, HuffArg hf,
+                                                             const uint32_t* __restrict__ bitoff, uint32_t* __restrict__ raw,
+                                                             size_t raw_words) {
+  __shared__ uint32_t dc_tab[24], ac_tab[512];
+  load_tables(hf, dc_tab, ac_tab);
+  const int b = blockIdx.x * kThreads + threadIdx.x;
+  if (b >= g.nblk) return;
+  const int16_t* face_coefs = coefs + (size_t)blockIdx.y * g.nblk * 64;
+  const uint32_t* off = bitoff + (size_t)blockIdx.y * (g.nblk + 1);
+  const uint32_t start = off[b];
+  EmitSink sink;
+  sink.word = raw + (size_t)blockIdx.y * raw_words + (start >> 5);
+  sink.n = start & 31u;
+  sink.shared = sink.n != 0;
+  code_block(g, face_coefs, b, dc_tab, ac_tab, sink);
+  if (b == g.nblk - 1) {                                       // fill the last byte with 1-bits
+    const uint32_t pad = (8u - (off[g.nblk] & 7u)) & 7u;
+    if (pad) sink.put((1u << pad) - 1u, pad);
+  }
+  sink.finish();
+}
+
+// ------------------------------------------------------------------------------------------------ byte stuffing
+__global__ void __launch_bounds__(kThreads) jpeg_stuff_kernel(const uint32_t* __restrict__ raw, size_t raw_words, int nblk,
+                                                              const uint32_t* __restrict__ bitoff, uint8_t* __restrict__ out,
+                                                              long long out_stride, long long capacity,
+                                                              int32_t* __restrict__ lengths) {
+  __shared__ uint32_t wave_sums[kThreads / 64];
+  const uint32_t nbytes = (bitoff[(size_t)blockIdx.x * (nblk + 1) + nblk] + 7u) >> 3;
+  const uint4* src = reinterpret_cast<const uint4*>(raw + (size_t)blockIdx.x * raw_words);
+  uint8_t* dst = out + (size_t)blockIdx.x * out_stride;
+  long long carry = 0;                                         // stuffed zeros before this round
+  for (uint32_t base = 0; base < nbytes; base += 16 * kThreads) {
+    const uint32_t first = base + 16 * threadIdx.x;            // this lane's 16 bytes: four big-endian words
+    uint32_t words[4] = {0, 0, 0, 0};
+    if (first < nbytes) {
+      const uint4 v = src[first >> 4];
+      words[0] = v.x, words[1] = v.y, words[2] = v.z, words[3] = v.w;
+    }
+    uint32_t ffs = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      ffs += (first + j < nbytes && ((words[j >> 2] >> (24 - 8 * (j & 3))) & 255u) == 255u) ? 1u : 0u;
+    uint32_t total;
+    const uint32_t excl = block_exclusive_scan(ffs, wave_sums, &total);
+    long long p = (long long)first + carry + excl;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if (first + j < nbytes) {
+        const uint32_t byte = (words[j >> 2] >> (24 - 8 * (j & 3))) & 255u;
+        if (p < capacity) dst[p] = (uint8_t)byte;
+        ++p;
+        if (byte == 255u) {
+          if (p < capacity) dst[p] = 0;
+          ++p;
+        }
+      }
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    const long long end = (long long)nbytes + carry;
+    if (end < capacity) dst[end] = 0xFF;
+    if (end + 1 < capacity) dst[end + 1] = 0xD9;
+    lengths[blockIdx.x] = (int32_t)(end + 2);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+struct Layout {
+  Geometry g;
+  size_t raw_words;             // per face, a multiple of 4: the stuffing pass reads 16 bytes at a time
+  size_t coef_bytes, off_bytes, raw_bytes;
+};
+
+Layout layout_of(int f, int h, int w, int c) {
+  Layout l;
+  Geometry& g = l.g;
+  g.h = h, g.w = w, g.c = c;
+  g.ybw = (w + 7) / 8, g.ybh = (h + 7) / 8;
+  if (c == 1) {
+    g.mw = g.ybw;
+    g.nblk = g.ybw * g.ybh;
+  } else {
+    g.mw = (w + 15) / 16;
+    g.nblk = 6 * g.mw * ((h + 15) / 16);
+  }
+  l.raw_words = (((size_t)g.nblk * kMaxBlockBits + 7 + 31) / 32 + 3) & ~(size_t)3;
+  l.coef_bytes = round16((size_t)f * g.nblk * 64 * sizeof(int16_t));
+  l.off_bytes = round16((size_t)f * (g.nblk + 1) * sizeof(uint32_t));
+  l.raw_bytes = (size_t)f * l.raw_words * sizeof(uint32_t);
+  return l;
+}
+
+void huffman_codes(const uint8_t* counts, const uint8_t* symbols, uint32_t* by_symbol) {
+  uint32_t code = 0;
+  int k = 0;
+  for (int len = 1; len <= 16; ++len) {
+    for (int i = 0; i < counts[len - 1]; ++i) by_symbol[symbols[k++]] = code++ | ((uint32_t)len << 16);
+    code <<= 1;
+  }
+}
+
+int check_sizes(int f, int h, int w, int channels) {
+  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "jpeg_encode: bad sizes (f %d, h %d, w %d)", f, h, w);
+  FCP_REQUIRE(channels == 1 || channels == 3, "jpeg_encode: 1 (gray) or 3 (RGB) channels, not %d", channels);
+  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "jpeg_encode: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide,
+              h, w);
+  FCP_REQUIRE(f <= 65535, "jpeg_encode: at most 65535 crops per call");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t fcp_jpeg_workspace_bytes(int f, int h, int w, int channels) {
+  if (check_sizes(f, h, w, channels) != 0) return -1;
+  const Layout l = layout_of(f, h, w, channels);
+  return (int64_t)(l.coef_bytes + l.off_bytes + l.raw_bytes);
+}
+
+extern "C" int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int channels, int quality, int subsampling,
+                                  uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths, void* workspace,
+                                  int64_t workspace_bytes, fcp_stream_t stream) {
+  if (check_sizes(f, h, w, channels) != 0) return FCP_ERR_ARG;
+  FCP_REQUIRE(quality >= 1 && quality <= 100, "jpeg_encode: quality 1..100, not %d", quality);
+  FCP_REQUIRE(subsampling == 2, "jpeg_encode: only 4:2:0 chroma subsampling (2) is built, not %d", subsampling);
+  FCP_REQUIRE(capacity >= 0 && out_stride >= capacity, "jpeg_encode: capacity %lld must be >= 0 and fit the stride %lld",
+              (long long)capacity, (long long)out_stride);
+  if (f == 0) return 0;
+  FCP_REQUIRE(crops && lengths && workspace && (out || capacity == 0), "jpeg_encode: null pointer");
+  const Layout l = layout_of(f, h, w, channels);
+  FCP_REQUIRE(workspace_bytes >= (int64_t)(l.coef_bytes + l.off_bytes + l.raw_bytes),
+              "jpeg_encode: workspace of %lld bytes, fcp_jpeg_workspace_bytes asks for %lld", (long long)workspace_bytes,
+              (long long)(l.coef_bytes + l.off_bytes + l.raw_bytes));
+  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "jpeg_encode: the workspace must be 16-byte aligned");
+
+  QuantArg q;
+  const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;          // the IJG quality scale, baseline range
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 64; ++k) {
+      int v = (kQuantBase[t][kZigzag[k]] * scale + 50) / 100;
+      v = v < 1 ? 1 : (v > 255 ? 255 : v);
+      q.div[t][k] = (uint16_t)(8 * v);
+    }
+  HuffArg hf = {};
+  static const uint8_t dc_symbols[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+  for (int t = 0; t < 2; ++t) {
+    huffman_codes(kDcCounts[t], dc_symbols, hf.dc[t]);
+    huffman_codes(kAcCounts[t], kAcSymbols[t], hf.ac[t]);
+  }
+
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  int16_t* coefs = reinterpret_cast<int16_t*>(ws);
+  uint32_t* bitoff = reinterpret_cast<uint32_t*>(ws + l.coef_bytes);
+  uint32_t* raw = reinterpret_cast<uint32_t*>(ws + l.coef_bytes + l.off_bytes);
+  hipStream_t s = (hipStream_t)stream;
+  FCP_HIP_OK(hipMemsetAsync(raw, 0, l.raw_bytes, s));
+  const dim3 per_block(fcp_cdiv(l.g.nblk, kThreads), f);
+  hipLaunchKernelGGL(jpeg_transform_kernel, per_block, dim3(kThreads), 0, s, crops, l.g, q, coefs);
+  FCP_LAUNCH_OK();
+  hipLaunchKernelGGL(jpeg_count_scan_kernel, dim3(f), dim3(kThreads), 0, s, coefs, l.g, hf, bitoff);
+  FCP_LAUNCH_OK();
+  hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(kThreads), 0, s, coefs, l.g, hf, bitoff, raw, l.raw_words);
+  FCP_LAUNCH_OK();
+  hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(f), dim3(kThreads), 0, s, raw, l.raw_words, l.g.nblk, bitoff, out,
+                     (long long)out_stride, (long long)capacity, lengths);
+  FCP_LAUNCH_OK();
+  return 0;
+}

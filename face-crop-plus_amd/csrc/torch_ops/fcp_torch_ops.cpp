@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -387,6 +387,35 @@ Tensor crop_sharpness(const Tensor& crops, const c10::optional<Tensor>& okf) {
   return sums;
 }
 
+// JPEG entropy-coded segments + EOI of crops (f,h,w,3) or (f,h,w) uint8 into the rows of `out` (f, capacity) uint8 — rows
+// may be a view of a wider buffer (unit stride inside a row) — and the true lengths (f,) int32, which may exceed the
+// capacity (fcp_jpeg_encode_u8; the header is written on the host).  The workspace comes from the caching allocator.
+Tensor jpeg_encode(const Tensor& crops, int64_t quality, int64_t subsampling, const Tensor& out) {
+  dev(crops, "crops", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  TORCH_CHECK((crops.dim() == 4 && (crops.size(3) == 3 || crops.size(3) == 1)) || crops.dim() == 3,
+              "crops (f,h,w,3) or (f,h,w) uint8");
+  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2), c = crops.dim() == 4 ? crops.size(3) : 1;
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops: sizes past int");
+  TORCH_CHECK(quality >= INT_MIN && quality <= INT_MAX && subsampling >= INT_MIN && subsampling <= INT_MAX,
+              "quality / subsampling past int");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kByte && out.get_device() == crops.get_device(),
+              "out must be a uint8 tensor on the device of the crops");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == f, "out must be (", f, ", capacity)");
+  const int64_t capacity = out.size(1), stride = f > 1 ? out.stride(0) : capacity;
+  TORCH_CHECK(capacity == 0 || out.stride(1) == 1, "out: the bytes of a row must be contiguous");
+  TORCH_CHECK(stride >= capacity, "out: rows overlap");
+  Tensor lengths = at::empty({f}, crops.options().dtype(at::kInt));
+  const int64_t need = fcp_jpeg_workspace_bytes((int)f, (int)h, (int)w, (int)c);
+  ok(need < 0 ? -1 : 0, "fcp::jpeg_encode");
+  Tensor work = at::empty({need}, crops.options());
+  ok(fcp_jpeg_encode_u8(crops.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (int)c, (int)quality, (int)subsampling,
+                        capacity > 0 ? out.data_ptr<uint8_t>() : nullptr, stride, capacity, lengths.data_ptr<int32_t>(),
+                        work.data_ptr(), need, cur_stream()),
+     "fcp::jpeg_encode");
+  return lengths;
+}
+
 Tensor bicubic_down4_round(const Tensor& x4) {
   dev(x4, "x4", at::kFloat);
   FCP_DEVICE_GUARD(x4);
@@ -446,6 +475,7 @@ TORCH_LIBRARY(fcp, m) {
         "int interp) -> Tensor");
   m.def("resize_area_u8_ragged(Tensor src, Tensor levels, Tensor(a!) dst) -> ()");
   m.def("crop_sharpness(Tensor crops, Tensor? ok) -> Tensor");
+  m.def("jpeg_encode(Tensor crops, int quality, int subsampling, Tensor(a!) out) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -470,6 +500,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("warp_affine_u8_interp_ragged", &warp_affine_u8_interp_ragged);
   m.impl("resize_area_u8_ragged", &resize_area_u8_ragged);
   m.impl("crop_sharpness", &crop_sharpness);
+  m.impl("jpeg_encode", &jpeg_encode);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

@@ -431,6 +431,34 @@ int fcp_warp_interp_weights(int interp, int16_t* out);
 int fcp_crop_sharpness_u8(const uint8_t* crops, int f, int h, int w, const int32_t* ok,
                           int64_t* sums, fcp_stream_t stream);
 
+/* Baseline JPEG encoding of crops (f,h,w,channels) uint8, channels 3 (RGB,
+ * 4:2:0 chroma) or 1 (gray), on the device: for face i the
+ * entropy-coded segment and the EOI marker, i.e. every byte libjpeg-turbo's
+ * default compressor (integer DCT, standard Huffman tables, no restart
+ * markers, no optimisation) writes after the SOS header at this quality, go
+ * to out + i * out_stride.  lengths[i] is the TRUE length of that stream even
+ * when it exceeds capacity; then only its first capacity bytes are written
+ * and the caller encodes the face some other way.  Nothing is written at or
+ * past out + i * out_stride + capacity, every byte below
+ * min(lengths[i], capacity) is written (out need not be zeroed).
+ * A stream can be larger than the pixels: a block costs at most
+ * 20 + 63 * 26 = 1658 bits (DC: 9-bit code + 11 bits; 63 AC: 16-bit code +
+ * 10 bits), twice that after FF -> FF 00 stuffing, so 416 bytes per 8x8 block
+ * (6 blocks per 16x16 MCU with 3 channels) plus 2 for EOI always suffice.
+ * quality 1..100 (the IJG scale, baseline tables); subsampling must be 2
+ * (4:2:0; it is ignored for gray), 0 (4:4:4) and 1 (4:2:2) are refused.
+ * workspace: fcp_jpeg_workspace_bytes(f,h,w,channels) bytes of device memory,
+ * 16-byte aligned, contents irrelevant (coefficients, bit offsets, the
+ * unstuffed bits: 128 + 4 + 208 bytes per block at most).
+ * One memset and four launches; the result does not depend on the order in
+ * which anything runs.  f == 0 is a no-op; h, w < 1 or > 8192, f > 65535,
+ * channels other than 1 / 3, capacity < 0 or > out_stride fail with a message
+ * (fcp_jpeg_workspace_bytes then returns -1). */
+int64_t fcp_jpeg_workspace_bytes(int f, int h, int w, int channels);
+int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int channels, int quality, int subsampling,
+                       uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths,
+                       void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */

@@ -17,7 +17,12 @@ with tempfile.TemporaryDirectory() as d:
     img = np.asarray(Image.fromarray(base).resize((size, size), Image.BICUBIC))
     for i in range(n):
         Image.fromarray(np.roll(img, i, 1)).save(os.path.join(src, f"{i:05d}.jpg"), quality=90)
-    c = Cropper(resize_size=size, batch_size=int(os.environ.get("FCP_BENCH_BATCH", "64")), num_processes=nproc, device="cuda:0", weights={"retinaface": "generated"})
+    extra = {}                                                # FCP_BENCH_FORMAT=jpg, FCP_BENCH_ENCODER=host|device (Cropper(encoder=...))
+    if os.environ.get("FCP_BENCH_FORMAT"):
+        extra["output_format"] = os.environ["FCP_BENCH_FORMAT"]
+    if os.environ.get("FCP_BENCH_ENCODER"):
+        extra["encoder"] = os.environ["FCP_BENCH_ENCODER"]
+    c = Cropper(resize_size=size, batch_size=int(os.environ.get("FCP_BENCH_BATCH", "64")), num_processes=nproc, device="cuda:0", weights={"retinaface": "generated"}, **extra)
     c.gpu_workers = nproc                                     # exactly nproc GPU worker threads (the product default: max(2, num_processes))
     if io:
         c.io_threads = io
@@ -32,7 +37,7 @@ with tempfile.TemporaryDirectory() as d:
     procs = c._io_procs
     print(f"{n} jpg {size}x{size}, num_processes={nproc}, io_threads={c.io_threads}, io_processes="
           f"{(procs.readers, procs.writers) if procs is not None else 'off (threads)'}, host cores {os.cpu_count()}: "
-          f"{n / dt:.1f} images/s ({len(os.listdir(dst))} crops written)")
+          f"{n / dt:.1f} images/s ({len(os.listdir(dst))} crops written)" + (f" {extra}" if extra else ""))
     if os.environ.get("FCP_STREAM_MATRIX"):                 # which of the workers' streams share a hardware queue (engine._streams_overlap)
         import torch
         from face_crop_plus_amd import engine as E
