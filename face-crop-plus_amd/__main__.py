@@ -50,7 +50,21 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-enc", "--encoder", type=str, default=argparse.SUPPRESS, choices=("host", "device"),
                    help="where output files are compressed: 'host' (default, Pillow on the I/O pool) or 'device' (JPEG "
                         "files of aligned crops and masks are encoded on the GPU, byte for byte the same files)")
+    p.add_argument("-bg", "--background", type=_background, default=argparse.SUPPRESS,
+                   help="replace the background of the crops with a uniform fill: 'R,G,B' or a single gray level, each "
+                        "0..255; by default the crops keep their background")
+    p.add_argument("-fg", "--foreground", type=json.loads, default=argparse.SUPPRESS,
+                   help="JSON list of the face parser's class indices that count as the subject (with --background; default "
+                        "every class but 0)")
+    p.add_argument("-fe", "--feather", type=int, default=argparse.SUPPRESS,
+                   help="soft edge of the background replacement in pixels: 0, 3, 5 or 7 (with --background; default 5)")
     return p
+
+
+def _background(text: str):
+    """'R,G,B' -> [R, G, B], 'V' -> V."""
+    parts = [int(v) for v in text.split(",")]
+    return parts[0] if len(parts) == 1 else parts
 
 
 def parse_args(argv=None) -> dict:

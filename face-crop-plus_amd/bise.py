@@ -262,9 +262,11 @@ class BiSeNet:
         return out
 
     @torch.no_grad()
-    def predict(self, images):
+    def predict(self, images, return_labels: bool = False):
         """Reference signature (bise.py:328-418).  ``images``: (N,3,H,W) float 0..255 tensor, a
-        list of such (3,H,W) tensors, or — the fast path — (N,H,W,3) uint8 crops."""
+        list of such (3,H,W) tensors, or — the fast path — (N,H,W,3) uint8 crops.  ``return_labels`` appends the label
+        map (N,H,W) uint8 the groups were made from, on the device (``Cropper(background=...)`` mattes with it); with
+        neither ``attr_groups`` nor ``mask_groups`` both groups are None and the label map is all there is."""
         with torch.cuda.device(self.device):
             if isinstance(images, list):
                 images = torch.stack(images)
@@ -278,4 +280,6 @@ class BiSeNet:
                 attr_groups = {k: v for k, v in self.group_by_attributes(counts).items() if len(v) > 0}
             if self.mask_groups is not None:
                 mask_groups = {k: v for k, v in self.group_by_masks(labels, counts).items() if len(v[0]) > 0}
+        if return_labels:
+            return attr_groups, mask_groups, labels
         return attr_groups, mask_groups

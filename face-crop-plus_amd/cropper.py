@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import align, trace
+from . import matte as matting
 from ._io_codec import write_bytes
 from .batch import batch_geometry, build_batch, upload_sources
 from .utils import get_ldm_slices, parse_landmarks_file, read_image, read_images, write_image
@@ -54,6 +55,9 @@ class Cropper:
         warp_family: str | None = None,
         crop_source: str = "batch",
         encoder: str = "host",
+        background: int | tuple[int, int, int] | list[int] | None = None,
+        foreground: list[int] | None = None,
+        feather: int | None = None,
         interpolation: str = "linear",
         min_sharpness: float | None = None,
     ):
@@ -82,7 +86,18 @@ class Cropper:
         the JPEG files (.jpg / .jpeg / .jpe) of aligned crops and parse masks on the GPU (``jpegenc.encode_jpeg``) — the
         same files byte for byte — so that the lengths and the compressed streams come back instead of the pixels and the
         I/O pool only writes.  Every other file (other formats, the images of "no alignment", a crop whose stream
-        outgrows its slot) is encoded on the host as before."""
+        outgrows its slot) is encoded on the host as before.
+        ``background``: replace what is behind the subject — an int 0..255 (gray) or three of them (R, G, B) fills every
+        pixel the face parser does not label as one of the ``foreground`` classes (BiSeNet indices; None: every class but
+        0), through a soft edge of ``feather`` pixels (0, 3, 5 or 7; None: 5): the Gaussian of that size over the hard
+        mask, OpenCV's fixed-point ``cv2.GaussianBlur(mask, (feather, feather), 0)`` restated, then
+        ``(crop * alpha + fill * (255 - alpha) + 127) // 255`` (``matte.matte``, INTEGRATION.md section 2g).  It runs on
+        the device after ``min_sharpness`` and the parse, which both see the original crop, and before anything is
+        encoded; the mask files of ``mask_groups`` are unchanged.  A face without a foreground pixel becomes a uniformly
+        filled image and is still written (``attr_groups`` is the way to drop such faces).  It creates the parser even
+        without ``attr_groups`` / ``mask_groups``, needs aligned crops like ``min_sharpness``, and ``foreground`` /
+        ``feather`` without ``background`` raise ValueError.  None (the default) launches nothing.
+        ``Cropper.matte`` applies it to crops and label maps one already has."""
         if encoder not in ("host", "device"):
             raise ValueError(f"unknown encoder {encoder!r}: choose 'host' or 'device'")
         self.encoder = encoder
@@ -103,6 +118,18 @@ class Cropper:
                                  "landmarks=None (no alignment), where the faces are the images themselves")
             min_sharpness = float(min_sharpness)
         self.min_sharpness = min_sharpness
+        self.background = matting.check_background(background)
+        if self.background is None:
+            if foreground is not None or feather is not None:
+                raise ValueError("foreground / feather need background: without it they would do nothing")
+            self.foreground, self.foreground_bits, self.feather = None, 0, None
+        else:
+            if det_threshold is None and landmarks is None:
+                raise ValueError("background needs aligned crops: it cannot be combined with det_threshold=None and "
+                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            self.foreground_bits = matting.check_foreground(foreground)
+            self.foreground = tuple(c for c in range(matting.NUM_CLASSES) if self.foreground_bits >> c & 1)
+            self.feather = matting.check_feather(feather)
         self.crop_source = crop_source
         self.interpolation = interpolation
         self.output_size = output_size
@@ -184,7 +211,7 @@ class Cropper:
             from .rrdb import RRDBNet
             self.enh_model = RRDBNet(self.enh_threshold)
             self.enh_model.load(self.device, self.weights.get("rrdb"), self.precision)
-        if self.attr_groups is not None or self.mask_groups is not None:
+        if self.attr_groups is not None or self.mask_groups is not None or self.background is not None:
             from .bise import BiSeNet
             self.par_model = BiSeNet(self.attr_groups, self.mask_groups, self.batch_size)
             self.par_model.load(self.device, self.weights.get("bisenet"), self.precision)
@@ -253,6 +280,24 @@ class Cropper:
         with torch.cuda.device(self.device):
             sums = align.sharpness_sums(torch.from_numpy(crops).to(self.device))
             return align.sharpness_score(sums, crops.shape[1] * crops.shape[2])
+
+    def matte(self, crops: np.ndarray, labels: np.ndarray):
+        """What ``background`` does, for crops and label maps one already has: (F,H,W,3) uint8 RGB crops and (F,H,W)
+        uint8 labels -> (the composited crops (F,H,W,3) uint8, the alpha (F,H,W) uint8), with this Cropper's
+        ``background`` / ``foreground`` / ``feather`` (``matte.matte``).  The alpha is what an RGBA file needs."""
+        if self.background is None:
+            raise ValueError("Cropper.matte needs a Cropper with background=...")
+        crops, labels = np.ascontiguousarray(crops), np.ascontiguousarray(labels)
+        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
+            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
+        if labels.dtype != np.uint8 or labels.shape != crops.shape[:3]:
+            raise ValueError(f"labels must be {crops.shape[:3]} uint8, not {labels.dtype} {labels.shape}")
+        if crops.size == 0:
+            return np.zeros(crops.shape, np.uint8), np.zeros(labels.shape, np.uint8)
+        with torch.cuda.device(self.device):
+            out, alpha = matting.matte(torch.from_numpy(crops).to(self.device), torch.from_numpy(labels).to(self.device),
+                                       self.foreground_bits, self.feather, self.background, with_alpha=True)
+            return out.cpu().numpy(), alpha.cpu().numpy()
 
     def encode_jpeg(self, crops: np.ndarray) -> list:
         """What ``encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F JPEG files as
@@ -486,7 +531,17 @@ class Cropper:
                 if faces_dev is None:
                     faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]
                 with trace.range("fcp:parse"):
-                    groups = self.par_model.predict(faces_dev)
+                    if self.background is not None and isinstance(faces_dev, torch.Tensor):
+                        # one parse per batch: the label map behind the groups is the one the matte uses
+                        *groups, labels = self.par_model.predict(faces_dev, return_labels=True)
+                        groups = tuple(groups)
+                    else:
+                        groups = self.par_model.predict(faces_dev)
+                if self.background is not None and isinstance(faces_dev, torch.Tensor):
+                    with trace.range("fcp:matte"):
+                        faces_dev, _ = matting.matte(faces_dev, labels, self.foreground_bits, self.feather, self.background)
+                    # the host copy, if the host encoder needs one, is the matted crop as well
+                    faces = None if self.encoder == "device" else faces_dev.cpu().numpy()
             if self.encoder == "device" and isinstance(faces_dev, torch.Tensor):
                 # aligned crops (and their masks): same size, on the device.  Faces and mask rows become lists that hold
                 # the encoded file of every JPEG target, in the order save_groups indexes them

@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / matte
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -416,6 +416,29 @@ Tensor jpeg_encode(const Tensor& crops, int64_t quality, int64_t subsampling, co
   return lengths;
 }
 
+// Crops (f,h,w,3) uint8 over a uniform fill through the soft mask of their label maps (f,h,w) uint8: the composited
+// crops and, with `with_alpha`, the alpha (f,h,w) uint8 (else an empty tensor) (fcp_matte_u8).
+std::tuple<Tensor, Tensor> matte(const Tensor& crops, const Tensor& labels, int64_t class_bits, int64_t feather, int64_t bg_r,
+                                 int64_t bg_g, int64_t bg_b, bool with_alpha) {
+  dev(crops, "crops", at::kByte);
+  dev(labels, "labels", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
+  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
+  TORCH_CHECK(labels.get_device() == crops.get_device() && labels.dim() == 3 && labels.size(0) == f && labels.size(1) == h &&
+                  labels.size(2) == w, "labels must be (", f, ",", h, ",", w, ") uint8 on the device of the crops");
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  for (int64_t v : {feather, bg_r, bg_g, bg_b}) TORCH_CHECK(v >= INT_MIN && v <= INT_MAX, "feather / fill past int");
+  Tensor out = at::empty_like(crops);
+  Tensor alpha = with_alpha ? at::empty({f, h, w}, crops.options()) : at::empty({0}, crops.options());
+  ok(fcp_matte_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits,
+                  (int)feather, (int)bg_r, (int)bg_g, (int)bg_b, out.data_ptr<uint8_t>(),
+                  with_alpha ? alpha.data_ptr<uint8_t>() : nullptr, cur_stream()),
+     "fcp::matte");
+  return {out, alpha};
+}
+
 Tensor bicubic_down4_round(const Tensor& x4) {
   dev(x4, "x4", at::kFloat);
   FCP_DEVICE_GUARD(x4);
@@ -476,6 +499,8 @@ TORCH_LIBRARY(fcp, m) {
   m.def("resize_area_u8_ragged(Tensor src, Tensor levels, Tensor(a!) dst) -> ()");
   m.def("crop_sharpness(Tensor crops, Tensor? ok) -> Tensor");
   m.def("jpeg_encode(Tensor crops, int quality, int subsampling, Tensor(a!) out) -> Tensor");
+  m.def("matte(Tensor crops, Tensor labels, int class_bits, int feather, int bg_r, int bg_g, int bg_b, bool with_alpha) "
+        "-> (Tensor, Tensor)");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -501,6 +526,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("resize_area_u8_ragged", &resize_area_u8_ragged);
   m.impl("crop_sharpness", &crop_sharpness);
   m.impl("jpeg_encode", &jpeg_encode);
+  m.impl("matte", &matte);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

@@ -459,6 +459,31 @@ int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int channels, 
                        uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths,
                        void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
 
+/* Background replacement of crops (f,h,w,3) uint8 RGB from label maps
+ * (f,h,w) uint8, in integers throughout:
+ *   m     = 255 where the label is below 32 and that bit of class_bits is
+ *           set, else 0 (labels 19..255 are background);
+ *   alpha = m for feather 0, else the separable fixed-point Gaussian of m
+ *           with OpenCV's 8.8 taps for ksize = feather (3: 64,128,64;
+ *           5: 16,64,96,64,16; 7: 8,28,56,72,56,28,8): a horizontal pass H
+ *           (at most 65280, no rounding), a vertical pass and one rounding
+ *           (sum + 32768) >> 16, BORDER_REFLECT_101 iterated until the index
+ *           is inside (a dimension of size 1 maps everything to index 0):
+ *           cv2.GaussianBlur(m, (feather, feather), 0) restated;
+ *   out   = (c * alpha + bg * (255 - alpha) + 127) / 255 per channel, bg =
+ *           (bg_r, bg_g, bg_b): round to nearest, there are no ties.
+ * out (f,h,w,3) and alpha (f,h,w) are written once, by ordinary stores;
+ * alpha may be NULL.  out MAY BE crops (in place): an output pixel depends
+ * on its own crop pixel and on labels only.  labels must not overlap out or
+ * alpha.  The three arrays may start at any byte; nothing outside them is
+ * written.  One launch, no workspace, the same bytes from run to run.
+ * f == 0 is a no-op; f < 0, h or w < 1 or > 8192, f > 65535, a feather other
+ * than 0 / 3 / 5 / 7, a fill component outside 0..255, a bit of class_bits at
+ * or above 19, or (f > 0) a null crops / labels / out fail with a message,
+ * before any HIP call. */
+int fcp_matte_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather,
+                 int bg_r, int bg_g, int bg_b, uint8_t* out, uint8_t* alpha, fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */

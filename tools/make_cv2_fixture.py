@@ -7,12 +7,13 @@ kernels to them.
 
     pip install opencv-python torchvision          # anywhere with a network
     python tools/make_cv2_fixture.py                # writes tests/golden/opencv_align.npz, opencv_batch.npz,
-                                                    #        opencv_interp.npz, opencv_sharpness.npz,
+                                                    #        opencv_interp.npz, opencv_sharpness.npz, opencv_matte.npz,
                                                     #        tests/golden/torchvision_resnet50.npz
     python -m pytest tests/test_third_party_pins.py            # oracle vs the pins (CPU)
     python -m pytest tests/test_third_party_pins.py -m gpu     # kernels vs the pins (MI355X)
     python -m pytest tests/test_warp_interp_pins.py            # cubic / Lanczos-4 restatement (and, -m gpu, kernels)
     python -m pytest tests/test_sharpness_pins.py              # RGB2GRAY + Laplacian restatement (and, -m gpu, the kernel)
+    python -m pytest tests/test_matte_pins.py                  # GaussianBlur restatement (and, -m gpu, the kernel's alpha)
 
 Everything is called exactly the way the reference calls it:
   cropper.py:515-527   cv2.estimateAffinePartial2D / estimateAffine2D(src, dst, ransacReprojThreshold=np.inf)[0]
@@ -20,6 +21,7 @@ Everything is called exactly the way the reference calls it:
                        and the same call with flags=INTER_CUBIC / INTER_LANCZOS4 (Cropper(interpolation=...))
   utils.py:320-335     cv2.resize(image, (ww, hh), interpolation=INTER_AREA | INTER_CUBIC) + cv2.copyMakeBorder
   (not in the reference) cv2.Laplacian(cv2.cvtColor(crop, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var()   (Cropper(min_sharpness=...))
+  (not in the reference) cv2.GaussianBlur(mask, (K, K), 0) for K in 3, 5, 7 on 0/255 masks          (Cropper(background=...))
   retinaface.py:93-99  torchvision.models.resnet50() + _utils.IntermediateLayerGetter(layer2, layer3, layer4)
 Only data is stored (inputs, outputs, library versions): no third-party source.
 """
@@ -213,6 +215,23 @@ def make_sharpness(cv2):
     print("wrote opencv_sharpness.npz")
 
 
+def make_matte(cv2):
+    """cv2.GaussianBlur(m, (K, K), 0), K in 3, 5, 7, on seeded random 0/255 CV_8U masks for tests/test_matte_pins.py: the
+    bit-exact fixed-point path of small kernels with sigma 0 and the default BORDER_REFLECT_101, at sizes below the radius
+    (1x1, 1x5, 2x2, 3x2, 2x7: the border is reflected more than once) and above it."""
+    rng = np.random.default_rng(700)
+    out = describe_cv2(cv2)
+    sizes = ((1, 1), (1, 5), (2, 2), (3, 2), (2, 7), (13, 17), (64, 48))
+    for k, (h, w) in enumerate(sizes):
+        m = (rng.integers(0, 2, (h, w)) * 255).astype(np.uint8)
+        out[f"matte{k}_mask"] = m
+        for ksize in (3, 5, 7):
+            out[f"matte{k}_blur{ksize}"] = cv2.GaussianBlur(m, (ksize, ksize), 0)
+    out["matte_cases"] = np.array(len(sizes))
+    np.savez_compressed(os.path.join(GOLDEN, "opencv_matte.npz"), **out)
+    print("wrote opencv_matte.npz")
+
+
 def make_resnet():
     """retinaface.py:93-99 with the build's generated `body.*` weights: the three feature maps torchvision's own
     ResNet-50 + IntermediateLayerGetter return for one seeded 96x128 input."""
@@ -250,6 +269,7 @@ def main():
             make_batch(cv2)
             make_interp(cv2)
             make_sharpness(cv2)
+            make_matte(cv2)
     if args.only != "cv2":
         try:
             import torchvision  # noqa: F401
