@@ -58,6 +58,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "every class but 0)")
     p.add_argument("-fe", "--feather", type=int, default=argparse.SUPPRESS,
                    help="soft edge of the background replacement in pixels: 0, 3, 5 or 7 (with --background; default 5)")
+    p.add_argument("-cl", "--clahe", type=float, default=argparse.SUPPRESS,
+                   help="equalise the contrast of the crops: clip limit (> 0, usually 2.0) of a contrast-limited adaptive "
+                        "histogram equalisation of their luma; by default the crops keep their contrast")
+    p.add_argument("-cg", "--clahe-grid", type=int, default=argparse.SUPPRESS,
+                   help="tiles per side of the equalisation, 1..16 (with --clahe; default 8)")
     return p
 
 

@@ -90,6 +90,7 @@ SIGNATURES = {
     "fcp_crop_sharpness_u8": [_P, _I, _I, _I, _P, _P, _P],
     "fcp_jpeg_encode_u8": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _P, _P, _L, _P],
     "fcp_matte_u8": [_P, _P, _I, _I, _I, C.c_uint32, _I, _I, _I, _I, _P, _P, _P],
+    "fcp_clahe_u8": [_P, _I, _I, _I, _I, C.c_double, _P, _P, _P],
 }
 EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes", "fcp_jpeg_workspace_bytes"] + list(SIGNATURES)
 

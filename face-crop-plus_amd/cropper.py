@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import align, trace
+from . import clahe as equalizing
 from . import matte as matting
 from ._io_codec import write_bytes
 from .batch import batch_geometry, build_batch, upload_sources
@@ -58,6 +59,8 @@ class Cropper:
         background: int | tuple[int, int, int] | list[int] | None = None,
         foreground: list[int] | None = None,
         feather: int | None = None,
+        clahe: float | None = None,
+        clahe_grid: int | None = None,
         interpolation: str = "linear",
         min_sharpness: float | None = None,
     ):
@@ -97,7 +100,16 @@ class Cropper:
         filled image and is still written (``attr_groups`` is the way to drop such faces).  It creates the parser even
         without ``attr_groups`` / ``mask_groups``, needs aligned crops like ``min_sharpness``, and ``foreground`` /
         ``feather`` without ``background`` raise ValueError.  None (the default) launches nothing.
-        ``Cropper.matte`` applies it to crops and label maps one already has."""
+        ``Cropper.matte`` applies it to crops and label maps one already has.
+        ``clahe``: equalise the contrast of every crop — the clip limit (finite, > 0; 2.0 is the usual value) of a
+        contrast-limited adaptive histogram equalisation of the luma on a ``clahe_grid`` x ``clahe_grid`` tiling (1..16;
+        None: 8), ``cv2.createCLAHE(clahe, (grid, grid)).apply(Y)`` between ``cv2.cvtColor(crop, COLOR_RGB2YCrCb)`` and
+        ``COLOR_YCrCb2RGB`` restated on the device (``clahe.clahe``).  It runs after
+        ``min_sharpness`` and the parse, which both see the original crop, and before ``background`` (the fill colour
+        stays exact) and the encoder; the histograms are over the whole crop and mask files are unchanged.  It needs
+        aligned crops like ``min_sharpness`` and an ``output_size`` of at least ``2 * clahe_grid`` on both sides;
+        ``clahe_grid`` without ``clahe`` raises ValueError.  None (the default) launches nothing.
+        ``Cropper.equalize`` applies it to crops one already has."""
         if encoder not in ("host", "device"):
             raise ValueError(f"unknown encoder {encoder!r}: choose 'host' or 'device'")
         self.encoder = encoder
@@ -130,6 +142,17 @@ class Cropper:
             self.foreground_bits = matting.check_foreground(foreground)
             self.foreground = tuple(c for c in range(matting.NUM_CLASSES) if self.foreground_bits >> c & 1)
             self.feather = matting.check_feather(feather)
+        self.clahe = equalizing.check_clahe(clahe)
+        if self.clahe is None:
+            if clahe_grid is not None:
+                raise ValueError("clahe_grid needs clahe: without it it would do nothing")
+            self.clahe_grid = None
+        else:
+            if det_threshold is None and landmarks is None:
+                raise ValueError("clahe needs aligned crops: it cannot be combined with det_threshold=None and "
+                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            size = (output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size)
+            self.clahe_grid = equalizing.check_grid(clahe_grid, size)
         self.crop_source = crop_source
         self.interpolation = interpolation
         self.output_size = output_size
@@ -298,6 +321,19 @@ class Cropper:
             out, alpha = matting.matte(torch.from_numpy(crops).to(self.device), torch.from_numpy(labels).to(self.device),
                                        self.foreground_bits, self.feather, self.background, with_alpha=True)
             return out.cpu().numpy(), alpha.cpu().numpy()
+
+    def equalize(self, crops: np.ndarray) -> np.ndarray:
+        """What ``clahe`` does, for crops one already has: (F,H,W,3) uint8 RGB -> the equalised crops (F,H,W,3) uint8,
+        with this Cropper's ``clahe`` / ``clahe_grid`` (``clahe.clahe``)."""
+        if self.clahe is None:
+            raise ValueError("Cropper.equalize needs a Cropper with clahe=...")
+        crops = np.ascontiguousarray(crops)
+        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
+            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
+        if crops.shape[0] == 0:
+            return np.zeros(crops.shape, np.uint8)
+        with torch.cuda.device(self.device):
+            return equalizing.clahe(torch.from_numpy(crops).to(self.device), self.clahe, self.clahe_grid).cpu().numpy()
 
     def encode_jpeg(self, crops: np.ndarray) -> list:
         """What ``encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F JPEG files as
@@ -527,6 +563,7 @@ class Cropper:
                 keep = score >= self.min_sharpness
                 faces, faces_dev = (None if faces is None else faces[keep]), faces_dev[torch.from_numpy(keep).to(self.device)]
                 indices = [i for i, k in zip(indices, keep) if k]
+            labels = None
             if self.par_model is not None and len(indices) > 0:
                 if faces_dev is None:
                     faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]
@@ -537,11 +574,16 @@ class Cropper:
                         groups = tuple(groups)
                     else:
                         groups = self.par_model.predict(faces_dev)
-                if self.background is not None and isinstance(faces_dev, torch.Tensor):
+            if len(indices) > 0 and isinstance(faces_dev, torch.Tensor) and (self.clahe is not None or labels is not None):
+                # after the parse, which saw the original crop: first the contrast, over the whole crop, then the fill
+                if self.clahe is not None:
+                    with trace.range("fcp:clahe"):
+                        faces_dev = equalizing.clahe(faces_dev, self.clahe, self.clahe_grid)
+                if labels is not None:
                     with trace.range("fcp:matte"):
                         faces_dev, _ = matting.matte(faces_dev, labels, self.foreground_bits, self.feather, self.background)
-                    # the host copy, if the host encoder needs one, is the matted crop as well
-                    faces = None if self.encoder == "device" else faces_dev.cpu().numpy()
+                # the host copy, if the host encoder needs one, is the equalised / matted crop as well
+                faces = None if self.encoder == "device" else faces_dev.cpu().numpy()
             if self.encoder == "device" and isinstance(faces_dev, torch.Tensor):
                 # aligned crops (and their masks): same size, on the device.  Faces and mask rows become lists that hold
                 # the encoded file of every JPEG target, in the order save_groups indexes them

@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / matte
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / matte / clahe
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -439,6 +439,23 @@ std::tuple<Tensor, Tensor> matte(const Tensor& crops, const Tensor& labels, int6
   return {out, alpha};
 }
 
+// Crops (f,h,w,3) uint8 with the luma equalised by CLAHE on a grid x grid tiling (fcp_clahe_u8); the LUT workspace
+// lives for the call.
+Tensor clahe(const Tensor& crops, int64_t grid, double clip_limit) {
+  dev(crops, "crops", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
+  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
+  TORCH_CHECK(grid >= 1 && grid <= 16, "clahe: grid must be 1..16 (got ", grid, ")");
+  Tensor out = at::empty_like(crops);
+  Tensor luts = at::empty({f, grid, grid, 256}, crops.options());
+  ok(fcp_clahe_u8(crops.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (int)grid, clip_limit, luts.data_ptr<uint8_t>(),
+                  out.data_ptr<uint8_t>(), cur_stream()),
+     "fcp::clahe");
+  return out;
+}
+
 Tensor bicubic_down4_round(const Tensor& x4) {
   dev(x4, "x4", at::kFloat);
   FCP_DEVICE_GUARD(x4);
@@ -501,6 +518,7 @@ TORCH_LIBRARY(fcp, m) {
   m.def("jpeg_encode(Tensor crops, int quality, int subsampling, Tensor(a!) out) -> Tensor");
   m.def("matte(Tensor crops, Tensor labels, int class_bits, int feather, int bg_r, int bg_g, int bg_b, bool with_alpha) "
         "-> (Tensor, Tensor)");
+  m.def("clahe(Tensor crops, int grid, float clip_limit) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -527,6 +545,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("crop_sharpness", &crop_sharpness);
   m.impl("jpeg_encode", &jpeg_encode);
   m.impl("matte", &matte);
+  m.impl("clahe", &clahe);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

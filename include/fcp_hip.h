@@ -484,6 +484,52 @@ int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int channels, 
 int fcp_matte_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather,
                  int bg_r, int bg_g, int bg_b, uint8_t* out, uint8_t* alpha, fcp_stream_t stream);
 
+/* Contrast-limited adaptive histogram equalisation of the luma of crops
+ * (f,h,w,3) uint8 RGB: cv2.createCLAHE(clip_limit,
+ * (grid, grid)).apply(Y) between cv2.cvtColor(COLOR_RGB2YCrCb) and
+ * cvtColor(COLOR_YCrCb2RGB), restated.  With g = grid, c = clip_limit:
+ *   colour  Y  = (4899 R + 9617 G + 1868 B + 8192) >> 14
+ *           Cr = sat(((R - Y) 11682 + (128 << 14) + 8192) >> 14)
+ *           Cb = sat(((B - Y) 9241 + (128 << 14) + 8192) >> 14); only Y is
+ *           equalised, and from the result Y':
+ *           R  = sat(Y' + (((Cr - 128) 22987 + 8192) >> 14))
+ *           G  = sat(Y' + (((Cb - 128) (-5636) + (Cr - 128) (-11698) + 8192) >> 14))
+ *           B  = sat(Y' + (((Cb - 128) 29049 + 8192) >> 14))
+ *           sat clamps to 0..255; arithmetic shifts of signed 32-bit values;
+ *   tiles   if h % g == 0 and w % g == 0 the luma plane as is, else extended
+ *           by g - h % g rows below and g - w % g columns on the right with
+ *           BORDER_REFLECT_101 (a divisible dimension grows by a full g
+ *           when the other is not: OpenCV's rule); th, tw = extended size /
+ *           g, area = th tw;
+ *   LUT     per tile: the 256-bin histogram; clip = max(int(c area / 256),
+ *           1) in double, truncated (area or more clips nothing); bins above
+ *           clip are cut to it, the excess summed into clipped; batch =
+ *           clipped / 256 is added to every bin; residual = clipped - 256
+ *           batch; if residual > 0, step = max(256 / residual, 1) and bin i
+ *           gets + 1 iff i % step == 0 and i / step < residual; s = the
+ *           inclusive prefix sum; lut[i] = sat(rint(float(s[i]) * scale)),
+ *           scale = 255.0f / float(area), round half to even;
+ *   apply   per pixel (y, x), float32, each operation rounded on its own:
+ *           inv_th = 1.0f / th; tyf = y inv_th - 0.5f; ty1 = floor(tyf);
+ *           ya = tyf - ty1; ya1 = 1.0f - ya; then ty2 = min(ty1 + 1, g - 1),
+ *           ty1 = max(ty1, 0); the same in x;
+ *           res = (L[ty1][tx1][Y] xa1 + L[ty1][tx2][Y] xa) ya1
+ *               + (L[ty2][tx1][Y] xa1 + L[ty2][tx2][Y] xa) ya;
+ *           Y' = sat(rint(res)).
+ * luts is a workspace of f * grid * grid * 256 bytes, 4-byte aligned, that
+ * holds the LUTs [f][grid][grid][256] afterwards; it must not overlap crops
+ * or out.  out (f,h,w,3) is written once, by ordinary stores;
+ * out MAY BE crops (in place): an output pixel depends on its own crop
+ * pixel and on the LUTs only.  crops and out may start at any byte; nothing
+ * outside the arrays is written.  Two launches on `stream`; the histograms
+ * are summed with integer atomics, which commute:
+ * the same bytes from run to run.
+ * f == 0 is a no-op; grid outside 1..16, f < 0 or > 65535, h or w below
+ * 2 * grid or above 4096, a clip_limit that is not finite or not > 0, or
+ * (f > 0) a null crops / luts / out or a misaligned luts fail with a
+ * message, before any HIP call. */
+int fcp_clahe_u8(const uint8_t* crops, int f, int h, int w, int grid, double clip_limit, uint8_t* luts, uint8_t* out, fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */

@@ -8,12 +8,14 @@ kernels to them.
     pip install opencv-python torchvision          # anywhere with a network
     python tools/make_cv2_fixture.py                # writes tests/golden/opencv_align.npz, opencv_batch.npz,
                                                     #        opencv_interp.npz, opencv_sharpness.npz, opencv_matte.npz,
+                                                    #        opencv_clahe.npz,
                                                     #        tests/golden/torchvision_resnet50.npz
     python -m pytest tests/test_third_party_pins.py            # oracle vs the pins (CPU)
     python -m pytest tests/test_third_party_pins.py -m gpu     # kernels vs the pins (MI355X)
     python -m pytest tests/test_warp_interp_pins.py            # cubic / Lanczos-4 restatement (and, -m gpu, kernels)
     python -m pytest tests/test_sharpness_pins.py              # RGB2GRAY + Laplacian restatement (and, -m gpu, the kernel)
     python -m pytest tests/test_matte_pins.py                  # GaussianBlur restatement (and, -m gpu, the kernel's alpha)
+    python -m pytest tests/test_clahe_pins.py                  # YCrCb + CLAHE restatement (and, -m gpu, the kernels)
 
 Everything is called exactly the way the reference calls it:
   cropper.py:515-527   cv2.estimateAffinePartial2D / estimateAffine2D(src, dst, ransacReprojThreshold=np.inf)[0]
@@ -22,6 +24,7 @@ Everything is called exactly the way the reference calls it:
   utils.py:320-335     cv2.resize(image, (ww, hh), interpolation=INTER_AREA | INTER_CUBIC) + cv2.copyMakeBorder
   (not in the reference) cv2.Laplacian(cv2.cvtColor(crop, cv2.COLOR_RGB2GRAY), cv2.CV_64F).var()   (Cropper(min_sharpness=...))
   (not in the reference) cv2.GaussianBlur(mask, (K, K), 0) for K in 3, 5, 7 on 0/255 masks          (Cropper(background=...))
+  (not in the reference) cv2.createCLAHE(clip, (g, g)).apply(Y) between cv2.cvtColor(COLOR_RGB2YCrCb / YCrCb2RGB)  (Cropper(clahe=...))
   retinaface.py:93-99  torchvision.models.resnet50() + _utils.IntermediateLayerGetter(layer2, layer3, layer4)
 Only data is stored (inputs, outputs, library versions): no third-party source.
 """
@@ -232,6 +235,41 @@ def make_matte(cv2):
     print("wrote opencv_matte.npz")
 
 
+def make_clahe(cv2):
+    """cv2.cvtColor(crop, COLOR_RGB2YCrCb), cv2.createCLAHE(clip, (g, g)).apply(Y) and cv2.cvtColor(..., COLOR_YCrCb2RGB) on
+    seeded crops for tests/test_clahe_pins.py: smooth and noisy content, sides that divide by the grid, that do not, and
+    one of each (OpenCV then pads the divisible side by a full grid), a single tile, 2 x 2 pixel tiles, and saturated
+    primaries over a ramp, whose way back to RGB clamps in both directions."""
+    rng = np.random.default_rng(800)
+
+    def smooth(h, w):
+        yy, xx = np.mgrid[0:h, 0:w]
+        img = np.zeros((h, w, 3))
+        for ch in range(3):
+            img[..., ch] = rng.uniform(40, 200)
+            for _ in range(4):
+                cy, cx, s = rng.uniform(0, h), rng.uniform(0, w), rng.uniform(3, max(h, w) / 2)
+                img[..., ch] += rng.uniform(-120, 120) * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * s * s))
+            img[..., ch] += rng.normal(0, rng.uniform(1, 12), (h, w))
+        return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+    colours = np.array([(255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 255, 0), (0, 255, 255), (255, 0, 255), (255, 255, 255), (0, 0, 0)])
+    primaries = ((colours[(np.arange(48) * 8) // 48][None] * 3 + (np.arange(40) * 255 // 39)[:, None, None]) // 4).astype(np.uint8)
+    cases = [(smooth(64, 64), 2.0, 8), (smooth(50, 37), 40.0, 8), (smooth(48, 37), 3.0, 8), (smooth(33, 31), 4.0, 1),
+             (smooth(32, 32), 2.0, 16), (rng.integers(0, 256, (96, 80, 3), dtype=np.uint8), 2.0, 8),
+             (np.full((64, 64, 3), 93, np.uint8), 0.5, 1), (primaries, 8.0, 4), (smooth(256, 256), 2.0, 8)]
+    out = describe_cv2(cv2)
+    for k, (crop, clip, grid) in enumerate(cases):
+        ycc = cv2.cvtColor(crop, cv2.COLOR_RGB2YCrCb)
+        y_eq = cv2.createCLAHE(clipLimit=clip, tileGridSize=(grid, grid)).apply(np.ascontiguousarray(ycc[..., 0]))
+        rgb = cv2.cvtColor(np.dstack([y_eq, ycc[..., 1], ycc[..., 2]]), cv2.COLOR_YCrCb2RGB)
+        out[f"clahe{k}_crop"], out[f"clahe{k}_clip"], out[f"clahe{k}_grid"] = crop, np.array(clip), np.array(grid)
+        out[f"clahe{k}_y"], out[f"clahe{k}_y_eq"], out[f"clahe{k}_rgb"] = ycc[..., 0], y_eq, rgb
+    out["clahe_cases"] = np.array(len(cases))
+    np.savez_compressed(os.path.join(GOLDEN, "opencv_clahe.npz"), **out)
+    print("wrote opencv_clahe.npz")
+
+
 def make_resnet():
     """retinaface.py:93-99 with the build's generated `body.*` weights: the three feature maps torchvision's own
     ResNet-50 + IntermediateLayerGetter return for one seeded 96x128 input."""
@@ -270,6 +308,7 @@ def main():
             make_interp(cv2)
             make_sharpness(cv2)
             make_matte(cv2)
+            make_clahe(cv2)
     if args.only != "cv2":
         try:
             import torchvision  # noqa: F401
