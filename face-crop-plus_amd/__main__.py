@@ -58,6 +58,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "every class but 0)")
     p.add_argument("-fe", "--feather", type=int, default=argparse.SUPPRESS,
                    help="soft edge of the background replacement in pixels: 0, 3, 5 or 7 (with --background; default 5)")
+    p.add_argument("-bb", "--background-blur", type=float, default=argparse.SUPPRESS,
+                   help="keep the background of the crops and blur it: sigma in output pixels, 0.5..16, of a Gaussian over "
+                        "the background pixels alone (not with --background; --foreground / --feather apply); by default "
+                        "the crops keep their background")
     p.add_argument("-cl", "--clahe", type=float, default=argparse.SUPPRESS,
                    help="equalise the contrast of the crops: clip limit (> 0, usually 2.0) of a contrast-limited adaptive "
                         "histogram equalisation of their luma; by default the crops keep their contrast")

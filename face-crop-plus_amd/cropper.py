@@ -59,6 +59,7 @@ class Cropper:
         background: int | tuple[int, int, int] | list[int] | None = None,
         foreground: list[int] | None = None,
         feather: int | None = None,
+        background_blur: float | None = None,
         clahe: float | None = None,
         clahe_grid: int | None = None,
         interpolation: str = "linear",
@@ -101,6 +102,14 @@ class Cropper:
         without ``attr_groups`` / ``mask_groups``, needs aligned crops like ``min_sharpness``, and ``foreground`` /
         ``feather`` without ``background`` raise ValueError.  None (the default) launches nothing.
         ``Cropper.matte`` applies it to crops and label maps one already has.
+        ``background_blur``: keep what is behind the subject and blur it — the sigma, in output pixels (0.5..16), of a
+        Gaussian over the background pixels alone, divided by the Gaussian weight of the background pixels it saw, so
+        that the subject's colours never leak into the background (a plain blur of the crop would show them as a halo
+        through the soft edge); the subject, ``foreground`` and ``feather`` are those of ``background`` and the
+        composite is the same, with the blurred background as the fill of every pixel (``matte.matte_blur``,
+        INTEGRATION.md section 2i).  It sits where ``background`` sits, cannot be combined with it (ValueError), creates
+        the parser and needs aligned crops like it; a face without a background pixel is written unchanged.  None (the
+        default) launches nothing.
         ``clahe``: equalise the contrast of every crop — the clip limit (finite, > 0; 2.0 is the usual value) of a
         contrast-limited adaptive histogram equalisation of the luma on a ``clahe_grid`` x ``clahe_grid`` tiling (1..16;
         None: 8), ``cv2.createCLAHE(clahe, (grid, grid)).apply(Y)`` between ``cv2.cvtColor(crop, COLOR_RGB2YCrCb)`` and
@@ -131,14 +140,19 @@ class Cropper:
             min_sharpness = float(min_sharpness)
         self.min_sharpness = min_sharpness
         self.background = matting.check_background(background)
-        if self.background is None:
+        self.background_blur = matting.check_blur(background_blur)
+        if self.background is not None and self.background_blur is not None:
+            raise ValueError("background and background_blur exclude each other: the background is filled or blurred")
+        self.blur_taps = None if self.background_blur is None else matting.blur_taps(self.background_blur)
+        if self.background is None and self.background_blur is None:
             if foreground is not None or feather is not None:
-                raise ValueError("foreground / feather need background: without it they would do nothing")
+                raise ValueError("foreground / feather need background or background_blur: without one they would do nothing")
             self.foreground, self.foreground_bits, self.feather = None, 0, None
         else:
             if det_threshold is None and landmarks is None:
-                raise ValueError("background needs aligned crops: it cannot be combined with det_threshold=None and "
-                                 "landmarks=None (no alignment), where the faces are the images themselves")
+                raise ValueError("background / background_blur need aligned crops: they cannot be combined with "
+                                 "det_threshold=None and landmarks=None (no alignment), where the faces are the images "
+                                 "themselves")
             self.foreground_bits = matting.check_foreground(foreground)
             self.foreground = tuple(c for c in range(matting.NUM_CLASSES) if self.foreground_bits >> c & 1)
             self.feather = matting.check_feather(feather)
@@ -234,7 +248,8 @@ class Cropper:
             from .rrdb import RRDBNet
             self.enh_model = RRDBNet(self.enh_threshold)
             self.enh_model.load(self.device, self.weights.get("rrdb"), self.precision)
-        if self.attr_groups is not None or self.mask_groups is not None or self.background is not None:
+        if (self.attr_groups is not None or self.mask_groups is not None or self.background is not None
+                or getattr(self, "background_blur", None) is not None):
             from .bise import BiSeNet
             self.par_model = BiSeNet(self.attr_groups, self.mask_groups, self.batch_size)
             self.par_model.load(self.device, self.weights.get("bisenet"), self.precision)
@@ -307,9 +322,10 @@ class Cropper:
     def matte(self, crops: np.ndarray, labels: np.ndarray):
         """What ``background`` does, for crops and label maps one already has: (F,H,W,3) uint8 RGB crops and (F,H,W)
         uint8 labels -> (the composited crops (F,H,W,3) uint8, the alpha (F,H,W) uint8), with this Cropper's
-        ``background`` / ``foreground`` / ``feather`` (``matte.matte``).  The alpha is what an RGBA file needs."""
-        if self.background is None:
-            raise ValueError("Cropper.matte needs a Cropper with background=...")
+        ``background`` / ``foreground`` / ``feather`` (``matte.matte``), or with its ``background_blur``
+        (``matte.matte_blur``).  The alpha is what an RGBA file needs."""
+        if self.background is None and self.background_blur is None:
+            raise ValueError("Cropper.matte needs a Cropper with background=... or background_blur=...")
         crops, labels = np.ascontiguousarray(crops), np.ascontiguousarray(labels)
         if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
             raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
@@ -318,8 +334,13 @@ class Cropper:
         if crops.size == 0:
             return np.zeros(crops.shape, np.uint8), np.zeros(labels.shape, np.uint8)
         with torch.cuda.device(self.device):
-            out, alpha = matting.matte(torch.from_numpy(crops).to(self.device), torch.from_numpy(labels).to(self.device),
-                                       self.foreground_bits, self.feather, self.background, with_alpha=True)
+            crops_dev, labels_dev = torch.from_numpy(crops).to(self.device), torch.from_numpy(labels).to(self.device)
+            if self.background_blur is not None:
+                out, alpha = matting.matte_blur(crops_dev, labels_dev, self.foreground_bits, self.feather, self.blur_taps,
+                                                with_alpha=True)
+            else:
+                out, alpha = matting.matte(crops_dev, labels_dev, self.foreground_bits, self.feather, self.background,
+                                           with_alpha=True)
             return out.cpu().numpy(), alpha.cpu().numpy()
 
     def equalize(self, crops: np.ndarray) -> np.ndarray:
@@ -568,7 +589,7 @@ class Cropper:
                 if faces_dev is None:
                     faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]
                 with trace.range("fcp:parse"):
-                    if self.background is not None and isinstance(faces_dev, torch.Tensor):
+                    if (self.background is not None or self.background_blur is not None) and isinstance(faces_dev, torch.Tensor):
                         # one parse per batch: the label map behind the groups is the one the matte uses
                         *groups, labels = self.par_model.predict(faces_dev, return_labels=True)
                         groups = tuple(groups)
@@ -581,7 +602,11 @@ class Cropper:
                         faces_dev = equalizing.clahe(faces_dev, self.clahe, self.clahe_grid)
                 if labels is not None:
                     with trace.range("fcp:matte"):
-                        faces_dev, _ = matting.matte(faces_dev, labels, self.foreground_bits, self.feather, self.background)
+                        if self.background_blur is not None:
+                            faces_dev, _ = matting.matte_blur(faces_dev, labels, self.foreground_bits, self.feather,
+                                                              self.blur_taps)
+                        else:
+                            faces_dev, _ = matting.matte(faces_dev, labels, self.foreground_bits, self.feather, self.background)
                 # the host copy, if the host encoder needs one, is the equalised / matted crop as well
                 faces = None if self.encoder == "device" else faces_dev.cpu().numpy()
             if self.encoder == "device" and isinstance(faces_dev, torch.Tensor):

@@ -1,0 +1,366 @@
+// Background blur of uint8 RGB crops from a per-pixel label map (Cropper(background_blur=...)):
+// what is behind the subject is kept and blurred, by a wide Gaussian over the BACKGROUND pixels only, divided by the
+// Gaussian weight of the background pixels it saw (a plain blur would smear the subject outward into a halo).
+//
+//   m(y,x)    = 255 if l(y,x) < 32 and bit l(y,x) of class_bits is set, else 0                  fcp_matte.hip's mask
+//   alpha     = the alpha of fcp_matte_u8 for this feather (0, 3, 5, 7; reflect-101; (sum + 32768) >> 16)
+//   b(y,x)    = 1 where m == 0, else 0                                                          from the HARD mask
+//   t[0..r]   : all >= 1, t[0] + 2 sum(t[1..r]) == 4096, 3 <= r <= 48; made on the host from sigma, data here
+//   D(y,x)    = sum_j sum_i t|j| t|i| b(y+j, x+i)                                               taps inside the image only
+//   N_ch(y,x) = sum_j sum_i t|j| t|i| b(y+j, x+i) c_ch(y+j, x+i)                                the same taps
+//   B_ch(y,x) = D > 0 ? (N_ch + D / 2) / D : c_ch(y,x)                                          integer division
+//   out_ch    = (c_ch alpha + B_ch (255 - alpha) + 127) / 255                                   fcp_matte.hip's over255
+//
+// Positions outside the image contribute to neither N nor D: the normalisation is the border rule.  Bounds, all in
+// unsigned 32 bits: a horizontal sum is at most 255 * 4096 < 2^20; N <= 255 * 4096^2 = 4 278 190 080 < 2^32 and
+// N + D / 2 <= 4 286 578 688 < 2^32, only just, which is why the entry point refuses taps that do not sum to 4096;
+// N <= 255 D, so B <= 255.  alpha < 255 needs a hard-background pixel within Chebyshev distance 3 inside the image
+// (reflect-101 revisits in-image pixels only), every tap is >= 1 and r >= 3, so D > 0 wherever B shows; the D == 0
+// branch only defines the bytes nobody sees.
+//
+// Two launches and a workspace of 16 bytes per pixel (the caller's: nothing is allocated here).
+//
+//   blur_rows_kernel, workgroups of 256 lanes over (4 rows x 256 columns, face).  A workgroup stages one dword per pixel
+//   of its rows and an r-pixel margin, (b, b c_r, b c_g, b c_b) as four bytes, zero for a subject pixel and for a
+//   position outside the image, so the border rule and the indicator cost nothing in the loop; then a lane per output
+//   pixel runs the 2 r + 1 taps over consecutive dwords (consecutive lanes, consecutive banks) and stores the four sums
+//   (H_b, H_r, H_g, H_b') as one 16-byte store.  LDS per workgroup: 4 x (256 + 96) x 4 B + 97 taps x 4 B = 6020 B (the
+//   tap table is mirrored to 2 r + 1 entries, so the loop has no |k|).  27 workgroups would fit the 160 KiB of a CU; the
+//   32 wave slots allow 8.
+//
+//   blur_cols_kernel, workgroups of 256 lanes over (64 rows x 16 columns, face), four pixels of a row per lane.  A
+//   workgroup stages the 16-byte sums of its columns for rows y0 - r .. y0 + 63 + r (zero outside the image), and the
+//   mask tile and its horizontal feather pass exactly as fcp_matte.hip does; then a lane runs the 2 r + 1 taps down its
+//   four columns (four 16-byte LDS reads per tap, 16 accumulators), divides, recomputes alpha, reads the 12 crop
+//   bytes of its group, composites and writes out (and alpha) once.  LDS per workgroup at r = 48 and feather 7:
+//   160 x 16 x 16 B = 40960 B of sums + 70 x 32 B + 70 x 24 B of feather + 388 B of taps = 45268 B: 3 workgroups per CU
+//   (160 KiB), 12 of 32 wave slots; at r = 24 (sigma 8) it is 28672 + 4308 B: 4 workgroups, the 5th misses by 1 KiB.
+//
+// Bytes per pixel, the floor of this form: the rows pass reads 4 (crop + label) and writes 16; the columns pass reads
+// 16 x (64 + 2 r) / 64 of sums (28 at r = 24, 40 at r = 48), 1.5 of labels and 3 of crop, and writes 3: 55.5 at r = 24,
+// 67.5 at r = 48, against the 7.3 of matte_kernel.  A single launch with a 2-D tile and a 48-pixel halo would move
+// fewer bytes to and from memory but read its input (64 + 96)^2 / 64^2 = 6.25 times and keep one workgroup per CU.
+//
+// out MAY BE crops: every read of c that a neighbour needs happens in blur_rows_kernel, which has finished before
+// blur_cols_kernel starts on the same stream; blur_cols_kernel reads c at its own pixels only (the centre of the
+// composite), and each group of four pixels has one lane that reads, then writes it.  No scratch copy of out is taken.
+// The result is the same from run to run: integer sums in a fixed order, one writer per byte.
+//
+// Rows are 3 w bytes and start at any byte.  The rows pass reads crop and label bytes as bytes.  The columns pass moves
+// crop, out and alpha bytes as fcp_matte.hip does: crops as the aligned dwords that hold at least one byte of the group,
+// out and alpha through dwords when the group is whole and aligned, through bytes otherwise.  No byte outside the
+// arrays is written, and no dword is read that does not hold a byte of them.
+#include "fcp_common.h"
+#include "fcp_hip.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMinRadius = 3;
+constexpr int kMaxRadius = 48;
+constexpr int kMaxSide = 8192;
+constexpr int kClasses = 19;
+constexpr uint32_t kTapSum = 4096;
+
+// rows pass
+constexpr int kRowTileW = 256;
+constexpr int kRowTileH = 4;
+constexpr int kRowPitch = kRowTileW + 2 * kMaxRadius;   // dwords of a staged row
+
+// columns pass
+constexpr int kTileW = 16;              // output pixels of a tile row: 4 groups of four
+constexpr int kTileH = 64;
+constexpr int kGroups = kTileW / 4;
+constexpr int kMaskPitch = kTileW + 8;  // bytes of a staged mask row: 16 + 2 * 3 halo, rounded up to dwords
+
+struct BlurTaps {
+  uint16_t t[kMaxRadius + 1];           // 49 x 16 bit in the kernel argument block
+};
+
+__host__ __device__ constexpr int tap(int r, int i) {   // fcp_matte.hip's feather taps
+  return r == 1 ? (i == 1 ? 128 : 64)
+       : r == 2 ? (i == 2 ? 96 : (i == 1 || i == 3) ? 64 : 16)
+                : (i == 3 ? 72 : (i == 2 || i == 4) ? 56 : (i == 1 || i == 5) ? 28 : 8);
+}
+
+// BORDER_REFLECT_101, iterated: the triangle wave of period 2 (n - 1); a dimension of size 1 maps everything to 0.
+__device__ __forceinline__ int reflect101(int p, int n) {
+  if (p >= 0 && p < n) return p;
+  if (n == 1) return 0;
+  const int period = 2 * (n - 1);
+  p %= period;
+  if (p < 0) p += period;
+  return p < n ? p : period - p;
+}
+
+__device__ __forceinline__ uint32_t mask_of(uint32_t label, uint32_t bits) {
+  return (label < 32u && ((bits >> (label & 31u)) & 1u)) ? 255u : 0u;
+}
+
+__device__ __forceinline__ bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+__device__ __forceinline__ uint32_t over255(uint32_t c, uint32_t a, uint32_t b) {
+  const uint32_t u = c * a + b * (255u - a) + 128u;
+  return (u + (u >> 8)) >> 8;
+}
+
+// the mirrored tap table, 2 r + 1 dwords: entry k is t|k - r|
+__device__ __forceinline__ void stage_taps(uint32_t* tl, const BlurTaps& taps, int radius) {
+  const int k = threadIdx.x;
+  if (k <= 2 * radius) tl[k] = taps.t[k < radius ? radius - k : k - radius];
+}
+
+__global__ void __launch_bounds__(kThreads) blur_rows_kernel(const uint8_t* __restrict__ crops, const uint8_t* __restrict__ labels,
+                                                             int h, int w, int tiles_x, uint32_t bits, BlurTaps taps, int radius,
+                                                             uint4* __restrict__ sums) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t* stage = reinterpret_cast<uint32_t*>(smem);   // kRowTileH rows of kRowPitch dwords
+  uint32_t* tl = stage + kRowTileH * kRowPitch;
+  const int f = blockIdx.y;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int x0 = tx * kRowTileW, y0 = ty * kRowTileH;
+  const int nrows = min(kRowTileH, h - y0), ncols = min(kRowTileW, w - x0);
+  const int span = ncols + 2 * radius;
+
+  stage_taps(tl, taps, radius);
+  for (int i = threadIdx.x; i < nrows * span; i += kThreads) {
+    const int tr = i / span, d = i - tr * span;
+    const int x = x0 - radius + d;
+    uint32_t v = 0;
+    if (x >= 0 && x < w) {
+      const size_t pixel = ((size_t)f * h + (y0 + tr)) * w + x;
+      if (mask_of(labels[pixel], bits) == 0u) {
+        const uint8_t* c = crops + pixel * 3;
+        v = 1u | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16) | ((uint32_t)c[2] << 24);
+      }
+    }
+    stage[tr * kRowPitch + d] = v;
+  }
+  __syncthreads();
+
+  for (int i = threadIdx.x; i < nrows * ncols; i += kThreads) {
+    const int tr = i / ncols, cx = i - tr * ncols;
+    const uint32_t* s = stage + tr * kRowPitch + cx;   // output x sums staged x .. x + 2 r
+    uint32_t a0 = 0u, a1 = 0u, a2 = 0u, a3 = 0u;        // each <= 255 * 4096
+    for (int k = 0; k <= 2 * radius; ++k) {
+      const uint32_t v = s[k], t = tl[k];
+      a0 += t * (v & 255u);
+      a1 += t * ((v >> 8) & 255u);
+      a2 += t * ((v >> 16) & 255u);
+      a3 += t * (v >> 24);
+    }
+    sums[((size_t)f * h + (y0 + tr)) * w + (x0 + cx)] = make_uint4(a0, a1, a2, a3);
+  }
+}
+
+// Bytes of dynamic LDS of blur_cols_kernel<R>: the sums, the feather's H rows and mask rows, the taps.
+template <int R>
+constexpr size_t cols_lds_bytes(int radius) {
+  return (size_t)(kTileH + 2 * radius) * kTileW * sizeof(uint4) +
+         (R > 0 ? (size_t)(kTileH + 2 * R) * (kGroups * sizeof(uint2) + kMaskPitch) : 0) +
+         (2 * kMaxRadius + 1) * sizeof(uint32_t);
+}
+
+// crops and out may be the same array: neither is __restrict__.
+template <int R>
+__global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crops, const uint8_t* __restrict__ labels,
+                                                             const uint4* __restrict__ sums, int h, int w, int tiles_x,
+                                                             uint32_t bits, BlurTaps taps, int radius, uint8_t* out,
+                                                             uint8_t* alpha) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint4* col = reinterpret_cast<uint4*>(smem);                                    // (kTileH + 2 r) rows of kTileW sums
+  uint2* hsum = reinterpret_cast<uint2*>(col + (kTileH + 2 * radius) * kTileW);   // R > 0: H rows, 8 bytes per group
+  uint32_t* mask32 = reinterpret_cast<uint32_t*>(hsum + (R > 0 ? (kTileH + 2 * R) * kGroups : 0));
+  uint32_t* tl = mask32 + (R > 0 ? (kTileH + 2 * R) * (kMaskPitch / 4) : 0);
+  const int f = blockIdx.y;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int x0 = tx * kTileW, y0 = ty * kTileH;
+  const int nrows = min(kTileH, h - y0);
+  const int groups = (min(kTileW, w - x0) + 3) >> 2;
+  const uint8_t* lab = labels + (size_t)f * h * w;
+
+  stage_taps(tl, taps, radius);
+  // sums of rows y0 - r .. y0 + nrows + r - 1, all kTileW columns: zero outside the image
+  for (int i = threadIdx.x; i < (nrows + 2 * radius) * kTileW; i += kThreads) {
+    const int tr = i / kTileW, c = i - tr * kTileW;
+    const int y = y0 - radius + tr, x = x0 + c;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (y >= 0 && y < h && x < w) v = sums[((size_t)f * h + y) * w + x];
+    col[i] = v;
+  }
+  if constexpr (R > 0) {
+    // fcp_matte.hip: mask bytes of rows y0 - R .. y0 + nrows + R - 1, columns x0 - R .. x0 + 4 groups + R - 1
+    const int mdw = (4 * groups + 2 * R + 3) >> 2;
+    for (int i = threadIdx.x; i < (nrows + 2 * R) * mdw; i += kThreads) {
+      const int tr = i / mdw, d = i - tr * mdw;
+      const uint8_t* row = lab + (size_t)reflect101(y0 - R + tr, h) * w;
+      uint32_t v = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v |= mask_of(row[reflect101(x0 - R + 4 * d + j, w)], bits) << (8 * j);
+      mask32[tr * (kMaskPitch / 4) + d] = v;
+    }
+    __syncthreads();
+    // H of the same rows: output x of the tile sums mask bytes x .. x + 2 R
+    for (int i = threadIdx.x; i < (nrows + 2 * R) * groups; i += kThreads) {
+      const int tr = i / groups, g = i - tr * groups;
+      const uint32_t* m = mask32 + tr * (kMaskPitch / 4) + g;
+      const uint32_t d[3] = {m[0], m[1], R == 3 ? m[2] : 0u};
+      uint32_t s[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int t = 0; t <= 2 * R; ++t) s[j] += (uint32_t)tap(R, t) * ((d[(j + t) >> 2] >> (8 * ((j + t) & 3))) & 255u);
+      }
+      hsum[tr * kGroups + g] = make_uint2(s[0] | (s[1] << 16), s[2] | (s[3] << 16));
+    }
+  }
+  __syncthreads();
+
+  for (int i = threadIdx.x; i < nrows * groups; i += kThreads) {
+    const int r = i / groups, g = i - r * groups;
+    const int y = y0 + r, x = x0 + 4 * g;
+    const int npx = min(4, w - x);
+    const size_t pixel = ((size_t)f * h + y) * w + x;
+
+    // D and N of the four pixels: N + D / 2 < 2^32
+    uint32_t dn[4][4] = {};
+    for (int k = 0; k <= 2 * radius; ++k) {
+      const uint32_t t = tl[k];
+      const uint4* p = col + (r + k) * kTileW + 4 * g;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint4 v = p[j];
+        dn[j][0] += t * v.x;
+        dn[j][1] += t * v.y;
+        dn[j][2] += t * v.z;
+        dn[j][3] += t * v.w;
+      }
+    }
+
+    uint32_t a[4];
+    if constexpr (R > 0) {
+      uint32_t s[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int t = 0; t <= 2 * R; ++t) {
+        const uint2 v = hsum[(r + t) * kGroups + g];
+        s[0] += (uint32_t)tap(R, t) * (v.x & 0xffffu);
+        s[1] += (uint32_t)tap(R, t) * (v.x >> 16);
+        s[2] += (uint32_t)tap(R, t) * (v.y & 0xffffu);
+        s[3] += (uint32_t)tap(R, t) * (v.y >> 16);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[j] = (s[j] + 32768u) >> 16;
+    } else {
+      const uint8_t* lp = labels + pixel;
+      if (npx == 4 && aligned4(lp)) {
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(lp);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = mask_of((v >> (8 * j)) & 255u, bits);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = j < npx ? mask_of(lp[j], bits) : 0u;
+      }
+    }
+    if (alpha != nullptr) {
+      uint8_t* ap = alpha + pixel;
+      if (npx == 4 && aligned4(ap)) {
+        *reinterpret_cast<uint32_t*>(ap) = a[0] | (a[1] << 8) | (a[2] << 16) | (a[3] << 24);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < npx) ap[j] = (uint8_t)a[j];
+      }
+    }
+
+    // the 3 * npx crop bytes of the group, from the aligned dwords that hold them (every dword read holds at least one)
+    const uint8_t* cp = crops + pixel * 3;
+    const int skew = (int)(reinterpret_cast<uintptr_t>(cp) & 3), nbytes = skew + 3 * npx;
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(cp - skew);
+    const uint32_t d0 = p[0];
+    const uint32_t d1 = nbytes > 4 ? p[1] : 0u;
+    const uint32_t d2 = nbytes > 8 ? p[2] : 0u;
+    const uint32_t d3 = nbytes > 12 ? p[3] : 0u;
+    const int sh = 8 * skew;
+    const uint32_t c[3] = {(uint32_t)((((uint64_t)d1 << 32) | d0) >> sh), (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh),
+                           (uint32_t)((((uint64_t)d3 << 32) | d2) >> sh)};
+    uint32_t o[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {            // byte k of the group: pixel k / 3, channel k % 3
+      const uint32_t cv = (c[k >> 2] >> (8 * (k & 3))) & 255u;
+      const uint32_t dd = dn[k / 3][0];
+      const uint32_t bv = dd > 0u ? (dn[k / 3][1 + k % 3] + (dd >> 1)) / dd : cv;
+      o[k >> 2] |= over255(cv, a[k / 3], bv) << (8 * (k & 3));
+    }
+    uint8_t* op = out + pixel * 3;
+    if (npx == 4 && aligned4(op)) {
+      uint32_t* q = reinterpret_cast<uint32_t*>(op);
+      q[0] = o[0];
+      q[1] = o[1];
+      q[2] = o[2];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 12; ++k)
+        if (k < 3 * npx) op[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
+    }
+  }
+}
+
+template <int R>
+void launch_cols(const uint8_t* crops, const uint8_t* labels, const uint4* sums, int f, int h, int w, uint32_t bits,
+                 const BlurTaps& taps, int radius, uint8_t* out, uint8_t* alpha, hipStream_t stream) {
+  const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
+  hipLaunchKernelGGL(blur_cols_kernel<R>, dim3(tiles_x * tiles_y, f), dim3(kThreads), cols_lds_bytes<R>(radius), stream, crops,
+                     labels, sums, h, w, tiles_x, bits, taps, radius, out, alpha);
+}
+
+}  // namespace
+
+extern "C" int64_t fcp_matte_blur_workspace_bytes(int f, int h, int w) {
+  if (f < 0 || f > 65535 || h < 1 || w < 1 || h > kMaxSide || w > kMaxSide) return -1;
+  return (int64_t)f * h * w * (int64_t)sizeof(uint4);
+}
+
+extern "C" int fcp_matte_blur_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits,
+                                 int feather, const uint16_t* taps, int radius, uint8_t* out, uint8_t* alpha, void* workspace,
+                                 int64_t workspace_bytes, fcp_stream_t stream) {
+  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "matte_blur: bad sizes (f %d, h %d, w %d)", f, h, w);
+  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "matte_blur: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h,
+              w);
+  FCP_REQUIRE(f <= 65535, "matte_blur: at most 65535 crops per call (got %d)", f);
+  FCP_REQUIRE(feather == 0 || feather == 3 || feather == 5 || feather == 7, "matte_blur: feather must be 0, 3, 5 or 7 (got %d)",
+              feather);
+  FCP_REQUIRE((class_bits >> kClasses) == 0, "matte_blur: class_bits 0x%x names a class at or above %d", class_bits, kClasses);
+  FCP_REQUIRE(radius >= kMinRadius && radius <= kMaxRadius, "matte_blur: radius must be %d..%d (got %d)", kMinRadius, kMaxRadius,
+              radius);
+  FCP_REQUIRE(taps != nullptr, "matte_blur: null taps");
+  // the 32-bit sums of the kernels hold because of this
+  BlurTaps t = {};
+  uint32_t total = 0;
+  for (int k = 0; k <= radius; ++k) {
+    FCP_REQUIRE(taps[k] >= 1, "matte_blur: tap %d is 0: every tap must be at least 1", k);
+    t.t[k] = taps[k];
+    total += (k == 0 ? 1u : 2u) * taps[k];
+  }
+  FCP_REQUIRE(total == kTapSum, "matte_blur: the taps must sum to %u over the window (got %u)", kTapSum, total);
+  if (f == 0) return 0;
+  FCP_REQUIRE(crops && labels && out, "matte_blur: null pointer");
+  const int64_t need = fcp_matte_blur_workspace_bytes(f, h, w);
+  FCP_REQUIRE(workspace != nullptr && workspace_bytes >= need, "matte_blur: the workspace needs %lld bytes (got %lld)",
+              (long long)need, (long long)workspace_bytes);
+  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "matte_blur: the workspace must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  uint4* sums = static_cast<uint4*>(workspace);
+  const int row_tiles_x = fcp_cdiv(w, kRowTileW), row_tiles_y = fcp_cdiv(h, kRowTileH);
+  hipLaunchKernelGGL(blur_rows_kernel, dim3(row_tiles_x * row_tiles_y, f), dim3(kThreads),
+                     (kRowTileH * kRowPitch + 2 * kMaxRadius + 1) * sizeof(uint32_t), s, crops, labels, h, w, row_tiles_x,
+                     class_bits, t, radius, sums);
+  FCP_LAUNCH_OK();
+  switch (feather) {
+    case 0: launch_cols<0>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+    case 3: launch_cols<1>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+    case 5: launch_cols<2>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+    default: launch_cols<3>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+  }
+  FCP_LAUNCH_OK();
+  return 0;
+}

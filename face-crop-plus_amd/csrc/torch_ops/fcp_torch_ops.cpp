@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / matte / clahe
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / matte / clahe / matte_blur
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -439,6 +439,39 @@ std::tuple<Tensor, Tensor> matte(const Tensor& crops, const Tensor& labels, int6
   return {out, alpha};
 }
 
+// Crops (f,h,w,3) uint8 over their own mask-normalised background blur through the soft mask of their label maps
+// (f,h,w) uint8: the composited crops and, with `with_alpha`, the alpha (f,h,w) uint8 (else an empty tensor)
+// (fcp_matte_blur_u8).  taps = t[0..radius] as integers; the 16-bytes-per-pixel workspace lives for the call.
+std::tuple<Tensor, Tensor> matte_blur(const Tensor& crops, const Tensor& labels, int64_t class_bits, int64_t feather,
+                                      at::IntArrayRef taps, bool with_alpha) {
+  dev(crops, "crops", at::kByte);
+  dev(labels, "labels", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
+  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
+  TORCH_CHECK(labels.get_device() == crops.get_device() && labels.dim() == 3 && labels.size(0) == f && labels.size(1) == h &&
+                  labels.size(2) == w, "labels must be (", f, ",", h, ",", w, ") uint8 on the device of the crops");
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  TORCH_CHECK(feather >= INT_MIN && feather <= INT_MAX, "feather past int");
+  const int64_t radius = (int64_t)taps.size() - 1;
+  TORCH_CHECK(radius >= 3 && radius <= 48, "matte_blur: taps must be t[0..radius] with radius 3..48 (got ", taps.size(), " taps)");
+  uint16_t t16[49];
+  for (int64_t k = 0; k <= radius; ++k) {
+    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, "matte_blur: tap ", k, " past 16 bits");
+    t16[k] = (uint16_t)taps[k];
+  }
+  Tensor out = at::empty_like(crops);
+  Tensor alpha = with_alpha ? at::empty({f, h, w}, crops.options()) : at::empty({0}, crops.options());
+  const int64_t need = fcp_matte_blur_workspace_bytes((int)f, (int)h, (int)w);
+  Tensor work = at::empty({need < 0 ? 0 : need}, crops.options());
+  ok(fcp_matte_blur_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits,
+                       (int)feather, t16, (int)radius, out.data_ptr<uint8_t>(), with_alpha ? alpha.data_ptr<uint8_t>() : nullptr,
+                       work.data_ptr(), work.numel(), cur_stream()),
+     "fcp::matte_blur");
+  return {out, alpha};
+}
+
 // Crops (f,h,w,3) uint8 with the luma equalised by CLAHE on a grid x grid tiling (fcp_clahe_u8); the LUT workspace
 // lives for the call.
 Tensor clahe(const Tensor& crops, int64_t grid, double clip_limit) {
@@ -519,6 +552,7 @@ TORCH_LIBRARY(fcp, m) {
   m.def("matte(Tensor crops, Tensor labels, int class_bits, int feather, int bg_r, int bg_g, int bg_b, bool with_alpha) "
         "-> (Tensor, Tensor)");
   m.def("clahe(Tensor crops, int grid, float clip_limit) -> Tensor");
+  m.def("matte_blur(Tensor crops, Tensor labels, int class_bits, int feather, int[] taps, bool with_alpha) -> (Tensor, Tensor)");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -546,6 +580,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("jpeg_encode", &jpeg_encode);
   m.impl("matte", &matte);
   m.impl("clahe", &clahe);
+  m.impl("matte_blur", &matte_blur);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

@@ -6,8 +6,16 @@ are on the device already (``fcp_matte_u8`` / ``torch.ops.fcp.matte``).
     alpha = m (feather 0), or cv2.GaussianBlur(m, (feather, feather), 0) restated: the 8.8 fixed-point taps of ksize 3,
             5 or 7, two passes, one rounding ``(sum + 32768) >> 16``, BORDER_REFLECT_101
     out   = (crop * alpha + fill * (255 - alpha) + 127) // 255
+
+``Cropper(background_blur=sigma)`` (section 2i) keeps the background and blurs it instead: the fill of a pixel becomes
+
+    B     = (N + D // 2) // D,  N and D the Gaussian window sums of the BACKGROUND pixels' colours and of their count
+            (``fcp_matte_blur_u8`` / ``torch.ops.fcp.matte_blur``, two launches), with integer taps made here from sigma
 """
 from __future__ import annotations
+
+import ctypes
+import math
 
 import numpy as np
 import torch
@@ -18,6 +26,9 @@ from . import torch_ops as T
 FEATHERS = (0, 3, 5, 7)
 DEFAULT_FEATHER = 5
 NUM_CLASSES = 19            # bise.NUM_CLASSES: the label maps are BiSeNet's
+MIN_SIGMA, MAX_SIGMA = 0.5, 16.0
+MIN_RADIUS, MAX_RADIUS = 3, 48
+TAP_SUM = 4096
 
 
 def _is_int(v) -> bool:
@@ -62,6 +73,57 @@ def check_feather(feather) -> int:
     if not _is_int(feather) or int(feather) not in FEATHERS:
         raise ValueError(f"feather must be one of {FEATHERS} or None, not {feather!r}")
     return int(feather)
+
+
+def check_blur(sigma):
+    """``background_blur`` of the Cropper -> None (off) or sigma in output pixels as a float: finite, 0.5..16."""
+    if sigma is None:
+        return None
+    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(sigma) or not MIN_SIGMA <= sigma <= MAX_SIGMA:
+        raise ValueError(f"background_blur must be None or a finite sigma in [{MIN_SIGMA}, {MAX_SIGMA}] pixels, not {sigma!r}")
+    return float(sigma)
+
+
+def blur_taps(sigma) -> list:
+    """sigma -> the integer taps t[0..r] of the background blur, in float64: r = min(48, max(3, ceil(3 sigma))),
+    g_k = exp(-k^2 / (2 sigma^2)), s = g_0 + 2 sum g_k, t_k = max(1, floor(4096 g_k / s)) for k >= 1 and t_0 the rest of
+    4096.  Every tap is >= 1, they do not grow with k, and the window sums to 4096: the kernel's 32-bit bounds."""
+    sigma = check_blur(sigma)
+    if sigma is None:
+        raise ValueError("blur_taps needs a sigma")
+    r = min(MAX_RADIUS, max(MIN_RADIUS, math.ceil(3 * sigma)))
+    g = [math.exp(-k * k / (2 * sigma * sigma)) for k in range(r + 1)]
+    s = g[0] + 2 * sum(g[1:])
+    t = [0] + [max(1, math.floor(TAP_SUM * g[k] / s)) for k in range(1, r + 1)]
+    t[0] = TAP_SUM - 2 * sum(t[1:])
+    assert all(t[k] >= t[k + 1] for k in range(r)) and t[r] >= 1, t
+    return t
+
+
+def matte_blur(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, feather: int, taps, with_alpha: bool = False):
+    """crops (F,H,W,3) u8 and labels (F,H,W) u8, device -> (out (F,H,W,3) u8, alpha (F,H,W) u8 or None), device: the
+    crops over their own mask-normalised background blur with the taps t[0..r] of ``blur_taps``.  Two launches and a
+    workspace of 16 bytes per pixel that lives for the call; H, W <= 8192."""
+    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
+    assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and tuple(labels_dev.shape) == tuple(crops_dev.shape[:3])
+    taps = [int(t) for t in taps]
+    if T.ENABLED:
+        out, alpha = T.load().matte_blur(crops_dev, labels_dev, int(class_bits), int(feather), taps, bool(with_alpha))
+        return out, (alpha if with_alpha else None)
+    if not MIN_RADIUS + 1 <= len(taps) <= MAX_RADIUS + 1 or min(taps) < 0 or max(taps) > 65535:
+        raise RuntimeError(f"fcp_matte_blur_u8: taps must be t[0..radius] with radius {MIN_RADIUS}..{MAX_RADIUS}, each 16 bits "
+                           f"(got {len(taps)} taps)")
+    f, h, w, _ = crops_dev.shape
+    out = torch.empty_like(crops_dev)
+    alpha = torch.empty((f, h, w), dtype=torch.uint8, device=crops_dev.device) if with_alpha else None
+    need = max(int(N.lib().fcp_matte_blur_workspace_bytes(f, h, w)), 0)
+    work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
+    t16 = (ctypes.c_uint16 * len(taps))(*taps)
+    N.check(N.lib().fcp_matte_blur_u8(N.ptr(crops_dev), N.ptr(labels_dev), f, h, w, int(class_bits), int(feather), t16,
+                                      len(taps) - 1, N.ptr(out), N.ptr(alpha), N.ptr(work), need, N.stream_ptr()),
+            "fcp_matte_blur_u8")
+    return out, alpha
 
 
 def matte(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, feather: int, fill, with_alpha: bool = False):

@@ -484,6 +484,42 @@ int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int channels, 
 int fcp_matte_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather,
                  int bg_r, int bg_g, int bg_b, uint8_t* out, uint8_t* alpha, fcp_stream_t stream);
 
+/* Background blur of crops (f,h,w,3) uint8 RGB from label maps (f,h,w)
+ * uint8, in integers throughout: the subject keeps the
+ * crop, what is behind it becomes a mask-normalised Gaussian of the
+ * background pixels alone.  m and alpha are exactly those of fcp_matte_u8
+ * for class_bits and feather; b = 1 where m == 0, else 0;
+ *   taps  = t[0..radius] on the HOST, each >= 1, t[0] + 2 sum(t[1..radius])
+ *           == 4096, 3 <= radius <= 48 (matte.blur_taps makes them from a
+ *           sigma; they travel in the kernel argument block);
+ *   D     = sum_j sum_i t|j| t|i| b(y+j, x+i) over the positions inside the
+ *           image, N_ch the same sum of b c_ch;
+ *   B_ch  = D > 0 ? (N_ch + D / 2) / D : c_ch        (integer division)
+ *   out   = (c * alpha + B * (255 - alpha) + 127) / 255 per channel.
+ * All sums are unsigned 32 bits: N + D / 2 <= 4 286 578 688 < 2^32, which
+ * is why taps that do not sum to 4096 are refused.  Wherever alpha < 255,
+ * D > 0.
+ * workspace: fcp_matte_blur_workspace_bytes(f,h,w) = 16 f h w bytes of
+ * device memory, 16-byte aligned, contents irrelevant (the four horizontal
+ * sums of every pixel); it must not overlap the other arrays.
+ * out (f,h,w,3) and alpha (f,h,w) are written once, by ordinary stores;
+ * alpha may be NULL.  out MAY BE crops (in place): the first launch reads
+ * every crop byte a neighbour needs into the workspace, the second reads a
+ * crop pixel only where it writes it.  labels must not overlap out or
+ * alpha.  crops, labels, out and alpha may start at any byte; nothing
+ * outside them is written.  Two launches on `stream`, nothing allocated,
+ * the same bytes from run to run.
+ * f == 0 is a no-op; f < 0, h or w < 1 or > 8192, f > 65535, a feather other
+ * than 0 / 3 / 5 / 7, a radius outside 3..48, a bit of class_bits at or above
+ * 19, null taps, a tap of 0, taps that do not sum to 4096, or (f > 0) a null
+ * crops / labels / out, a workspace that is null, too small or misaligned
+ * fail with a message, before any HIP call
+ * (fcp_matte_blur_workspace_bytes then returns -1). */
+int64_t fcp_matte_blur_workspace_bytes(int f, int h, int w);
+int fcp_matte_blur_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather,
+                      const uint16_t* taps, int radius, uint8_t* out, uint8_t* alpha, void* workspace, int64_t workspace_bytes,
+                      fcp_stream_t stream);
+
 /* Contrast-limited adaptive histogram equalisation of the luma of crops
  * (f,h,w,3) uint8 RGB: cv2.createCLAHE(clip_limit,
  * (grid, grid)).apply(Y) between cv2.cvtColor(COLOR_RGB2YCrCb) and
