@@ -67,6 +67,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "histogram equalisation of their luma; by default the crops keep their contrast")
     p.add_argument("-cg", "--clahe-grid", type=int, default=argparse.SUPPRESS,
                    help="tiles per side of the equalisation, 1..16 (with --clahe; default 8)")
+    p.add_argument("-jq", "--jpeg-quality", type=int, default=argparse.SUPPRESS,
+                   help="quality of the JPEG files written, 1..100 (default 95, cv2.imwrite's)")
+    p.add_argument("-jss", "--jpeg-subsampling", type=str, default=argparse.SUPPRESS, choices=("4:4:4", "4:2:2", "4:2:0"),
+                   help="chroma subsampling of the JPEG files written (default '4:2:0'; '4:4:4' keeps the colour at full "
+                        "resolution)")
+    p.add_argument("-jo", "--jpeg-optimize", action="store_true", default=argparse.SUPPRESS,
+                   help="give every JPEG file Huffman tables of its own: smaller files, the same pixels")
     return p
 
 

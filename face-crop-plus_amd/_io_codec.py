@@ -4,7 +4,9 @@ import only this module.  ``utils.py`` re-exports ``read_image`` / ``write_image
 from __future__ import annotations
 
 import os
+import threading
 import warnings
+from typing import NamedTuple
 
 import numpy as np
 
@@ -43,15 +45,79 @@ _NOT_CV2_FORMATS = {"GIF", "PDF", "ICO", "ICNS", "PALM", "MPO", "XBM", "IM", "MS
                     "BLP", "BUFR", "GRIB", "HDF5", "DIB", "APNG"}   # Pillow writes them, cv2.imwrite refuses: skipped like there
 
 
-def write_image(path: str, image: np.ndarray) -> bool:
+JPEG_SUBSAMPLINGS = ("4:4:4", "4:2:2", "4:2:0")     # index = the `subsampling` argument of the device encoder
+
+
+class JpegSettings(NamedTuple):
+    """``Cropper(jpeg_quality=, jpeg_subsampling=, jpeg_optimize=)`` as it travels to the writers (picklable)."""
+    quality: int = 95
+    subsampling: str = "4:2:0"
+    optimize: bool = False
+
+
+def check_jpeg_settings(quality, subsampling, optimize) -> JpegSettings:
+    """The three settings, validated: an int 1..100 (no bool, no float), one of the three strings, a bool."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not (1 <= int(quality) <= 100):
+        raise ValueError(f"jpeg_quality must be an int in 1..100, not {quality!r}")
+    if not isinstance(subsampling, str) or subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"unknown jpeg_subsampling {subsampling!r}: choose '4:4:4', '4:2:2' or '4:2:0'")
+    if not isinstance(optimize, (bool, np.bool_)):
+        raise ValueError(f"jpeg_optimize must be True or False, not {optimize!r}")
+    return JpegSettings(int(quality), subsampling, bool(optimize))
+
+
+_MAXBLOCK_LOCK = threading.Lock()
+
+
+def jpeg_worst_case_bytes(h: int, w: int) -> int:
+    """No JPEG file of an h x w image written here is longer: a block costs at most 27 + 63 * 26 = 1665 bits, 417 bytes
+    after FF -> FF 00 stuffing; there are at most 12 blocks per 16 x 16 pixels (4:4:4, or 4:2:0's MCUs with their dummy
+    blocks, rounded up to whole MCUs); the header with four full Huffman tables stays below 2048 bytes."""
+    return 2048 + 417 * 12 * ((h + 15) // 16) * ((w + 15) // 16)
+
+
+def save_jpeg(image: np.ndarray, target, kw: dict):
+    """``Image.fromarray(image).save(target, **kw)`` for a JPEG.  With ``optimize`` libjpeg writes the whole file into
+    ONE buffer, which Pillow sizes at w * h bytes (2 w h from quality 95) or ``ImageFile.MAXBLOCK``, whichever is larger;
+    a file longer than that (noise at 4:4:4 is) fails with "broken data stream" (libjpeg: "Suspension not allowed
+    here").  So MAXBLOCK is raised to the worst case of this image for the duration of the save, and restored."""
+    from PIL import Image, ImageFile
+    im = Image.fromarray(image)
+    if not kw.get("optimize"):
+        im.save(target, **kw)
+        return
+    with _MAXBLOCK_LOCK:                             # the I/O threads of the inline path share the module attribute
+        old = ImageFile.MAXBLOCK
+        ImageFile.MAXBLOCK = max(old, jpeg_worst_case_bytes(image.shape[0], image.shape[1]))
+        try:
+            im.save(target, **kw)
+        finally:
+            ImageFile.MAXBLOCK = old
+
+
+def jpeg_kw(jpeg: JpegSettings | None = None, ext: str = ".jpg") -> dict:
+    """Pillow's keywords of a JPEG file: the table entry, overridden by ``jpeg``."""
+    kw = _ENCODER_KW[ext]
+    if jpeg is None:
+        return kw
+    quality, subsampling, optimize = jpeg
+    return dict(kw, quality=int(quality), subsampling=subsampling, optimize=bool(optimize))
+
+
+def write_image(path: str, image: np.ndarray, jpeg: JpegSettings | None = None) -> bool:
     """RGB (or single-channel mask) uint8 array -> file; format from the extension, ``cv2.imwrite`` defaults for the
     formats listed above, Pillow's own choice of encoder for every other extension it knows (.ppm / .pgm / .pnm /
     .jp2 / ... — ``cv2.imwrite`` writes these too).  Only an extension NO encoder exists for warns and returns False
-    (the file is skipped) instead of raising."""
+    (the file is skipped) instead of raising.  ``jpeg`` (quality, subsampling, optimize) overrides the table entry of
+    the three JPEG extensions and touches no other format."""
     from PIL import Image
-    kw = _ENCODER_KW.get(os.path.splitext(path)[1].lower())
+    ext = os.path.splitext(path)[1].lower()
+    kw = _ENCODER_KW.get(ext)
     if kw is not None:
-        Image.fromarray(image).save(path, **kw)
+        if jpeg is not None and kw.get("format") == "JPEG":
+            save_jpeg(image, path, jpeg_kw(jpeg, ext))
+        else:
+            Image.fromarray(image).save(path, **kw)
         return True
     ext = os.path.splitext(path)[1].lower()
     Image.init()                                    # fill Pillow's extension -> encoder registry

@@ -13,7 +13,8 @@ CPU-heavy part runs outside the parent's interpreter:
   A worker NEVER waits for ring space — an image that does not fit right now travels through the socket instead — so a
   ring that is too small for a batch of 4K frames costs speed, not progress.
 * write: the parent sends the crop's bytes through the socket (a syscall, GIL released), the worker encodes with
-  ``_io_codec.write_image`` (same encoder table, same warn-and-skip) and replies.
+  ``_io_codec.write_image`` (same encoder table, same warn-and-skip; the JPEG settings of the Cropper, if it has any of
+  its own, travel in the request) and replies.
 
 Workers are fresh interpreters (``python -m face_crop_plus_amd._io_pool`` with the ring / control / socket descriptors
 passed explicitly): they import numpy + Pillow only.  They are deliberately NOT forked from the parent: a fork of a
@@ -76,9 +77,9 @@ def _serve(conn, ring, ring_bytes: int, ctl, slot: int):
                     for img in through_socket:
                         conn.send_bytes(memoryview(np.ascontiguousarray(img)).cast("B"))
                 elif kind == "write":
-                    _, path, shape = msg
+                    _, path, shape, jpeg = msg              # jpeg: None, or (quality, subsampling, optimize)
                     pixels = np.frombuffer(conn.recv_bytes(), dtype=np.uint8).reshape(shape)
-                    ok = write_image(path, pixels)
+                    ok = write_image(path, pixels, jpeg)
                     conn.send(("done", bool(ok), [str(w.message) for w in caught]))
                 elif kind == "bytes":                       # a file encoded elsewhere (on the GPU): only written here
                     ok = write_bytes(msg[1], conn.recv_bytes())
@@ -193,9 +194,9 @@ class _Worker:
                 self.given_back += self.regions.pop(first)[0]
             self.ctl[self.slot] = self.given_back    # one aligned 8-byte store: the worker only ever reads it
 
-    def write(self, path, pixels: np.ndarray) -> bool:
+    def write(self, path, pixels: np.ndarray, jpeg=None) -> bool:
         pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
-        self._io(self.conn.send, ("write", path, pixels.shape))
+        self._io(self.conn.send, ("write", path, pixels.shape, None if jpeg is None else tuple(jpeg)))
         self._io(self.conn.send_bytes, memoryview(pixels).cast("B"))
         rep = self._reply()
         for note in rep[2]:
@@ -302,8 +303,8 @@ class IOProcesses:
     def read_many(self, paths):
         return self._mine("r", self._free_r).read_many(paths)
 
-    def write(self, path, pixels):
-        return self._mine("w", self._free_w).write(path, pixels)
+    def write(self, path, pixels, jpeg=None):
+        return self._mine("w", self._free_w).write(path, pixels, jpeg)
 
     def write_bytes(self, path, data):
         return self._mine("w", self._free_w).write_bytes(path, data)

@@ -18,7 +18,7 @@ import torch
 from . import align, trace
 from . import clahe as equalizing
 from . import matte as matting
-from ._io_codec import write_bytes
+from ._io_codec import JpegSettings, check_jpeg_settings, write_bytes
 from .batch import batch_geometry, build_batch, upload_sources
 from .utils import get_ldm_slices, parse_landmarks_file, read_image, read_images, write_image
 
@@ -56,6 +56,9 @@ class Cropper:
         warp_family: str | None = None,
         crop_source: str = "batch",
         encoder: str = "host",
+        jpeg_quality: int = 95,
+        jpeg_subsampling: str = "4:2:0",
+        jpeg_optimize: bool = False,
         background: int | tuple[int, int, int] | list[int] | None = None,
         foreground: list[int] | None = None,
         feather: int | None = None,
@@ -118,10 +121,19 @@ class Cropper:
         stays exact) and the encoder; the histograms are over the whole crop and mask files are unchanged.  It needs
         aligned crops like ``min_sharpness`` and an ``output_size`` of at least ``2 * clahe_grid`` on both sides;
         ``clahe_grid`` without ``clahe`` raises ValueError.  None (the default) launches nothing.
-        ``Cropper.equalize`` applies it to crops one already has."""
+        ``Cropper.equalize`` applies it to crops one already has.
+        ``jpeg_quality`` (an int, 1..100; 95), ``jpeg_subsampling`` ("4:4:4", "4:2:2" or "4:2:0"; "4:2:0") and
+        ``jpeg_optimize`` (per-file Huffman tables, Pillow's ``optimize=True``: smaller files, the same pixels; False):
+        the settings of every JPEG file (.jpg / .jpeg / .jpe) this Cropper writes — aligned crops, the mask files of
+        ``mask_groups``, the images of "no alignment" — through either encoder, which still write the same bytes
+        (INTEGRATION.md section 2j); other formats are untouched.  A gray mask file has no chroma: the subsampling only
+        changes the sampling byte of its frame header, as it does in Pillow.  The defaults are ``cv2.imwrite``'s, i.e. the
+        reference's, and change nothing.  ``Cropper.encode_jpeg`` uses them too."""
         if encoder not in ("host", "device"):
             raise ValueError(f"unknown encoder {encoder!r}: choose 'host' or 'device'")
         self.encoder = encoder
+        self.jpeg = check_jpeg_settings(jpeg_quality, jpeg_subsampling, jpeg_optimize)
+        self.jpeg_quality, self.jpeg_subsampling, self.jpeg_optimize = self.jpeg
         explicit_family = warp_family if warp_family is not None else (os.environ.get("FCP_WARP_FAMILY") or None)
         align.check_interpolation(interpolation, explicit_family)
         if crop_source not in ("batch", "original"):
@@ -366,7 +378,14 @@ class Cropper:
         if crops.shape[0] == 0:
             return []
         with torch.cuda.device(self.device):
-            return jpegenc.encode_jpeg(torch.from_numpy(crops).to(self.device))
+            return jpegenc.encode_jpeg(torch.from_numpy(crops).to(self.device), **self._jpeg_kw())
+
+    def _jpeg_kw(self) -> dict:
+        """Keywords of ``jpegenc.encode_jpeg`` for this Cropper's settings; none at all for the defaults."""
+        jpeg = getattr(self, "jpeg", None)
+        if jpeg is None or jpeg == JpegSettings():
+            return {}
+        return dict(quality=jpeg.quality, subsampling=jpeg.subsampling, optimize=jpeg.optimize)
 
     # ----------------------------------------------------------------- saving
     MAX_PENDING_WRITES = 256     # encode / write tasks in flight before a GPU worker waits (process_dir)
@@ -395,8 +414,11 @@ class Cropper:
         # Locals: process_dir resets the attributes when it unwinds, while tasks of a failed run may still be in flight.
         writer, writes, slots = getattr(self, "_io", None) or (None, None, None)      # ONE read: never a torn triple
         encoded = isinstance(pixels, bytes)
+        jpeg = getattr(self, "jpeg", None)
+        # the defaults are the encoder table's own entry: the writers are called as they always were
+        jpeg = {} if jpeg is None or jpeg == JpegSettings() else {"jpeg": jpeg}
         if writer is None:
-            write_bytes(path, pixels) if encoded else write_image(path, pixels)
+            write_bytes(path, pixels) if encoded else write_image(path, pixels, **jpeg)
             return
         slots.acquire()
         procs = getattr(self, "_io_procs_active", None)       # encode in the thread's worker process, or on the thread
@@ -404,9 +426,9 @@ class Cropper:
         def task():
             try:
                 if procs is not None:
-                    procs.write_bytes(path, pixels) if encoded else procs.write(path, pixels)
+                    procs.write_bytes(path, pixels) if encoded else procs.write(path, pixels, **jpeg)
                 else:
-                    write_bytes(path, pixels) if encoded else write_image(path, pixels)
+                    write_bytes(path, pixels) if encoded else write_image(path, pixels, **jpeg)
             finally:
                 slots.release()
         with self._write_lock:
@@ -466,7 +488,7 @@ class Cropper:
         if jpeg.any():
             with trace.range("fcp:jpeg"):
                 rows = pixels_dev if jpeg.all() else pixels_dev[torch.from_numpy(jpeg).to(pixels_dev.device)].contiguous()
-                for i, data in zip(np.nonzero(jpeg)[0], jpegenc.encode_jpeg(rows)):
+                for i, data in zip(np.nonzero(jpeg)[0], jpegenc.encode_jpeg(rows, **self._jpeg_kw())):
                     out[i] = data
         if not jpeg.all():
             host = pixels if pixels is not None else pixels_dev.cpu().numpy()

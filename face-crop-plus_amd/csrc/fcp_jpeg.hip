@@ -1,10 +1,12 @@
-// Baseline JPEG entropy-coded segments of uint8 crops (f,h,w,c), c = 3 (RGB, 4:2:0) or 1 (gray), on the device:
-// byte for byte what libjpeg-turbo's default compressor writes between the SOS header and the end of the file
-// (the header itself is jpegenc.jpeg_header, on the host).  Four kernels after one memset:
+// Baseline JPEG entropy-coded segments of uint8 crops (f,h,w,c), c = 3 (RGB; 4:4:4, 4:2:2 or 4:2:0) or 1 (gray), on the
+// device: byte for byte what libjpeg-turbo's compressor writes between the SOS header and the end of the file, with the
+// standard Huffman tables or with tables made for the face (libjpeg's optimize_coding) (INTEGRATION.md sections 2f and
+// 2j; the header itself is jpegenc.jpeg_header, on the host).  Four kernels after one memset:
 //
-//   transform   one lane per 8x8 block, blocks in scan (MCU) order: 16-bit scaled RGB -> YCbCr, edge replication, 2x2 chroma
-//               average with the alternating 1, 2 bias, the 13-bit integer forward DCT ("islow", output scaled by 8),
-//               division by 8 Q rounding half away from zero; 64 int16 per block, zig-zag order, to the workspace
+//   transform   one lane per 8x8 block, blocks in scan (MCU) order: 16-bit scaled RGB -> YCbCr, edge replication, chroma at
+//               full resolution (4:4:4), as the pair average with the alternating 0, 1 bias (4:2:2) or as the 2x2
+//               average with the alternating 1, 2 bias (4:2:0), the 13-bit integer forward DCT ("islow", output scaled by
+//               8), division by 8 Q rounding half away from zero; 64 int16 per block, zig-zag order, to the workspace
 //   count_scan  one workgroup per face: Huffman bit count of every block (DC difference against the block before it of
 //               the same component), exclusive scan over the face -> the bit offset of every block
 //   emit        one lane per block: the block's code bits, shifted to its offset, into 32-bit big-endian words; words a
@@ -13,8 +15,18 @@
 //   stuff       one workgroup per face: FF -> FF 00 with output positions from a scan of per-lane FF counts, then EOI
 //               and the length; every store is checked against the caller's capacity
 //
-// An MCU that overhangs an odd Y block grid carries dummy blocks: all AC zero and the DC of the block before them, i.e. a
-// zero DC difference and an end-of-block, and the DC prediction passes through them unchanged.  They are never transformed.
+// and, with optimised tables, two more between transform and count_scan:
+//
+//   histogram   one lane per block, the same walk over its symbols as count_scan and emit: the frequency of every symbol
+//               per face and table (Y DC, Y AC, chroma DC, chroma AC), through per-wave LDS histograms and integer
+//               global atomics (adds commute: the counts do not depend on the order)
+//   tables      one wave per table: libjpeg's jpeg_gen_optimal_table restated -> the table's 272-byte record for the
+//               header and 256 x (code | length << 16) for count_scan and emit, which stage the face's own tables in LDS
+//
+// The chroma subsampling is a template argument of the kernels (an MCU is hs * vs Y blocks, then Cb, then Cr); gray crops
+// run the 4:2:0 instances.  An MCU that overhangs an odd Y block grid carries dummy blocks: all AC zero and the DC of the
+// block before them, i.e. a zero DC difference and an end-of-block, and the DC prediction passes through them unchanged.
+// They are never transformed.
 #include "fcp_common.h"
 #include "fcp_hip.h"
 
@@ -23,6 +35,10 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxSide = 8192;          // 6 * 512 * 512 blocks * 1658 bits < 2^32: bit offsets of a face fit 32 bits
 constexpr int kMaxBlockBits = 20 + 63 * 26;   // DC: 9-bit code + 11 bits; 63 x (16-bit code + 10 bits); no ZRL can join them
+constexpr int kMaxBlockBitsOpt = 27 + 63 * 26;   // optimised tables: a DC code may be 16 bits long as well
+constexpr int kTableBytes = 272;              // a table's record: 16 counts + up to 256 symbols in code order, zero padded
+constexpr long long kFib35 = 9227465;         // a Huffman tree over fewer counts than Fibonacci(35) is at most 32 deep
+constexpr int kMaxCodeLength = 32;            // libjpeg's MAX_CLEN: the lengths its arrays hold before the limit to 16
 
 // zig-zag position -> natural (row-major) index
 constexpr int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -62,12 +78,20 @@ struct HuffArg {
   uint32_t ac[2][256];          // code | length << 16, by run << 4 | size
 };
 
-// Where the blocks of a face are.  One component: blocks row by row.  Three: MCUs of Y00 Y01 Y10 Y11 Cb Cr.
+// Where the blocks of a face are.  One component: blocks row by row.  Three: MCUs of hs * vs Y blocks row by row, Cb, Cr.
 struct Geometry {
   int h, w, c;
   int ybw, ybh;                 // Y block grid: ceil(w / 8), ceil(h / 8)
   int mw;                       // MCUs (c == 3) or blocks (c == 1) per row
   int nblk;                     // blocks of a face in the scan, dummies included
+  int hs, vs;                   // luma sampling factors: 1 1 (4:4:4), 2 1 (4:2:2), 2 2 (4:2:0)
+};
+
+// The same factors where the kernels need them at compile time; SS is the `subsampling` argument: 0, 1, 2.
+template <int SS>
+struct Mcu {
+  static constexpr int hs = SS == 0 ? 1 : 2, vs = SS == 2 ? 2 : 1;
+  static constexpr int ny = hs * vs, blocks = ny + 2;
 };
 
 struct BlockPos {
@@ -75,19 +99,21 @@ struct BlockPos {
   bool real;
 };
 
+template <int SS>
 __device__ __forceinline__ BlockPos block_pos(const Geometry& g, int b) {
+  using M = Mcu<SS>;
   BlockPos p;
   if (g.c == 1) {
     p.comp = 0, p.by = b / g.mw, p.bx = b - p.by * g.mw, p.real = true;
     return p;
   }
-  const int m = b / 6, k = b - 6 * m;
+  const int m = b / M::blocks, k = b - M::blocks * m;
   const int my = m / g.mw, mx = m - my * g.mw;
-  if (k < 4) {
-    p.comp = 0, p.by = 2 * my + (k >> 1), p.bx = 2 * mx + (k & 1);
+  if (k < M::ny) {
+    p.comp = 0, p.by = M::vs * my + k / M::hs, p.bx = M::hs * mx + k % M::hs;
     p.real = p.by < g.ybh && p.bx < g.ybw;
   } else {
-    p.comp = k - 3, p.by = my, p.bx = mx, p.real = true;
+    p.comp = k - M::ny + 1, p.by = my, p.bx = mx, p.real = true;
   }
   return p;
 }
@@ -125,11 +151,12 @@ __device__ __forceinline__ int chroma_of(const uint8_t* p, int comp) {
   return comp == 1 ? (-11059 * r - 21709 * g + 32768 * b + kOffset) >> 16 : (32768 * r - 27439 * g - 5329 * b + kOffset) >> 16;
 }
 
+template <int SS>
 __global__ void __launch_bounds__(kThreads) jpeg_transform_kernel(const uint8_t* __restrict__ crops, Geometry g, QuantArg q,
                                                                   int16_t* __restrict__ coefs) {
   const int b = blockIdx.x * kThreads + threadIdx.x;
   if (b >= g.nblk) return;
-  const BlockPos pos = block_pos(g, b);
+  const BlockPos pos = block_pos<SS>(g, b);
   if (!pos.real) return;                                     // dummy blocks have no coefficients: nothing reads theirs
   const uint8_t* face = crops + (size_t)blockIdx.y * g.h * g.w * g.c;
   int d[64];
@@ -142,6 +169,28 @@ __global__ void __launch_bounds__(kThreads) jpeg_transform_kernel(const uint8_t*
         const int x = min(pos.bx * 8 + j, g.w - 1);
         const uint8_t* p = face + ((size_t)y * g.w + x) * g.c;
         d[8 * i + j] = (g.c == 1 ? (int)p[0] : (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16) - 128;
+      }
+    }
+  } else if (SS == 0) {                                        // full resolution: the pixel's own Cb / Cr
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const size_t y = min(pos.by * 8 + i, g.h - 1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const size_t x = min(pos.bx * 8 + j, g.w - 1);
+        d[8 * i + j] = chroma_of(face + (y * g.w + x) * 3, pos.comp) - 128;
+      }
+    }
+  } else if (SS == 1) {                                        // libjpeg's h2v1_downsample: pairs, bias 0 1 0 1 ..
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const size_t y = min(pos.by * 8 + i, g.h - 1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int xo = pos.bx * 8 + j;
+        const size_t x0 = min(2 * xo, g.w - 1), x1 = min(2 * xo + 1, g.w - 1);
+        const int sum = chroma_of(face + (y * g.w + x0) * 3, pos.comp) + chroma_of(face + (y * g.w + x1) * 3, pos.comp);
+        d[8 * i + j] = ((sum + (j & 1)) >> 1) - 128;
       }
     }
   } else {
@@ -183,27 +232,32 @@ __global__ void __launch_bounds__(kThreads) jpeg_transform_kernel(const uint8_t*
 // ------------------------------------------------------------------------------------------------ entropy coding
 // DC of the block the difference of block b is taken against: the nearest earlier block of the component that holds samples
 // (dummies repeat the DC before them), 0 at the start of the face.
+template <int SS>
 __device__ __forceinline__ int dc_before(const Geometry& g, const int16_t* face_coefs, int b) {
+  using M = Mcu<SS>;
   if (g.c == 1) return b == 0 ? 0 : face_coefs[(size_t)(b - 1) * 64];
-  const int k = b % 6;
-  if (k >= 4) return b < 6 ? 0 : face_coefs[(size_t)(b - 6) * 64];
-  for (int p = (k == 0 ? b - 3 : b - 1); p >= 0; p = (p % 6 == 0 ? p - 3 : p - 1))    // Y blocks are k = 0..3 of every MCU
-    if (block_pos(g, p).real) return face_coefs[(size_t)p * 64];
+  const int k = b % M::blocks;
+  if (k >= M::ny) return b < M::blocks ? 0 : face_coefs[(size_t)(b - M::blocks) * 64];
+  // Y blocks are the first ny of every MCU: the one before the first of an MCU is three back, past Cr and Cb
+  for (int p = (k == 0 ? b - 3 : b - 1); p >= 0; p = (p % M::blocks == 0 ? p - 3 : p - 1))
+    if (block_pos<SS>(g, p).real) return face_coefs[(size_t)p * 64];
   return 0;
 }
 
 __device__ __forceinline__ int size_of(int v) { return 32 - __clz(abs(v)); }             // bits of |v|; 0 for 0
 
-// Walk one block's symbols; sink.put(bits, length) gets every code with its appended value bits (length <= 26).
-template <typename Sink>
-__device__ __forceinline__ void code_block(const Geometry& g, const int16_t* face_coefs, int b, const uint32_t* dc_tab,
-                                           const uint32_t* ac_tab, Sink& sink) {
-  const BlockPos pos = block_pos(g, b);
-  const uint32_t* dc = dc_tab + (pos.comp == 0 ? 0 : 12);
-  const uint32_t* ac = ac_tab + (pos.comp == 0 ? 0 : 256);
+__device__ __forceinline__ uint32_t value_bits(int v, int s) { return (uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u); }
+
+// Walk one block's symbols: sink.dc(set, size category, value bits) once, then sink.ac(set, run << 4 | size, value bits,
+// size) for every AC symbol, ZRL and EOB among them; set = 0 for Y, 1 for chroma.  What a symbol costs or looks like is
+// the sink's business: count_scan, emit and the histogram are this one walk.
+template <int SS, typename Sink>
+__device__ __forceinline__ void code_block(const Geometry& g, const int16_t* face_coefs, int b, Sink& sink) {
+  const BlockPos pos = block_pos<SS>(g, b);
+  const int set = pos.comp == 0 ? 0 : 1;
   if (!pos.real) {
-    sink.put(dc[0] & 0xffffu, dc[0] >> 16);
-    sink.put(ac[0] & 0xffffu, ac[0] >> 16);
+    sink.dc(set, 0, 0u);
+    sink.ac(set, 0, 0u, 0);
     return;
   }
   const uint4* src = reinterpret_cast<const uint4*>(face_coefs + (size_t)b * 64);
@@ -215,10 +269,9 @@ __device__ __forceinline__ void code_block(const Geometry& g, const int16_t* fac
     for (int j = 0; j < 8; ++j) {
       int v = (int)(int16_t)(words[j >> 1] >> (16 * (j & 1)));
       if (k8 == 0 && j == 0) {
-        v -= dc_before(g, face_coefs, b);
+        v -= dc_before<SS>(g, face_coefs, b);
         const int s = size_of(v);
-        const uint32_t e = dc[s];
-        sink.put(((e & 0xffffu) << s) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u)), (e >> 16) + s);
+        sink.dc(set, s, value_bits(v, s));
         continue;
       }
       if (v == 0) {
@@ -226,30 +279,56 @@ __device__ __forceinline__ void code_block(const Geometry& g, const int16_t* fac
         continue;
       }
       while (run > 15) {
-        sink.put(ac[0xF0] & 0xffffu, ac[0xF0] >> 16);
+        sink.ac(set, 0xF0, 0u, 0);
         run -= 16;
       }
       const int s = size_of(v);
-      const uint32_t e = ac[(run << 4) | s];
-      sink.put(((e & 0xffffu) << s) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u)), (e >> 16) + s);
+      sink.ac(set, (run << 4) | s, value_bits(v, s), s);
       run = 0;
     }
   }
-  if (run > 0) sink.put(ac[0] & 0xffffu, ac[0] >> 16);
+  if (run > 0) sink.ac(set, 0, 0u, 0);
 }
 
+// The code tables of a workgroup, in LDS: code | length << 16 by DC size category and by AC symbol, per set.
+struct CodeTables {
+  uint32_t dc[2][12];
+  uint32_t ac[2][256];
+};
+
 struct CountSink {
+  const CodeTables* t;
   uint32_t bits = 0;
-  __device__ __forceinline__ void put(uint32_t, uint32_t n) { bits += n; }
+  __device__ __forceinline__ void dc(int set, int s, uint32_t) { bits += (t->dc[set][s] >> 16) + s; }
+  __device__ __forceinline__ void ac(int set, int sym, uint32_t, int s) { bits += (t->ac[set][sym] >> 16) + s; }
+};
+
+// One count per symbol into the wave's own histogram in LDS.  The transform's coefficients give size categories of 11
+// at most; the indices are clamped all the same, so that no 16-bit value at all could leave the arrays.
+struct HistSink {
+  uint32_t* dc_bins;            // [2][16]
+  uint32_t* ac_bins;            // [2][256]
+  __device__ __forceinline__ void dc(int set, int s, uint32_t) { atomicAdd(dc_bins + set * 16 + min(s, 15), 1u); }
+  __device__ __forceinline__ void ac(int set, int sym, uint32_t, int) { atomicAdd(ac_bins + set * 256 + (sym & 255), 1u); }
 };
 
 // Bits go out most significant first.  `acc` holds the `n` (< 32) bits not yet written of the word `word` points at; the
-// first word starts with the bits of the block before (zeros here: OR leaves them alone).
+// first word starts with the bits of the block before (zeros here: OR leaves them alone).  put() takes up to 27 bits (a
+// 16-bit DC code of an optimised table and 11 value bits): with n < 32 that is at most 58 bits in the 64 of `acc`.
 struct EmitSink {
+  const CodeTables* t;
   uint32_t* word;
   uint64_t acc = 0;
   uint32_t n;
   bool shared;                  // the word `word` points at may also hold bits of the block before this one
+  __device__ __forceinline__ void dc(int set, int s, uint32_t bits) {
+    const uint32_t e = t->dc[set][s];
+    put(((e & 0xffffu) << s) | bits, (e >> 16) + s);
+  }
+  __device__ __forceinline__ void ac(int set, int sym, uint32_t bits, int s) {
+    const uint32_t e = t->ac[set][sym];
+    put(((e & 0xffffu) << s) | bits, (e >> 16) + s);
+  }
   __device__ __forceinline__ void put(uint32_t code, uint32_t len) {
     acc = (acc << len) | code;
     n += len;
@@ -267,11 +346,20 @@ struct EmitSink {
   }
 };
 
-__device__ __forceinline__ void load_tables(const HuffArg& hf, uint32_t* dc_tab, uint32_t* ac_tab) {
-  const uint32_t* dc = &hf.dc[0][0];
-  const uint32_t* ac = &hf.ac[0][0];
-  for (int i = threadIdx.x; i < 24; i += kThreads) dc_tab[i] = dc[i];
-  for (int i = threadIdx.x; i < 512; i += kThreads) ac_tab[i] = ac[i];
+// The standard tables from the kernel-argument block, or (face_codes != nullptr) the face's own four 256-entry tables the
+// table kernel left in the workspace, in record order: Y DC, Y AC, chroma DC, chroma AC.  2144 bytes of LDS either way.
+__device__ __forceinline__ void load_tables(const HuffArg& hf, const uint32_t* face_codes, CodeTables* t) {
+  uint32_t* dc_tab = &t->dc[0][0];
+  uint32_t* ac_tab = &t->ac[0][0];
+  if (face_codes == nullptr) {
+    const uint32_t* dc = &hf.dc[0][0];
+    const uint32_t* ac = &hf.ac[0][0];
+    for (int i = threadIdx.x; i < 24; i += kThreads) dc_tab[i] = dc[i];
+    for (int i = threadIdx.x; i < 512; i += kThreads) ac_tab[i] = ac[i];
+  } else {
+    for (int i = threadIdx.x; i < 24; i += kThreads) dc_tab[i] = face_codes[(i / 12) * 512 + i % 12];
+    for (int i = threadIdx.x; i < 512; i += kThreads) ac_tab[i] = face_codes[(i >> 8) * 512 + 256 + (i & 255)];
+  }
   __syncthreads();
 }
 
@@ -296,17 +384,21 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* w
   return before + incl - v;
 }
 
+template <int SS>
 __global__ void __launch_bounds__(kThreads) jpeg_count_scan_kernel(const int16_t* __restrict__ coefs, Geometry g, HuffArg hf,
+                                                                   const uint32_t* __restrict__ codes,
                                                                    uint32_t* __restrict__ bitoff) {
-  __shared__ uint32_t dc_tab[24], ac_tab[512], wave_sums[kThreads / 64];
-  load_tables(hf, dc_tab, ac_tab);
+  __shared__ CodeTables tabs;
+  __shared__ uint32_t wave_sums[kThreads / 64];
+  load_tables(hf, codes ? codes + (size_t)blockIdx.x * 1024 : nullptr, &tabs);
   const int16_t* face_coefs = coefs + (size_t)blockIdx.x * g.nblk * 64;
   uint32_t* off = bitoff + (size_t)blockIdx.x * (g.nblk + 1);
   uint32_t carry = 0;
   for (int base = 0; base < g.nblk; base += kThreads) {        // uniform trip count: every lane reaches the barriers
     const int b = base + threadIdx.x;
     CountSink sink;
-    if (b < g.nblk) code_block(g, face_coefs, b, dc_tab, ac_tab, sink);
+    sink.t = &tabs;
+    if (b < g.nblk) code_block<SS>(g, face_coefs, b, sink);
     uint32_t total;
     const uint32_t excl = block_exclusive_scan(sink.bits, wave_sums, &total);
     if (b < g.nblk) off[b] = carry + excl;
@@ -315,26 +407,182 @@ __global__ void __launch_bounds__(kThreads) jpeg_count_scan_kernel(const int16_t
   if (threadIdx.x == 0) off[g.nblk] = carry;
 }
 
+template <int SS>
 __global__ void __launch_bounds__(kThreads) jpeg_emit_kernel(const int16_t* __restrict__ coefs, Geometry g, HuffArg hf,
+                                                             const uint32_t* __restrict__ codes,
                                                              const uint32_t* __restrict__ bitoff, uint32_t* __restrict__ raw,
                                                              size_t raw_words) {
-  __shared__ uint32_t dc_tab[24], ac_tab[512];
-  load_tables(hf, dc_tab, ac_tab);
+  __shared__ CodeTables tabs;
+  load_tables(hf, codes ? codes + (size_t)blockIdx.y * 1024 : nullptr, &tabs);
   const int b = blockIdx.x * kThreads + threadIdx.x;
   if (b >= g.nblk) return;
   const int16_t* face_coefs = coefs + (size_t)blockIdx.y * g.nblk * 64;
   const uint32_t* off = bitoff + (size_t)blockIdx.y * (g.nblk + 1);
   const uint32_t start = off[b];
   EmitSink sink;
+  sink.t = &tabs;
   sink.word = raw + (size_t)blockIdx.y * raw_words + (start >> 5);
   sink.n = start & 31u;
   sink.shared = sink.n != 0;
-  code_block(g, face_coefs, b, dc_tab, ac_tab, sink);
+  code_block<SS>(g, face_coefs, b, sink);
   if (b == g.nblk - 1) {                                       // fill the last byte with 1-bits
     const uint32_t pad = (8u - (off[g.nblk] & 7u)) & 7u;
     if (pad) sink.put((1u << pad) - 1u, pad);
   }
   sink.finish();
+}
+
+// ------------------------------------------------------------------------------------------------ optimised tables
+constexpr int kHistBins = 2 * 16 + 2 * 256;   // a wave's histogram: DC size categories and AC symbols of both sets
+
+// hist (f, 4, 256), zeroed by the caller's memset: += the symbol counts of this workgroup's blocks.  Dummy blocks count
+// their DC 0 and their EOB, like libjpeg's statistics pass.
+template <int SS>
+__global__ void __launch_bounds__(kThreads) jpeg_histogram_kernel(const int16_t* __restrict__ coefs, Geometry g,
+                                                                  uint32_t* __restrict__ hist) {
+  __shared__ uint32_t bins[kThreads / 64][kHistBins];
+  for (int i = threadIdx.x; i < (kThreads / 64) * kHistBins; i += kThreads) (&bins[0][0])[i] = 0;
+  __syncthreads();
+  const int b = blockIdx.x * kThreads + threadIdx.x;
+  if (b < g.nblk) {
+    HistSink sink;
+    sink.dc_bins = bins[threadIdx.x >> 6];
+    sink.ac_bins = bins[threadIdx.x >> 6] + 32;
+    code_block<SS>(g, coefs + (size_t)blockIdx.y * g.nblk * 64, b, sink);
+  }
+  __syncthreads();
+  uint32_t* dst = hist + (size_t)blockIdx.y * 1024;
+  for (int i = threadIdx.x; i < kHistBins; i += kThreads) {
+    uint32_t n = 0;
+#pragma unroll
+    for (int k = 0; k < kThreads / 64; ++k) n += bins[k][i];
+    if (n == 0) continue;
+    const int col = i < 32 ? (i >> 4) * 512 + (i & 15) : ((i - 32) >> 8) * 512 + 256 + ((i - 32) & 255);
+    atomicAdd(dst + col, n);
+  }
+}
+
+// libjpeg's jpeg_gen_optimal_table, one wave per table.  Entry i of the 257 (256 symbols and the pseudo-symbol 256 of
+// frequency 1, which keeps the all-ones code free) lives in lane i % 64, in registers.  A merge takes the two smallest
+// non-zero frequencies, ties going to the larger index: one butterfly over the lanes' (smallest, second smallest) pairs of
+// the key frequency << 9 | 511 - index.  libjpeg then walks the two `others` chains to add 1 to the code size of every
+// symbol under c1 and c2 and links them; a chain is only a set, so here every entry carries the head of its set instead:
+// each lane adds 1 to its entries under c1 or c2 and moves those under c2 to c1.  Same code sizes, no serial walk.
+// Preconditions (a row sums to less than Fibonacci(35) - 1, so no code is longer than 32 bits) are the caller's; if they
+// do not hold the tables are meaningless but every index below is clamped into its array.
+__global__ void __launch_bounds__(64) jpeg_tables_kernel(const uint32_t* __restrict__ freq, uint8_t* __restrict__ tables,
+                                                         uint32_t* __restrict__ codes) {
+  __shared__ int bits[kMaxCodeLength + 1];
+  __shared__ uint8_t size_by_symbol[256];
+  __shared__ uint8_t record[kTableBytes];
+  __shared__ int first_pos[18];
+  __shared__ uint32_t first_code[17];
+  const int lane = threadIdx.x;
+  const size_t t = blockIdx.x;
+  uint32_t fr[5];
+  int head[5], cs[5];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) fr[j] = freq[t * 256 + lane + 64 * j];
+  fr[4] = lane == 0 ? 1u : 0u;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) head[j] = lane + 64 * j, cs[j] = 0;
+  for (int i = lane; i < kTableBytes; i += 64) record[i] = 0;
+  if (lane <= kMaxCodeLength) bits[lane] = 0;
+  if (__ballot((fr[0] | fr[1] | fr[2] | fr[3]) != 0u) == 0ull) {          // nothing to code: an all-zero record
+    for (int i = lane; i < kTableBytes; i += 64) tables[t * kTableBytes + i] = 0;
+    if (codes)
+      for (int i = lane; i < 256; i += 64) codes[t * 256 + i] = 0u;
+    return;
+  }
+  constexpr unsigned long long kNone = ~0ull;
+  for (int merges = 0; merges < 256; ++merges) {                          // every merge empties one of 257 entries
+    unsigned long long k1 = kNone, k2 = kNone;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      if (fr[j] == 0u) continue;
+      const unsigned long long key = ((unsigned long long)fr[j] << 9) | (unsigned long long)(511 - (lane + 64 * j));
+      if (key < k1) k2 = k1, k1 = key; else if (key < k2) k2 = key;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const unsigned long long o1 = __shfl_xor(k1, off, 64), o2 = __shfl_xor(k2, off, 64);
+      const unsigned long long lo = k1 < o1 ? k1 : o1, hi = k1 < o1 ? o1 : k1, rest = k2 < o2 ? k2 : o2;
+      k1 = lo, k2 = hi < rest ? hi : rest;
+    }
+    if (k2 == kNone) break;                                               // one entry left: the tree is complete
+    const int c1 = 511 - (int)(k1 & 511ull), c2 = 511 - (int)(k2 & 511ull);
+    const uint32_t v2 = (uint32_t)(k2 >> 9);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const int idx = lane + 64 * j;
+      if (idx == c1) fr[j] += v2;
+      if (idx == c2) fr[j] = 0u;
+      if (head[j] == c1 || head[j] == c2) {
+        ++cs[j];
+        head[j] = c1;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j) cs[j] = min(cs[j], kMaxCodeLength);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+    if (cs[j] > 0 && (j < 4 || lane == 0)) atomicAdd(&bits[cs[j]], 1);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) size_by_symbol[lane + 64 * j] = (uint8_t)cs[j];
+  __syncthreads();
+  if (lane == 0) {
+    // libjpeg's limit to 16 bits: take a pair of the longest codes away, give its prefix to one of them and split a
+    // shorter code for the other.  Signed counts and the j > 0 guard only matter when the preconditions do not hold.
+    bool sane = true;
+    for (int i = kMaxCodeLength; i > 16 && sane; --i) {
+      while (bits[i] > 0) {
+        int j = i - 2;
+        while (j > 0 && bits[j] == 0) --j;
+        if (j == 0) {
+          sane = false;
+          break;
+        }
+        bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
+      }
+    }
+    int i = 16;
+    while (i > 0 && bits[i] == 0) --i;
+    if (i > 0) --bits[i];                                                 // the pseudo-symbol's code is not a symbol's
+    uint32_t code = 0;
+    int pos = 0;
+    for (int len = 1; len <= 16; ++len) {
+      const int n = min(max(bits[len], 0), 255);
+      record[len - 1] = (uint8_t)n;
+      first_pos[len] = pos, first_code[len] = code;
+      pos += n;
+      code = (code + (uint32_t)n) << 1;
+    }
+    first_pos[17] = pos;
+  }
+  __syncthreads();
+  // symbols in code order: by code size before the limit, then by value; the limited lengths go to them in that order
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int sym = lane + 64 * j;
+    uint32_t entry = 0u;
+    if (cs[j] > 0) {
+      const int mine = (cs[j] << 8) | sym;
+      int p = 0;
+      for (int i = 0; i < 256; ++i) {
+        const int other = size_by_symbol[i];
+        p += (other > 0 && ((other << 8) | i) < mine) ? 1 : 0;
+      }
+      record[16 + p] = (uint8_t)sym;                                      // p < 256: at most 255 symbols come before one
+      for (int len = 1; len <= 16; ++len)
+        if (p >= first_pos[len] && p < first_pos[len + 1])
+          entry = ((first_code[len] + (uint32_t)(p - first_pos[len])) & 0xffffu) | ((uint32_t)len << 16);
+    }
+    if (codes) codes[t * 256 + sym] = entry;
+  }
+  __syncthreads();
+  for (int i = lane; i < kTableBytes; i += 64) tables[t * kTableBytes + i] = record[i];
 }
 
 // ------------------------------------------------------------------------------------------------ byte stuffing
@@ -390,24 +638,30 @@ struct Layout {
   Geometry g;
   size_t raw_words;             // per face, a multiple of 4: the stuffing pass reads 16 bytes at a time
   size_t coef_bytes, off_bytes, raw_bytes;
+  size_t hist_bytes, code_bytes;   // optimised tables only: (f, 4, 256) counts behind the raw bits, then as many codes
+  size_t total() const { return coef_bytes + off_bytes + raw_bytes + hist_bytes + code_bytes; }
 };
 
-Layout layout_of(int f, int h, int w, int c) {
+int blocks_of(int h, int w, int c, int ss) {
+  if (c == 1) return ((w + 7) / 8) * ((h + 7) / 8);
+  const int hs = ss == 0 ? 1 : 2, vs = ss == 2 ? 2 : 1;
+  return (hs * vs + 2) * ((w + 8 * hs - 1) / (8 * hs)) * ((h + 8 * vs - 1) / (8 * vs));
+}
+
+Layout layout_of(int f, int h, int w, int c, int ss, int optimize) {
   Layout l;
   Geometry& g = l.g;
   g.h = h, g.w = w, g.c = c;
   g.ybw = (w + 7) / 8, g.ybh = (h + 7) / 8;
-  if (c == 1) {
-    g.mw = g.ybw;
-    g.nblk = g.ybw * g.ybh;
-  } else {
-    g.mw = (w + 15) / 16;
-    g.nblk = 6 * g.mw * ((h + 15) / 16);
-  }
-  l.raw_words = (((size_t)g.nblk * kMaxBlockBits + 7 + 31) / 32 + 3) & ~(size_t)3;
+  g.hs = ss == 0 ? 1 : 2, g.vs = ss == 2 ? 2 : 1;
+  g.mw = c == 1 ? g.ybw : (w + 8 * g.hs - 1) / (8 * g.hs);
+  g.nblk = blocks_of(h, w, c, ss);
+  const int block_bits = optimize ? kMaxBlockBitsOpt : kMaxBlockBits;
+  l.raw_words = (((size_t)g.nblk * block_bits + 7 + 31) / 32 + 3) & ~(size_t)3;
   l.coef_bytes = round16((size_t)f * g.nblk * 64 * sizeof(int16_t));
   l.off_bytes = round16((size_t)f * (g.nblk + 1) * sizeof(uint32_t));
   l.raw_bytes = (size_t)f * l.raw_words * sizeof(uint32_t);
+  l.hist_bytes = l.code_bytes = optimize ? (size_t)f * 4 * 256 * sizeof(uint32_t) : 0;
   return l;
 }
 
@@ -429,28 +683,51 @@ int check_sizes(int f, int h, int w, int channels) {
   return 0;
 }
 
-}  // namespace
-
-extern "C" int64_t fcp_jpeg_workspace_bytes(int f, int h, int w, int channels) {
-  if (check_sizes(f, h, w, channels) != 0) return -1;
-  const Layout l = layout_of(f, h, w, channels);
-  return (int64_t)(l.coef_bytes + l.off_bytes + l.raw_bytes);
+// What the extended entry points check on top: the two settings, and the two limits a face's block count has.
+int check_options(int h, int w, int channels, int subsampling, int optimize) {
+  FCP_REQUIRE(subsampling >= 0 && subsampling <= 2, "jpeg_encode: subsampling 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), not %d",
+              subsampling);
+  FCP_REQUIRE(optimize == 0 || optimize == 1, "jpeg_encode: optimize 0 or 1, not %d", optimize);
+  const long long nblk = blocks_of(h, w, channels, subsampling);
+  FCP_REQUIRE(nblk * (optimize ? kMaxBlockBitsOpt : kMaxBlockBits) <= 0xffffffffll,
+              "jpeg_encode: a face of %lld blocks is too large for 32-bit bit offsets (h %d, w %d)", nblk, h, w);
+  FCP_REQUIRE(!optimize || 64 * nblk + 1 < kFib35,
+              "jpeg_encode: optimised tables need fewer than %lld coefficients per face, a face of %lld blocks has %lld "
+              "(a deeper Huffman tree than libjpeg's 32 levels would be possible)", kFib35 - 1, nblk, 64 * nblk);
+  return 0;
 }
 
-extern "C" int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int channels, int quality, int subsampling,
-                                  uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths, void* workspace,
-                                  int64_t workspace_bytes, fcp_stream_t stream) {
-  if (check_sizes(f, h, w, channels) != 0) return FCP_ERR_ARG;
+template <int SS>
+void launch_encode(const uint8_t* crops, int f, const Layout& l, const QuantArg& q, const HuffArg& hf, int optimize,
+                   uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths, uint8_t* tables, int16_t* coefs,
+                   uint32_t* bitoff, uint32_t* raw, uint32_t* hist, uint32_t* codes, hipStream_t s) {
+  const dim3 per_block(fcp_cdiv(l.g.nblk, kThreads), f);
+  hipLaunchKernelGGL(jpeg_transform_kernel<SS>, per_block, dim3(kThreads), 0, s, crops, l.g, q, coefs);
+  if (optimize) {
+    hipLaunchKernelGGL(jpeg_histogram_kernel<SS>, per_block, dim3(kThreads), 0, s, coefs, l.g, hist);
+    hipLaunchKernelGGL(jpeg_tables_kernel, dim3(4 * f), dim3(64), 0, s, hist, tables, codes);
+  }
+  hipLaunchKernelGGL(jpeg_count_scan_kernel<SS>, dim3(f), dim3(kThreads), 0, s, coefs, l.g, hf, optimize ? codes : nullptr,
+                     bitoff);
+  hipLaunchKernelGGL(jpeg_emit_kernel<SS>, per_block, dim3(kThreads), 0, s, coefs, l.g, hf, optimize ? codes : nullptr, bitoff,
+                     raw, l.raw_words);
+  hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(f), dim3(kThreads), 0, s, raw, l.raw_words, l.g.nblk, bitoff, out,
+                     (long long)out_stride, (long long)capacity, lengths);
+}
+
+// Everything behind both entry points; the caller has checked sizes, subsampling and optimize.
+int encode(const uint8_t* crops, int f, int h, int w, int channels, int quality, int subsampling, int optimize, uint8_t* out,
+           int64_t out_stride, int64_t capacity, int32_t* lengths, uint8_t* tables, void* workspace, int64_t workspace_bytes,
+           const char* sizer, fcp_stream_t stream) {
   FCP_REQUIRE(quality >= 1 && quality <= 100, "jpeg_encode: quality 1..100, not %d", quality);
-  FCP_REQUIRE(subsampling == 2, "jpeg_encode: only 4:2:0 chroma subsampling (2) is built, not %d", subsampling);
   FCP_REQUIRE(capacity >= 0 && out_stride >= capacity, "jpeg_encode: capacity %lld must be >= 0 and fit the stride %lld",
               (long long)capacity, (long long)out_stride);
   if (f == 0) return 0;
   FCP_REQUIRE(crops && lengths && workspace && (out || capacity == 0), "jpeg_encode: null pointer");
-  const Layout l = layout_of(f, h, w, channels);
-  FCP_REQUIRE(workspace_bytes >= (int64_t)(l.coef_bytes + l.off_bytes + l.raw_bytes),
-              "jpeg_encode: workspace of %lld bytes, fcp_jpeg_workspace_bytes asks for %lld", (long long)workspace_bytes,
-              (long long)(l.coef_bytes + l.off_bytes + l.raw_bytes));
+  FCP_REQUIRE(!optimize || tables, "jpeg_encode: optimize needs the tables buffer (null pointer)");
+  const Layout l = layout_of(f, h, w, channels, subsampling, optimize);
+  FCP_REQUIRE(workspace_bytes >= (int64_t)l.total(), "jpeg_encode: workspace of %lld bytes, %s asks for %lld",
+              (long long)workspace_bytes, sizer, (long long)l.total());
   FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "jpeg_encode: the workspace must be 16-byte aligned");
 
   QuantArg q;
@@ -472,17 +749,63 @@ extern "C" int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int
   int16_t* coefs = reinterpret_cast<int16_t*>(ws);
   uint32_t* bitoff = reinterpret_cast<uint32_t*>(ws + l.coef_bytes);
   uint32_t* raw = reinterpret_cast<uint32_t*>(ws + l.coef_bytes + l.off_bytes);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(ws + l.coef_bytes + l.off_bytes + l.raw_bytes);
+  uint32_t* codes = reinterpret_cast<uint32_t*>(ws + l.coef_bytes + l.off_bytes + l.raw_bytes + l.hist_bytes);
   hipStream_t s = (hipStream_t)stream;
-  FCP_HIP_OK(hipMemsetAsync(raw, 0, l.raw_bytes, s));
-  const dim3 per_block(fcp_cdiv(l.g.nblk, kThreads), f);
-  hipLaunchKernelGGL(jpeg_transform_kernel, per_block, dim3(kThreads), 0, s, crops, l.g, q, coefs);
+  FCP_HIP_OK(hipMemsetAsync(raw, 0, l.raw_bytes + l.hist_bytes, s));            // the counts sit right behind the bits
+  switch (channels == 1 ? 2 : subsampling) {                                    // gray has no MCUs: any instance does
+    case 0:
+      launch_encode<0>(crops, f, l, q, hf, optimize, out, out_stride, capacity, lengths, tables, coefs, bitoff, raw, hist, codes, s);
+      break;
+    case 1:
+      launch_encode<1>(crops, f, l, q, hf, optimize, out, out_stride, capacity, lengths, tables, coefs, bitoff, raw, hist, codes, s);
+      break;
+    default:
+      launch_encode<2>(crops, f, l, q, hf, optimize, out, out_stride, capacity, lengths, tables, coefs, bitoff, raw, hist, codes, s);
+  }
   FCP_LAUNCH_OK();
-  hipLaunchKernelGGL(jpeg_count_scan_kernel, dim3(f), dim3(kThreads), 0, s, coefs, l.g, hf, bitoff);
-  FCP_LAUNCH_OK();
-  hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(kThreads), 0, s, coefs, l.g, hf, bitoff, raw, l.raw_words);
-  FCP_LAUNCH_OK();
-  hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(f), dim3(kThreads), 0, s, raw, l.raw_words, l.g.nblk, bitoff, out,
-                     (long long)out_stride, (long long)capacity, lengths);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t fcp_jpeg_workspace_bytes(int f, int h, int w, int channels) {
+  if (check_sizes(f, h, w, channels) != 0) return -1;
+  return (int64_t)layout_of(f, h, w, channels, 2, 0).total();
+}
+
+extern "C" int64_t fcp_jpeg_workspace_bytes_ex(int f, int h, int w, int channels, int subsampling, int optimize) {
+  if (check_sizes(f, h, w, channels) != 0 || check_options(h, w, channels, subsampling, optimize) != 0) return -1;
+  return (int64_t)layout_of(f, h, w, channels, subsampling, optimize).total();
+}
+
+extern "C" int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int channels, int quality, int subsampling,
+                                  uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths, void* workspace,
+                                  int64_t workspace_bytes, fcp_stream_t stream) {
+  if (check_sizes(f, h, w, channels) != 0) return FCP_ERR_ARG;
+  FCP_REQUIRE(quality >= 1 && quality <= 100, "jpeg_encode: quality 1..100, not %d", quality);
+  FCP_REQUIRE(subsampling == 2, "jpeg_encode: only 4:2:0 chroma subsampling (2) is built, not %d", subsampling);
+  return encode(crops, f, h, w, channels, quality, 2, 0, out, out_stride, capacity, lengths, nullptr, workspace, workspace_bytes,
+                "fcp_jpeg_workspace_bytes", stream);
+}
+
+extern "C" int fcp_jpeg_encode_ex_u8(const uint8_t* crops, int f, int h, int w, int channels, int quality, int subsampling,
+                                     int optimize, uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths,
+                                     uint8_t* tables, void* workspace, int64_t workspace_bytes, fcp_stream_t stream) {
+  if (check_sizes(f, h, w, channels) != 0) return FCP_ERR_ARG;
+  FCP_REQUIRE(quality >= 1 && quality <= 100, "jpeg_encode: quality 1..100, not %d", quality);
+  if (check_options(h, w, channels, subsampling, optimize) != 0) return FCP_ERR_ARG;
+  return encode(crops, f, h, w, channels, quality, subsampling, optimize, out, out_stride, capacity, lengths, tables, workspace,
+                workspace_bytes, "fcp_jpeg_workspace_bytes_ex", stream);
+}
+
+extern "C" int fcp_jpeg_huffman_tables(const uint32_t* freq, int n, uint8_t* tables, uint32_t* codes, fcp_stream_t stream) {
+  FCP_REQUIRE(n >= 0 && n <= 4 * 65535, "jpeg_huffman_tables: 0..%d rows, not %d", 4 * 65535, n);
+  if (n == 0) return 0;
+  FCP_REQUIRE(freq && tables, "jpeg_huffman_tables: null pointer");
+  FCP_REQUIRE((reinterpret_cast<uintptr_t>(freq) & 3) == 0 && (reinterpret_cast<uintptr_t>(codes) & 3) == 0,
+              "jpeg_huffman_tables: freq and codes must be 4-byte aligned");
+  hipLaunchKernelGGL(jpeg_tables_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, freq, tables, codes);
   FCP_LAUNCH_OK();
   return 0;
 }

@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / matte / clahe / matte_blur
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / matte / clahe / matte_blur
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -416,6 +416,59 @@ Tensor jpeg_encode(const Tensor& crops, int64_t quality, int64_t subsampling, co
   return lengths;
 }
 
+// jpeg_encode with the caller's chroma subsampling (0 / 1 / 2) and, when `tables` (f,4,272) uint8 is given, Huffman tables
+// made for every face, which are written there (fcp_jpeg_encode_ex_u8).
+Tensor jpeg_encode_ex(const Tensor& crops, int64_t quality, int64_t subsampling, const Tensor& out,
+                      const c10::optional<Tensor>& tables) {
+  dev(crops, "crops", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  TORCH_CHECK((crops.dim() == 4 && (crops.size(3) == 3 || crops.size(3) == 1)) || crops.dim() == 3,
+              "crops (f,h,w,3) or (f,h,w) uint8");
+  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2), c = crops.dim() == 4 ? crops.size(3) : 1;
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops: sizes past int");
+  TORCH_CHECK(quality >= INT_MIN && quality <= INT_MAX && subsampling >= INT_MIN && subsampling <= INT_MAX,
+              "quality / subsampling past int");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kByte && out.get_device() == crops.get_device(),
+              "out must be a uint8 tensor on the device of the crops");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == f, "out must be (", f, ", capacity)");
+  const int64_t capacity = out.size(1), stride = f > 1 ? out.stride(0) : capacity;
+  TORCH_CHECK(capacity == 0 || out.stride(1) == 1, "out: the bytes of a row must be contiguous");
+  TORCH_CHECK(stride >= capacity, "out: rows overlap");
+  const bool optimize = tables.has_value() && tables->defined();
+  if (optimize) {
+    const Tensor& t = *tables;
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kByte && t.get_device() == crops.get_device() && t.is_contiguous() &&
+                    t.dim() == 3 && t.size(0) == f && t.size(1) == 4 && t.size(2) == 272,
+                "tables must be a contiguous (", f, ",4,272) uint8 tensor on the device of the crops");
+  }
+  Tensor lengths = at::empty({f}, crops.options().dtype(at::kInt));
+  const int64_t need = fcp_jpeg_workspace_bytes_ex((int)f, (int)h, (int)w, (int)c, (int)subsampling, optimize ? 1 : 0);
+  ok(need < 0 ? -1 : 0, "fcp::jpeg_encode_ex");
+  Tensor work = at::empty({need}, crops.options());
+  ok(fcp_jpeg_encode_ex_u8(crops.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (int)c, (int)quality, (int)subsampling,
+                           optimize ? 1 : 0, capacity > 0 ? out.data_ptr<uint8_t>() : nullptr, stride, capacity,
+                           lengths.data_ptr<int32_t>(), optimize ? tables->data_ptr<uint8_t>() : nullptr, work.data_ptr(), need,
+                           cur_stream()),
+     "fcp::jpeg_encode_ex");
+  return lengths;
+}
+
+// Rows of 256 symbol counts (n,256) int32 -> libjpeg's optimal Huffman tables: the records (n,272) uint8 and, with
+// `with_codes`, code | length << 16 by symbol (n,256) int32 (else an empty tensor) (fcp_jpeg_huffman_tables).
+std::tuple<Tensor, Tensor> jpeg_huffman_tables(const Tensor& freq, bool with_codes) {
+  dev(freq, "freq", at::kInt);
+  FCP_DEVICE_GUARD(freq);
+  TORCH_CHECK(freq.dim() == 2 && freq.size(1) == 256 && freq.is_contiguous(), "freq (n,256) int32, contiguous");
+  const int64_t n = freq.size(0);
+  TORCH_CHECK(n <= INT_MAX, "freq: rows past int");
+  Tensor tables = at::empty({n, 272}, freq.options().dtype(at::kByte));
+  Tensor codes = with_codes ? at::empty({n, 256}, freq.options()) : at::empty({0}, freq.options());
+  ok(fcp_jpeg_huffman_tables(reinterpret_cast<const uint32_t*>(freq.data_ptr<int32_t>()), (int)n, tables.data_ptr<uint8_t>(),
+                             with_codes ? reinterpret_cast<uint32_t*>(codes.data_ptr<int32_t>()) : nullptr, cur_stream()),
+     "fcp::jpeg_huffman_tables");
+  return {tables, codes};
+}
+
 // Crops (f,h,w,3) uint8 over a uniform fill through the soft mask of their label maps (f,h,w) uint8: the composited
 // crops and, with `with_alpha`, the alpha (f,h,w) uint8 (else an empty tensor) (fcp_matte_u8).
 std::tuple<Tensor, Tensor> matte(const Tensor& crops, const Tensor& labels, int64_t class_bits, int64_t feather, int64_t bg_r,
@@ -549,6 +602,8 @@ TORCH_LIBRARY(fcp, m) {
   m.def("resize_area_u8_ragged(Tensor src, Tensor levels, Tensor(a!) dst) -> ()");
   m.def("crop_sharpness(Tensor crops, Tensor? ok) -> Tensor");
   m.def("jpeg_encode(Tensor crops, int quality, int subsampling, Tensor(a!) out) -> Tensor");
+  m.def("jpeg_encode_ex(Tensor crops, int quality, int subsampling, Tensor(a!) out, Tensor(b!)? tables) -> Tensor");
+  m.def("jpeg_huffman_tables(Tensor freq, bool with_codes) -> (Tensor, Tensor)");
   m.def("matte(Tensor crops, Tensor labels, int class_bits, int feather, int bg_r, int bg_g, int bg_b, bool with_alpha) "
         "-> (Tensor, Tensor)");
   m.def("clahe(Tensor crops, int grid, float clip_limit) -> Tensor");
@@ -578,6 +633,8 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("resize_area_u8_ragged", &resize_area_u8_ragged);
   m.impl("crop_sharpness", &crop_sharpness);
   m.impl("jpeg_encode", &jpeg_encode);
+  m.impl("jpeg_encode_ex", &jpeg_encode_ex);
+  m.impl("jpeg_huffman_tables", &jpeg_huffman_tables);
   m.impl("matte", &matte);
   m.impl("clahe", &clahe);
   m.impl("matte_blur", &matte_blur);

@@ -1,7 +1,8 @@
 """JPEG files of device-resident crops (``Cropper(encoder="device")``): the kernels of
 ``csrc/fcp_jpeg.hip`` write every face's entropy-coded segment, the host puts the header in front.  The result is byte for
 byte the file ``_io_codec.write_image`` (Pillow over libjpeg-turbo) writes for the same pixels, so a face whose stream does
-not fit its slot is simply encoded there instead."""
+not fit its slot is simply encoded there instead.  Quality, chroma subsampling and per-file ("optimised") Huffman tables
+are the caller's (section 2j); the defaults are the encoder table's and take the entry point they always took."""
 from __future__ import annotations
 
 import io
@@ -11,7 +12,7 @@ import torch
 
 from . import _native as N
 from . import torch_ops as T
-from ._io_codec import _ENCODER_KW
+from ._io_codec import _ENCODER_KW, JPEG_SUBSAMPLINGS, JpegSettings, jpeg_kw, save_jpeg
 
 JPEG_EXTENSIONS = tuple(ext for ext, kw in _ENCODER_KW.items() if kw.get("format") == "JPEG")     # .jpg / .jpeg / .jpe
 _KW = _ENCODER_KW[".jpg"]
@@ -51,45 +52,101 @@ def _segment(marker: int, payload: bytes) -> bytes:
     return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, "big") + payload
 
 
-def jpeg_header(h: int, w: int, channels: int, quality: int = QUALITY) -> bytes:
+TABLE_BYTES = 272                # one Huffman table of the device encoder: 16 counts + up to 256 symbols, zero padded
+
+
+def subsampling_index(subsampling) -> int:
+    """"4:4:4" / "4:2:2" / "4:2:0" (or 0 / 1 / 2 already) -> the `subsampling` argument of the C entry points."""
+    if isinstance(subsampling, str):
+        if subsampling not in JPEG_SUBSAMPLINGS:
+            raise ValueError(f"unknown subsampling {subsampling!r}: choose '4:4:4', '4:2:2' or '4:2:0'")
+        return JPEG_SUBSAMPLINGS.index(subsampling)
+    if isinstance(subsampling, bool) or int(subsampling) not in (0, 1, 2):
+        raise ValueError(f"subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), not {subsampling!r}")
+    return int(subsampling)
+
+
+def _dht_payloads(tables, sets: int):
+    """`tables`: None (the standard tables) or one face's four 272-byte records -> [(DC payload, AC payload)] per set."""
+    if tables is None:
+        return [(bytes(_DC[k][0]) + bytes(_DC[k][1]), bytes(_AC[k][0]) + bytes(_AC[k][1])) for k in range(sets)]
+    rec = np.frombuffer(bytes(tables), np.uint8) if isinstance(tables, (bytes, bytearray)) else np.asarray(tables, np.uint8)
+    rec = rec.reshape(4, TABLE_BYTES)
+    out = []
+    for k in range(sets):
+        pair = []
+        for r in rec[2 * k:2 * k + 2]:
+            n = int(r[:16].sum())
+            if n > 256:
+                raise ValueError("a Huffman table record lists more than 256 symbols")
+            pair.append(r[:16 + n].tobytes())
+        out.append(tuple(pair))
+    return out
+
+
+def jpeg_header(h: int, w: int, channels: int, quality: int = QUALITY, *, subsampling=SUBSAMPLING, tables=None) -> bytes:
     """Everything of the file in front of the entropy-coded segment, as Pillow / libjpeg write it at these settings: SOI,
     the JFIF 1.01 APP0 segment (no density unit, 1:1), one DQT per table (IJG quality scale, baseline range), SOF0 (8 bit;
-    luma sampled 2x2 — written for gray too, where it changes nothing), the standard Huffman tables, SOS."""
+    luma sampled 1x1, 2x1 or 2x2 for 4:4:4, 4:2:2, 4:2:0 — written for gray too, where it changes nothing but that
+    byte), the Huffman tables, SOS.  ``tables``: None for the standard tables, or the face's four 272-byte records as
+    the device encoder wrote them (Y DC, Y AC, chroma DC, chroma AC): optimised tables sit where the standard ones do."""
     if channels not in (1, 3):
         raise ValueError(f"channels must be 1 or 3, not {channels!r}")
     if not (1 <= int(quality) <= 100):
         raise ValueError(f"quality must be in 1..100, not {quality!r}")
     if not (1 <= h <= 65535 and 1 <= w <= 65535):
         raise ValueError(f"a JPEG frame is 1..65535 px on each side, not {h} x {w}")
+    ss = subsampling_index(subsampling)
     sets = 1 if channels == 1 else 2
     scale = 5000 // int(quality) if quality < 50 else 200 - 2 * int(quality)
     out = b"\xff\xd8" + _segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
     for k in range(sets):
         table = [min(max((_QUANT[k][i] * scale + 50) // 100, 1), 255) for i in _ZIGZAG]
         out += _segment(0xDB, bytes([k]) + bytes(table))
-    comps = [(1, 0x22, 0), (2, 0x11, 1), (3, 0x11, 1)][:channels]
+    comps = [(1, (0x11, 0x21, 0x22)[ss], 0), (2, 0x11, 1), (3, 0x11, 1)][:channels]
     out += _segment(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([channels]) +
                     b"".join(bytes(c) for c in comps))
-    for k in range(sets):
-        out += _segment(0xC4, bytes([k]) + bytes(_DC[k][0]) + bytes(_DC[k][1]))
-        out += _segment(0xC4, bytes([0x10 | k]) + bytes(_AC[k][0]) + bytes(_AC[k][1]))
+    for k, (dc, ac) in enumerate(_dht_payloads(tables, sets)):
+        out += _segment(0xC4, bytes([k]) + dc)
+        out += _segment(0xC4, bytes([0x10 | k]) + ac)
     return out + _segment(0xDA, bytes([channels]) + b"".join(bytes([c[0], 0x11 * c[2]]) for c in comps) + b"\x00\x3f\x00")
 
 
-def encode_scans(crops_dev: torch.Tensor, out: torch.Tensor, quality: int = QUALITY) -> torch.Tensor:
+def encode_scans(crops_dev: torch.Tensor, out: torch.Tensor, quality: int = QUALITY, *, subsampling=SUBSAMPLING,
+                 tables: torch.Tensor | None = None) -> torch.Tensor:
     """crops (F,H,W,3) or (F,H,W) u8 device, out (F, capacity) u8 device (rows may be a view of a wider buffer) -> lengths
     (F,) int32 device.  Row i receives face i's entropy-coded segment and EOI, at most ``capacity`` bytes of it; the length
-    is the true one even then.  One memset and four launches."""
+    is the true one even then.  One memset and four launches.
+    ``tables`` (F,4,272) u8 device, contiguous: code every face with Huffman tables made for it (libjpeg's
+    ``optimize_coding``); the four records of face i are written to tables[i] (a histogram and a table launch more).
+    With 4:2:0 and no ``tables`` this is the call it always was; anything else takes ``fcp_jpeg_encode_ex_u8``."""
     assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() in (3, 4)
     assert out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == crops_dev.shape[0]
-    if T.ENABLED:
-        return T.load().jpeg_encode(crops_dev, int(quality), SUBSAMPLING, out)
+    ss = subsampling_index(subsampling)
     f, h, w = crops_dev.shape[:3]
+    if tables is not None:
+        assert tables.dtype == torch.uint8 and tables.is_contiguous() and tuple(tables.shape) == (f, 4, TABLE_BYTES)
+        assert tables.device == crops_dev.device
+    ex = ss != SUBSAMPLING or tables is not None
+    if T.ENABLED:
+        if ex:
+            return T.load().jpeg_encode_ex(crops_dev, int(quality), ss, out, tables)
+        return T.load().jpeg_encode(crops_dev, int(quality), SUBSAMPLING, out)
     c = crops_dev.shape[3] if crops_dev.dim() == 4 else 1
     capacity = out.shape[1]
     if capacity and out.stride(1) != 1:
         raise RuntimeError("jpeg_encode: the bytes of a row of out must be contiguous")
     lengths = torch.empty((f,), dtype=torch.int32, device=crops_dev.device)
+    if ex:
+        opt = 0 if tables is None else 1
+        need = N.lib().fcp_jpeg_workspace_bytes_ex(f, h, w, c, ss, opt)
+        N.check(-1 if need < 0 else 0, "fcp_jpeg_encode_ex_u8")
+        work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
+        N.check(N.lib().fcp_jpeg_encode_ex_u8(N.ptr(crops_dev), f, h, w, c, int(quality), ss, opt,
+                                              N.ptr(out) if capacity else None, out.stride(0) if f > 1 else capacity, capacity,
+                                              N.ptr(lengths), N.ptr(tables), N.ptr(work), need, N.stream_ptr()),
+                "fcp_jpeg_encode_ex_u8")
+        return lengths
     need = N.lib().fcp_jpeg_workspace_bytes(f, h, w, c)
     N.check(-1 if need < 0 else 0, "fcp_jpeg_encode_u8")
     work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
@@ -99,34 +156,58 @@ def encode_scans(crops_dev: torch.Tensor, out: torch.Tensor, quality: int = QUAL
     return lengths
 
 
-def _host_jpeg(pixels: np.ndarray, quality: int) -> bytes:
-    from PIL import Image
+def huffman_tables(freq: torch.Tensor, with_codes: bool = False):
+    """freq (N,256) uint32-valued int32 device rows of symbol counts (each row's sum below 9 227 464) -> the optimal
+    tables libjpeg's ``jpeg_gen_optimal_table`` makes of them, as records (N,272) u8 device; with ``with_codes`` also
+    (N,256) int32 ``code | length << 16`` by symbol.  An all-zero row gives an all-zero record.  One launch."""
+    assert freq.dtype == torch.int32 and freq.is_contiguous() and freq.dim() == 2 and freq.shape[1] == 256
+    if T.ENABLED:
+        tables, codes = T.load().jpeg_huffman_tables(freq, bool(with_codes))
+        return (tables, codes) if with_codes else tables
+    n = freq.shape[0]
+    tables = torch.empty((n, TABLE_BYTES), dtype=torch.uint8, device=freq.device)
+    codes = torch.empty((n, 256), dtype=torch.int32, device=freq.device) if with_codes else None
+    N.check(N.lib().fcp_jpeg_huffman_tables(N.ptr(freq), n, N.ptr(tables), N.ptr(codes), N.stream_ptr()),
+            "fcp_jpeg_huffman_tables")
+    return (tables, codes) if with_codes else tables
+
+
+def _host_jpeg(pixels: np.ndarray, quality: int, subsampling=SUBSAMPLING, optimize: bool = False) -> bytes:
     buf = io.BytesIO()
-    Image.fromarray(pixels).save(buf, **dict(_KW, quality=int(quality)))
+    save_jpeg(pixels, buf, jpeg_kw(JpegSettings(int(quality), JPEG_SUBSAMPLINGS[subsampling_index(subsampling)], bool(optimize))))
     return buf.getvalue()
 
 
-def encode_jpeg(crops_dev: torch.Tensor, quality: int = QUALITY, capacity: int | None = None) -> list:
+def encode_jpeg(crops_dev: torch.Tensor, quality: int = QUALITY, capacity: int | None = None, *, subsampling=SUBSAMPLING,
+                optimize: bool = False) -> list:
     """crops (F,H,W,3) or (F,H,W) u8 device -> F complete JPEG files (bytes), each equal to what ``write_image`` writes for
-    those pixels.  ``capacity``: bytes of a face's slot on the device (default: the raw size of a face, H*W*C); what comes
-    back to the host is the lengths and the used part of the slots, not the pixels.  A face whose stream is longer than
-    its slot (noise can be: a block costs up to 416 bytes) is read back alone and encoded on the host: same bytes."""
+    those pixels at these settings.  ``capacity``: bytes of a face's slot on the device (default: the raw size of a face,
+    H*W*C); what comes back to the host is the lengths, the used part of the slots and, with ``optimize``, the faces'
+    Huffman tables (1088 bytes each) — not the pixels.  A face whose stream is longer than its slot (noise can be: a
+    block costs up to 417 bytes) is read back alone and encoded on the host: same bytes."""
     f, h, w = crops_dev.shape[:3]
     c = crops_dev.shape[3] if crops_dev.dim() == 4 else 1
     if f == 0:
         return []
+    ss = subsampling_index(subsampling)
     capacity = h * w * c if capacity is None else int(capacity)
     out = torch.empty((f, capacity), dtype=torch.uint8, device=crops_dev.device)
-    lengths = encode_scans(crops_dev, out, quality).cpu().numpy()
+    tables = torch.empty((f, 4, TABLE_BYTES), dtype=torch.uint8, device=crops_dev.device) if optimize else None
+    if ss == SUBSAMPLING and not optimize:
+        lengths = encode_scans(crops_dev, out, quality).cpu().numpy()
+    else:
+        lengths = encode_scans(crops_dev, out, quality, subsampling=ss, tables=tables).cpu().numpy()
     fits = lengths <= capacity
     used = int(lengths[fits].max()) if fits.any() else 0
     scans = out[:, :used].cpu().numpy() if used else None
-    head = jpeg_header(h, w, c, quality)
+    records = tables.cpu().numpy() if optimize else None
+    head = None if optimize else jpeg_header(h, w, c, quality, subsampling=ss)
     files = []
     for i in range(f):
         if fits[i]:
-            files.append(head + scans[i, :lengths[i]].tobytes())
+            face_head = jpeg_header(h, w, c, quality, subsampling=ss, tables=records[i]) if optimize else head
+            files.append(face_head + scans[i, :lengths[i]].tobytes())
         else:
             px = crops_dev[i].cpu().numpy()
-            files.append(_host_jpeg(px[..., 0] if px.ndim == 3 and c == 1 else px, quality))
+            files.append(_host_jpeg(px[..., 0] if px.ndim == 3 and c == 1 else px, quality, ss, optimize))
     return files

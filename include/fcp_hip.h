@@ -459,6 +459,77 @@ int fcp_jpeg_encode_u8(const uint8_t* crops, int f, int h, int w, int channels, 
                        uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths,
                        void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
 
+/* The same encoder with the caller's chroma subsampling and, optionally,
+ * Huffman tables made for every face: byte for byte what
+ * libjpeg-turbo writes after the SOS header with these settings (Pillow's
+ * subsampling= and optimize=).  fcp_jpeg_encode_u8 is this call with
+ * subsampling 2 and optimize 0; everything said there about out, lengths,
+ * capacity and quality holds here.
+ * subsampling: 0 is 4:4:4, 1 is 4:2:2, 2 is 4:2:0; ignored for gray.  An MCU
+ * is hs * vs Y blocks row by row (1x1, 2x1, 2x2), then Cb, then Cr; Y
+ * positions past the block grid are dummy blocks (a zero DC difference and an
+ * end-of-block).  Chroma samples: positions past the image repeat the last
+ * row / column of the full-resolution plane before any averaging; 4:4:4 takes
+ * the pixel's own Cb / Cr; 4:2:2 takes (c(y,2x) + c(y,2x+1) + bias) >> 1 with
+ * bias 0 in even and 1 in odd output columns (libjpeg's h2v1_downsample);
+ * 4:2:0 is the 2x2 average with bias 1, 2.
+ * optimize: 0 codes with the standard tables; `tables` may be NULL and is not
+ * touched.  1 codes every face with the tables libjpeg's optimize_coding
+ * makes for it (see fcp_jpeg_huffman_tables) and writes them to `tables`,
+ * (f,4,272) bytes: per face four records in the order Y DC, Y AC, chroma DC,
+ * chroma AC, each 16 counts of codes per length 1..16 followed by up to 256
+ * symbols in code order, zero padded.  Every byte of every record is written;
+ * for gray, records 2 and 3 are zeros.  The host builds the face's DHT
+ * segments from them (jpegenc.jpeg_header).
+ * With optimised tables a DC code may be 16 bits long as well, so a block
+ * costs at most 27 + 63 * 26 = 1665 bits, 417 bytes after stuffing.
+ * workspace: fcp_jpeg_workspace_bytes_ex(f,h,w,channels,subsampling,optimize)
+ * bytes, 16-byte aligned; with optimize 0 and subsampling 2 that is
+ * fcp_jpeg_workspace_bytes; with optimize 1 the unstuffed bits are sized for
+ * 1665 bits a block and 2 x 4096 bytes per face (symbol counts, code tables)
+ * are added.
+ * One memset and four launches, six with optimize (a histogram and a table
+ * launch); no host round trip, one stream, nothing allocated, the same bytes
+ * from run to run; nothing is written outside out[i][0..capacity), lengths,
+ * tables and the workspace.
+ * Refused with a message, before any HIP call: everything fcp_jpeg_encode_u8
+ * refuses; a subsampling outside 0..2; an optimize other than 0 / 1; optimize
+ * with a null tables; a face whose blocks times the worst case of a block
+ * (1658 bits, 1665 with optimize) exceed 2^32 - 1, the range of the bit
+ * offsets (4:4:4 at 8192 x 8192 does, 4:2:2 and 4:2:0 do not); with optimize,
+ * a face with 64 * blocks + 1 >= 9 227 465, the 35th Fibonacci number: below
+ * it no Huffman tree is deeper than 32, the limit of libjpeg's own arrays
+ * (about 144 000 blocks: 4:2:0 crops up to 2048 x 2048, 4:4:4 up to about
+ * 1750 x 1750).  fcp_jpeg_workspace_bytes_ex then returns -1. */
+int64_t fcp_jpeg_workspace_bytes_ex(int f, int h, int w, int channels, int subsampling, int optimize);
+int fcp_jpeg_encode_ex_u8(const uint8_t* crops, int f, int h, int w, int channels, int quality,
+                          int subsampling, int optimize,
+                          uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths,
+                          uint8_t* tables, void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
+
+/* libjpeg's jpeg_gen_optimal_table for n rows of 256 symbol frequencies
+ * (device memory, 4-byte aligned), one wave per row: a pseudo-symbol 256 of
+ * frequency 1 joins the row (it keeps the all-ones code free); while two
+ * non-zero entries are left, c1 is the entry with the smallest non-zero
+ * frequency, the LARGEST index among equals, c2 the same search without c1;
+ * freq[c1] += freq[c2], freq[c2] = 0, and the code size of every symbol under
+ * c1 and under c2 grows by one, c2's symbols joining c1's.  bits[len] counts
+ * the symbols of each size up to 32; for i from 32 down to 17, while
+ * bits[i] > 0: j = i - 2 stepping down while bits[j] == 0, bits[i] -= 2,
+ * bits[i-1] += 1, bits[j+1] += 2, bits[j] -= 1; one code is taken from the
+ * longest non-empty length (the pseudo-symbol's).  Symbols are ordered by
+ * code size (before the limit), then by value, and get the canonical codes of
+ * the limited lengths in that order.
+ * tables (n,272): row i's record as described above.  codes (n,256), or NULL:
+ * code | length << 16 by symbol, 0 for a symbol without a code.  A row of
+ * zeros gives a record (and codes) of zeros.
+ * Precondition: a row sums to less than 9 227 464, so that no code size
+ * exceeds 32 (fcp_jpeg_encode_ex_u8 guarantees it by its refusal); beyond it
+ * the tables mean nothing, but nothing outside tables and codes is written.
+ * One launch.  n == 0 is a no-op; n < 0 or > 262140, a null freq / tables or
+ * a misaligned freq / codes fail with a message, before any HIP call. */
+int fcp_jpeg_huffman_tables(const uint32_t* freq, int n, uint8_t* tables, uint32_t* codes, fcp_stream_t stream);
+
 /* Background replacement of crops (f,h,w,3) uint8 RGB from label maps
  * (f,h,w) uint8, in integers throughout:
  *   m     = 255 where the label is below 32 and that bit of class_bits is
