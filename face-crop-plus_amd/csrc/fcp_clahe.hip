@@ -51,13 +51,13 @@
 // g = 16) give blocks of four pixels, which is a size nobody crops to.  The cell borders are found with the very float
 // expression the pixels use (it is monotonic in y), so a lane's floor(tyf) IS the cell index of its block, also where
 // y inv_th rounds across a border.  Blocks of cells that the crop does not reach (the extension) leave at once.
-// Crop bytes move as in fcp_matte.hip: four pixels per lane, read as the aligned dwords that hold at least one of their
-// bytes and shifted, written as three dwords when the group is whole and aligned and as bytes otherwise.  Rows are 3 w
-// bytes and start at any byte; no byte outside the arrays is written, and no dword is read that holds none of their
-// bytes.  Every output pixel depends on its own input pixel and on the LUTs only, so out may be the crops.
+// Crop bytes move four pixels per lane, by the rules of fcp_crop_bytes.h.  Rows are 3 w bytes and start at any byte; no
+// byte outside the arrays is written, and no dword is read that holds none of their bytes.  Every output pixel depends
+// on its own input pixel and on the LUTs only, so out may be the crops.
 // LDS 1 KiB, fewer than 64 VGPRs: 8 workgroups per CU (the wave slots).  A 256 x 256 crop at g = 8 is 49 blocks of 32 x 32
 // and 32 half or quarter ones; it moves 6 bytes per pixel here and 3 in the LUT kernel, 9 in all.
 #include "fcp_common.h"
+#include "fcp_crop_bytes.h"
 #include "fcp_hip.h"
 
 #include <cmath>
@@ -72,30 +72,20 @@ constexpr int kMaxSide = 4096;          // area <= 2^24: every int -> float conv
 constexpr int kBlockW = 64;             // pixels of an apply block: 16 groups of four, 32 rows, inside one cell
 constexpr int kBlockH = 32;
 
-__device__ __forceinline__ bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 __device__ __forceinline__ uint32_t luma(uint32_t r, uint32_t g, uint32_t b) {
   return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;       // at most (16384 * 255 + 8192) >> 14 = 255
 }
 
 __device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
 
-// The npx (1..4) RGB pixels at cp as px[j] = R | G << 8 | B << 16, from the aligned dwords that hold their 3 npx bytes
-// (every dword read holds at least one of them).
+// The npx (1..4) RGB pixels at cp as px[j] = R | G << 8 | B << 16.
 __device__ __forceinline__ void load_group(const uint8_t* cp, int npx, uint32_t px[4]) {
-  const int skew = (int)(reinterpret_cast<uintptr_t>(cp) & 3), nbytes = skew + 3 * npx;
-  const uint32_t* p = reinterpret_cast<const uint32_t*>(cp - skew);
-  const uint32_t d0 = p[0];
-  const uint32_t d1 = nbytes > 4 ? p[1] : 0u;
-  const uint32_t d2 = nbytes > 8 ? p[2] : 0u;
-  const uint32_t d3 = nbytes > 12 ? p[3] : 0u;
-  const int sh = 8 * skew;
-  const uint32_t c0 = (uint32_t)((((uint64_t)d1 << 32) | d0) >> sh), c1 = (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh),
-                 c2 = (uint32_t)((((uint64_t)d3 << 32) | d2) >> sh);
-  px[0] = c0 & 0xffffffu;
-  px[1] = ((c0 >> 24) | (c1 << 8)) & 0xffffffu;
-  px[2] = ((c1 >> 16) | (c2 << 16)) & 0xffffffu;
-  px[3] = c2 >> 8;
+  uint32_t c[3];
+  fcp_crop_bytes::load_rgb(cp, npx, c);
+  px[0] = c[0] & 0xffffffu;
+  px[1] = ((c[0] >> 24) | (c[1] << 8)) & 0xffffffu;
+  px[2] = ((c[1] >> 16) | (c[2] << 16)) & 0xffffffu;
+  px[3] = c[2] >> 8;
 }
 
 __global__ void __launch_bounds__(kThreads) clahe_lut_kernel(const uint8_t* __restrict__ crops, int h, int w, int grid, int th,
@@ -250,17 +240,7 @@ __global__ void __launch_bounds__(kThreads) clahe_apply_kernel(const uint8_t* cr
         }
       }
     }
-    uint8_t* op = out + pixel * 3;
-    if (npx == 4 && aligned4(op)) {
-      uint32_t* q = reinterpret_cast<uint32_t*>(op);
-      q[0] = o[0];
-      q[1] = o[1];
-      q[2] = o[2];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 12; ++k)
-        if (k < 3 * npx) op[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
-    }
+    fcp_crop_bytes::store_rgb(out + pixel * 3, npx, o);
   }
 }
 

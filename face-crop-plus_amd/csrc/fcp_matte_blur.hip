@@ -2,14 +2,13 @@
 // what is behind the subject is kept and blurred, by a wide Gaussian over the BACKGROUND pixels only, divided by the
 // Gaussian weight of the background pixels it saw (a plain blur would smear the subject outward into a halo).
 //
-//   m(y,x)    = 255 if l(y,x) < 32 and bit l(y,x) of class_bits is set, else 0                  fcp_matte.hip's mask
-//   alpha     = the alpha of fcp_matte_u8 for this feather (0, 3, 5, 7; reflect-101; (sum + 32768) >> 16)
+//   m, alpha  = the mask and the feathered alpha of fcp_feather.h (feather 0, 3, 5, 7): those of fcp_matte_u8
 //   b(y,x)    = 1 where m == 0, else 0                                                          from the HARD mask
 //   t[0..r]   : all >= 1, t[0] + 2 sum(t[1..r]) == 4096, 3 <= r <= 48; made on the host from sigma, data here
 //   D(y,x)    = sum_j sum_i t|j| t|i| b(y+j, x+i)                                               taps inside the image only
 //   N_ch(y,x) = sum_j sum_i t|j| t|i| b(y+j, x+i) c_ch(y+j, x+i)                                the same taps
 //   B_ch(y,x) = D > 0 ? (N_ch + D / 2) / D : c_ch(y,x)                                          integer division
-//   out_ch    = (c_ch alpha + B_ch (255 - alpha) + 127) / 255                                   fcp_matte.hip's over255
+//   out_ch    = (c_ch alpha + B_ch (255 - alpha) + 127) / 255                                   fcp_feather.h's over255
 //
 // Positions outside the image contribute to neither N nor D: the normalisation is the border rule.  Bounds, all in
 // unsigned 32 bits: a horizontal sum is at most 255 * 4096 < 2^20; N <= 255 * 4096^2 = 4 278 190 080 < 2^32 and
@@ -30,9 +29,9 @@
 //
 //   blur_cols_kernel, workgroups of 256 lanes over (64 rows x 16 columns, face), four pixels of a row per lane.  A
 //   workgroup stages the 16-byte sums of its columns for rows y0 - r .. y0 + 63 + r (zero outside the image), and the
-//   mask tile and its horizontal feather pass exactly as fcp_matte.hip does; then a lane runs the 2 r + 1 taps down its
-//   four columns (four 16-byte LDS reads per tap, 16 accumulators), divides, recomputes alpha, reads the 12 crop
-//   bytes of its group, composites and writes out (and alpha) once.  LDS per workgroup at r = 48 and feather 7:
+//   feather's tile (fcp_feather.h: Tile::stage); then a lane runs the 2 r + 1 taps down its four columns (four 16-byte
+//   LDS reads per tap, 16 accumulators), divides, runs the feather's vertical pass, reads the 12 crop bytes of its
+//   group, composites and writes out (and alpha) once.  LDS per workgroup at r = 48 and feather 7:
 //   160 x 16 x 16 B = 40960 B of sums + 70 x 32 B + 70 x 24 B of feather + 388 B of taps = 45268 B: 3 workgroups per CU
 //   (160 KiB), 12 of 32 wave slots; at r = 24 (sigma 8) it is 28672 + 4308 B: 4 workgroups, the 5th misses by 1 KiB.
 //
@@ -47,19 +46,21 @@
 // The result is the same from run to run: integer sums in a fixed order, one writer per byte.
 //
 // Rows are 3 w bytes and start at any byte.  The rows pass reads crop and label bytes as bytes.  The columns pass moves
-// crop, out and alpha bytes as fcp_matte.hip does: crops as the aligned dwords that hold at least one byte of the group,
-// out and alpha through dwords when the group is whole and aligned, through bytes otherwise.  No byte outside the
-// arrays is written, and no dword is read that does not hold a byte of them.
+// crop, out, alpha and the feather-0 labels by the rules of fcp_crop_bytes.h.  No byte outside the arrays is written,
+// and no dword is read that does not hold a byte of them.
 #include "fcp_common.h"
+#include "fcp_crop_bytes.h"
+#include "fcp_feather.h"
 #include "fcp_hip.h"
 
 namespace {
 
+using namespace fcp_crop_bytes;
+using namespace fcp_feather;
+
 constexpr int kThreads = 256;
 constexpr int kMinRadius = 3;
 constexpr int kMaxRadius = 48;
-constexpr int kMaxSide = 8192;
-constexpr int kClasses = 19;
 constexpr uint32_t kTapSum = 4096;
 
 // rows pass
@@ -70,39 +71,10 @@ constexpr int kRowPitch = kRowTileW + 2 * kMaxRadius;   // dwords of a staged ro
 // columns pass
 constexpr int kTileW = 16;              // output pixels of a tile row: 4 groups of four
 constexpr int kTileH = 64;
-constexpr int kGroups = kTileW / 4;
-constexpr int kMaskPitch = kTileW + 8;  // bytes of a staged mask row: 16 + 2 * 3 halo, rounded up to dwords
 
 struct BlurTaps {
   uint16_t t[kMaxRadius + 1];           // 49 x 16 bit in the kernel argument block
 };
-
-__host__ __device__ constexpr int tap(int r, int i) {   // fcp_matte.hip's feather taps
-  return r == 1 ? (i == 1 ? 128 : 64)
-       : r == 2 ? (i == 2 ? 96 : (i == 1 || i == 3) ? 64 : 16)
-                : (i == 3 ? 72 : (i == 2 || i == 4) ? 56 : (i == 1 || i == 5) ? 28 : 8);
-}
-
-// BORDER_REFLECT_101, iterated: the triangle wave of period 2 (n - 1); a dimension of size 1 maps everything to 0.
-__device__ __forceinline__ int reflect101(int p, int n) {
-  if (p >= 0 && p < n) return p;
-  if (n == 1) return 0;
-  const int period = 2 * (n - 1);
-  p %= period;
-  if (p < 0) p += period;
-  return p < n ? p : period - p;
-}
-
-__device__ __forceinline__ uint32_t mask_of(uint32_t label, uint32_t bits) {
-  return (label < 32u && ((bits >> (label & 31u)) & 1u)) ? 255u : 0u;
-}
-
-__device__ __forceinline__ bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
-__device__ __forceinline__ uint32_t over255(uint32_t c, uint32_t a, uint32_t b) {
-  const uint32_t u = c * a + b * (255u - a) + 128u;
-  return (u + (u >> 8)) >> 8;
-}
 
 // the mirrored tap table, 2 r + 1 dwords: entry k is t|k - r|
 __device__ __forceinline__ void stage_taps(uint32_t* tl, const BlurTaps& taps, int radius) {
@@ -153,11 +125,10 @@ __global__ void __launch_bounds__(kThreads) blur_rows_kernel(const uint8_t* __re
   }
 }
 
-// Bytes of dynamic LDS of blur_cols_kernel<R>: the sums, the feather's H rows and mask rows, the taps.
+// Bytes of dynamic LDS of blur_cols_kernel<R>: the sums, the feather's tile, the taps.
 template <int R>
 constexpr size_t cols_lds_bytes(int radius) {
-  return (size_t)(kTileH + 2 * radius) * kTileW * sizeof(uint4) +
-         (R > 0 ? (size_t)(kTileH + 2 * R) * (kGroups * sizeof(uint2) + kMaskPitch) : 0) +
+  return (size_t)(kTileH + 2 * radius) * kTileW * sizeof(uint4) + Tile<R, kTileW, kTileH>::kBytes +
          (2 * kMaxRadius + 1) * sizeof(uint32_t);
 }
 
@@ -167,17 +138,16 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
                                                              const uint4* __restrict__ sums, int h, int w, int tiles_x,
                                                              uint32_t bits, BlurTaps taps, int radius, uint8_t* out,
                                                              uint8_t* alpha) {
+  using Feather = Tile<R, kTileW, kTileH>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* col = reinterpret_cast<uint4*>(smem);                                    // (kTileH + 2 r) rows of kTileW sums
-  uint2* hsum = reinterpret_cast<uint2*>(col + (kTileH + 2 * radius) * kTileW);   // R > 0: H rows, 8 bytes per group
-  uint32_t* mask32 = reinterpret_cast<uint32_t*>(hsum + (R > 0 ? (kTileH + 2 * R) * kGroups : 0));
-  uint32_t* tl = mask32 + (R > 0 ? (kTileH + 2 * R) * (kMaskPitch / 4) : 0);
+  uint2* hsum = reinterpret_cast<uint2*>(col + (kTileH + 2 * radius) * kTileW);   // R > 0: the feather's tile
+  uint32_t* tl = reinterpret_cast<uint32_t*>(hsum) + Feather::kBytes / 4;
   const int f = blockIdx.y;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int x0 = tx * kTileW, y0 = ty * kTileH;
   const int nrows = min(kTileH, h - y0);
   const int groups = (min(kTileW, w - x0) + 3) >> 2;
-  const uint8_t* lab = labels + (size_t)f * h * w;
 
   stage_taps(tl, taps, radius);
   // sums of rows y0 - r .. y0 + nrows + r - 1, all kTileW columns: zero outside the image
@@ -188,32 +158,7 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
     if (y >= 0 && y < h && x < w) v = sums[((size_t)f * h + y) * w + x];
     col[i] = v;
   }
-  if constexpr (R > 0) {
-    // fcp_matte.hip: mask bytes of rows y0 - R .. y0 + nrows + R - 1, columns x0 - R .. x0 + 4 groups + R - 1
-    const int mdw = (4 * groups + 2 * R + 3) >> 2;
-    for (int i = threadIdx.x; i < (nrows + 2 * R) * mdw; i += kThreads) {
-      const int tr = i / mdw, d = i - tr * mdw;
-      const uint8_t* row = lab + (size_t)reflect101(y0 - R + tr, h) * w;
-      uint32_t v = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v |= mask_of(row[reflect101(x0 - R + 4 * d + j, w)], bits) << (8 * j);
-      mask32[tr * (kMaskPitch / 4) + d] = v;
-    }
-    __syncthreads();
-    // H of the same rows: output x of the tile sums mask bytes x .. x + 2 R
-    for (int i = threadIdx.x; i < (nrows + 2 * R) * groups; i += kThreads) {
-      const int tr = i / groups, g = i - tr * groups;
-      const uint32_t* m = mask32 + tr * (kMaskPitch / 4) + g;
-      const uint32_t d[3] = {m[0], m[1], R == 3 ? m[2] : 0u};
-      uint32_t s[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int t = 0; t <= 2 * R; ++t) s[j] += (uint32_t)tap(R, t) * ((d[(j + t) >> 2] >> (8 * ((j + t) & 3))) & 255u);
-      }
-      hsum[tr * kGroups + g] = make_uint2(s[0] | (s[1] << 16), s[2] | (s[3] << 16));
-    }
-  }
+  if constexpr (R > 0) Feather::stage(hsum, labels + (size_t)f * h * w, h, w, x0, y0, nrows, groups, bits, kThreads);
   __syncthreads();
 
   for (int i = threadIdx.x; i < nrows * groups; i += kThreads) {
@@ -238,51 +183,11 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
     }
 
     uint32_t a[4];
-    if constexpr (R > 0) {
-      uint32_t s[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int t = 0; t <= 2 * R; ++t) {
-        const uint2 v = hsum[(r + t) * kGroups + g];
-        s[0] += (uint32_t)tap(R, t) * (v.x & 0xffffu);
-        s[1] += (uint32_t)tap(R, t) * (v.x >> 16);
-        s[2] += (uint32_t)tap(R, t) * (v.y & 0xffffu);
-        s[3] += (uint32_t)tap(R, t) * (v.y >> 16);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[j] = (s[j] + 32768u) >> 16;
-    } else {
-      const uint8_t* lp = labels + pixel;
-      if (npx == 4 && aligned4(lp)) {
-        const uint32_t v = *reinterpret_cast<const uint32_t*>(lp);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] = mask_of((v >> (8 * j)) & 255u, bits);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] = j < npx ? mask_of(lp[j], bits) : 0u;
-      }
-    }
-    if (alpha != nullptr) {
-      uint8_t* ap = alpha + pixel;
-      if (npx == 4 && aligned4(ap)) {
-        *reinterpret_cast<uint32_t*>(ap) = a[0] | (a[1] << 8) | (a[2] << 16) | (a[3] << 24);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (j < npx) ap[j] = (uint8_t)a[j];
-      }
-    }
+    Feather::alpha(hsum, r, g, labels + pixel, npx, bits, a);
+    if (alpha != nullptr) store_u8(alpha + pixel, npx, a);
 
-    // the 3 * npx crop bytes of the group, from the aligned dwords that hold them (every dword read holds at least one)
-    const uint8_t* cp = crops + pixel * 3;
-    const int skew = (int)(reinterpret_cast<uintptr_t>(cp) & 3), nbytes = skew + 3 * npx;
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(cp - skew);
-    const uint32_t d0 = p[0];
-    const uint32_t d1 = nbytes > 4 ? p[1] : 0u;
-    const uint32_t d2 = nbytes > 8 ? p[2] : 0u;
-    const uint32_t d3 = nbytes > 12 ? p[3] : 0u;
-    const int sh = 8 * skew;
-    const uint32_t c[3] = {(uint32_t)((((uint64_t)d1 << 32) | d0) >> sh), (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh),
-                           (uint32_t)((((uint64_t)d3 << 32) | d2) >> sh)};
+    uint32_t c[3];
+    load_rgb(crops + pixel * 3, npx, c);
     uint32_t o[3] = {0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 12; ++k) {            // byte k of the group: pixel k / 3, channel k % 3
@@ -291,17 +196,7 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
       const uint32_t bv = dd > 0u ? (dn[k / 3][1 + k % 3] + (dd >> 1)) / dd : cv;
       o[k >> 2] |= over255(cv, a[k / 3], bv) << (8 * (k & 3));
     }
-    uint8_t* op = out + pixel * 3;
-    if (npx == 4 && aligned4(op)) {
-      uint32_t* q = reinterpret_cast<uint32_t*>(op);
-      q[0] = o[0];
-      q[1] = o[1];
-      q[2] = o[2];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 12; ++k)
-        if (k < 3 * npx) op[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
-    }
+    store_rgb(out + pixel * 3, npx, o);
   }
 }
 

@@ -6,11 +6,13 @@
 //   S1 = sum L,  S2 = sum L*L   over the crop, as 64-bit integers          (the host divides: align.sharpness_score)
 //
 // One launch over (row strip, face) workgroups of 256 lanes.  A workgroup turns the RGB bytes of its strip and of the row
-// above and below it (reflected at the crop's edge) into gray bytes in LDS, four pixels per lane and aligned dword store,
+// above and below it (reflected at the crop's edge) into gray bytes in LDS, four pixels per lane (read by the rules of
+// fcp_crop_bytes.h: rows are 3 w bytes and start at any byte) and aligned dword store,
 // adds the reflected column left and right of every row, then every lane evaluates L for four pixels of a row from three
 // dword and two byte LDS reads.  Integer sums commute: wave shuffle, LDS across the four waves, one pair of 64-bit atomic
 // adds per workgroup, so the result is the same from run to run and for every strip height.
 #include "fcp_common.h"
+#include "fcp_crop_bytes.h"
 #include "fcp_hip.h"
 
 namespace {
@@ -49,25 +51,16 @@ __global__ void __launch_bounds__(kThreads) crop_sharpness_kernel(const uint8_t*
   const int nrows = min(rows, h - y0);
   const uint8_t* face = crops + (size_t)f * h * w * 3;
 
-  // RGB -> gray, rows y0 - 1 .. y0 + nrows.  A lane takes the 12 bytes of four pixels.  Rows are 3 * w bytes and start at
-  // any byte, so it reads the aligned dwords that hold them and shifts: every dword it touches holds at least one byte of
-  // the row (never a page the crops do not own), consecutive lanes read consecutive 12-byte pieces.
+  // RGB -> gray, rows y0 - 1 .. y0 + nrows.  A lane takes the 12 bytes of four pixels, consecutive lanes consecutive
+  // 12-byte pieces.
   for (int i = threadIdx.x; i < (nrows + 2) * chunks; i += kThreads) {
     const int r = i / chunks, c = i - r * chunks;
     int y = y0 - 1 + r;
     y = y < 0 ? (h > 1 ? 1 : 0) : (y >= h ? (h > 1 ? h - 2 : 0) : y);
     const int npx = min(4, w - 4 * c);
-    const uint8_t* first = face + ((size_t)y * w + 4 * c) * 3;
-    const int skew = (int)(reinterpret_cast<uintptr_t>(first) & 3), nbytes = skew + 3 * npx;   // from the aligned dword on
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(first - skew);
-    const uint32_t d0 = p[0];
-    const uint32_t d1 = nbytes > 4 ? p[1] : 0u;
-    const uint32_t d2 = nbytes > 8 ? p[2] : 0u;
-    const uint32_t d3 = nbytes > 12 ? p[3] : 0u;
-    const int sh = 8 * skew;
-    const uint32_t w0 = (uint32_t)((((uint64_t)d1 << 32) | d0) >> sh);
-    const uint32_t w1 = (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh);
-    const uint32_t w2 = (uint32_t)((((uint64_t)d3 << 32) | d2) >> sh);
+    uint32_t px[3];
+    fcp_crop_bytes::load_rgb(face + ((size_t)y * w + 4 * c) * 3, npx, px);
+    const uint32_t w0 = px[0], w1 = px[1], w2 = px[2];
     // pixels past the row's end (npx < 4) get a meaningless gray: bytes 4 + w .. of the tile row, which nothing reads
     // before the column pass below has written the one that matters
     const uint32_t g0 = gray_of(w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u);
