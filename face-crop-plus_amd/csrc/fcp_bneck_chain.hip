@@ -98,14 +98,6 @@ constexpr int wgs_per_cu(int cw, int cn, bool has_c2, bool direct = false) {
 
 __device__ __forceinline__ int swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 // PATCH (the conv2 forms): the tile is an 8 x 16 PATCH of one image instead of 128 consecutive pixels, and phase 1 stages the
 // patch's (8 + 2) x (16 + 2) halo ONCE per 32-channel slice; the nine taps read it at shifted rows (the scheme of
 // conv3x3_halo_f16x3).  A tile of consecutive pixels fetches a 128-byte operand row per pixel, tap and slice: 288 of the ~720
@@ -208,7 +200,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int rr = 0; rr < 16; ++rr) {
-        const int row = wm * 64 + i * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+        const int row = wm * 64 + i * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;   // mfma_c_row (fcp_conv_common.h), spelled out: see there
         Cs[row * C + wn * 32 + l31] = acc1[i][rr];
       }
     __syncthreads();
@@ -227,11 +219,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
         const f32x4 b = *reinterpret_cast<const f32x4*>(Cs + row * C + ccol + 4);
         float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float x = v[e] * ws8[e] + b8[e];
-          x = x >= 0.f ? x : x * 0.f;
-          v[e] = x * 1.f;
-        }
+        for (int e = 0; e < 8; ++e) v[e] = conv_value_relu(v[e], ws8[e], b8[e]);
         u32x4_t hi, lo;
         split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);
         const int q = (ccol & 31) >> 3, sw = swz(row);
@@ -293,13 +281,13 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
 #pragma unroll
     for (int i = 0; i < 2; ++i) hr0[i] = (wm * 4 + i * 2 + (l31 >> 4)) * 18 + (l31 & 15);
     const char* Bw = lds + BST_OFF + (wn * 32 + l31) * ROWB;
-    static_for<0, NSTEP>([&](auto gc) {
+    fcp_static_for<0, NSTEP>([&](auto gc) {
       constexpr int g = decltype(gc)::value;
       // the filter slices of step g have landed (with the halo patch, at g = 0) and every wave has read those of step g - 1
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      static_for<0, TPB>([&](auto uc) {
+      fcp_static_for<0, TPB>([&](auto uc) {
         constexpr int kt = g * TPB + decltype(uc)::value, cs = kt / 9, tap = kt % 9;   // K order: channel slice outer, taps inner
         const char* Bb = Bw + (g & 1) * BSTG + decltype(uc)::value * BSL;
         f16x8 ah[2][2], al[2][2], bh[2], bl[2];
@@ -609,19 +597,19 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
         else acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pch[1], wy[t], acc3[t], 0, 0, 0);
       }
     };
-    static_for<0, CS / BG>([&](auto gc) {
+    fcp_static_for<0, CS / BG>([&](auto gc) {
       constexpr int g = decltype(gc)::value;
       if constexpr (g + 1 < CS / BG) read_b2((g + 1) & 1, g + 1);  // next group's fragments under this group's MFMAs
-      static_for<0, 2 * BG>([&](auto tc) {
+      fcp_static_for<0, 2 * BG>([&](auto tc) {
         constexpr int q = decltype(tc)::value / 2, s = decltype(tc)::value % 2, sl = g * BG + q, trip = 2 * sl + s;
-        static_for<0, 3>([&](auto ec) {
+        fcp_static_for<0, 3>([&](auto ec) {
           constexpr int term = decltype(ec)::value;
           if constexpr (term == 0) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sl][s], bh[g & 1][q][s], acc2, 0, 0, 0);
           else if constexpr (term == 1) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sl][s], bl[g & 1][q][s], acc2, 0, 0, 0);
           else acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sl][s], bh[g & 1][q][s], acc2, 0, 0, 0);
           if constexpr (ROT) {
             __builtin_amdgcn_sched_barrier(0);
-            if (prev) static_for<0, PQ>([&](auto pc) { p3_step(std::integral_constant<int, (3 * trip + term) * PQ + decltype(pc)::value>{}); });
+            if (prev) fcp_static_for<0, PQ>([&](auto pc) { p3_step(std::integral_constant<int, (3 * trip + term) * PQ + decltype(pc)::value>{}); });
             __builtin_amdgcn_sched_barrier(0);
           }
         });
@@ -645,9 +633,9 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
       const int q = l31 >> 3;
 #pragma unroll
       for (int rr = 0; rr < 16; ++rr) {
-        const int row = wave * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+        const int row = wave * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;   // mfma_c_row, spelled out
         const int piece = ((l31 & 4) ? (4 + q) : q) ^ swz(row);
-        *reinterpret_cast<float*>(lds + CT_OFF + row * ROWB + (piece << 4) + (l31 & 3) * 4) = acc2[rr] * ws_l + b_l;
+        *reinterpret_cast<float*>(lds + CT_OFF + row * ROWB + (piece << 4) + (l31 & 3) * 4) = conv_scale_bias(acc2[rr], ws_l, b_l);
       }
     }
     // ---- epilogue of conv3 for this chunk (own rows: LDS accesses of one wave execute in order, no barrier):
@@ -668,10 +656,8 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
       if constexpr (HAS_RES) join8(rhi[it], rlo[it], r);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float x = v[e];
-        if constexpr (HAS_RES) x += r[e];
-        x = x >= 0.f ? x : x * 0.f;
-        v[e] = x * 1.f;
+        if constexpr (HAS_RES) v[e] = conv_finish_relu(v[e], r[e]);
+        else v[e] = conv_finish_relu(v[e]);
       }
       split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, ohi[it], olo[it]);
       if constexpr (HAS_P3) {                                      // ... and T3, conv1's operand (the expand form has no phase 3)
@@ -784,7 +770,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int rr = 0; rr < 16; ++rr) {
-        const int row = wave * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+        const int row = wave * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;   // mfma_c_row, spelled out
         Cs[row * 64 + t * 32 + l31] = acc3[CN == 64 ? t : 2 * hh + t][rr];
       }
     __syncthreads();
@@ -804,14 +790,10 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
       const f32x4 b = *reinterpret_cast<const f32x4*>(Cs + row * 64 + ccol + 4);
       float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float x = v[e] * ws8[e] + b8[e];
-        x = x >= 0.f ? x : x * 0.f;
-        v[e] = x * 1.f;
-      }
+      for (int e = 0; e < 8; ++e) v[e] = conv_value_relu(v[e], ws8[e], b8[e]);
       if (m < 0) continue;
-      u32x4_t hi, lo;
-      split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);
+      u32x4_t hi, lo;                                              // pack8 / store8 (fcp_conv_common.h) for split32, spelled out: through
+      split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);   // them the compiler orders this kernel's code differently
       char* ob = reinterpret_cast<char*>(p.t1n) + m * p.t1n_ld * 4 + split_chan_off(co);
       if (p.nt_store) {
         __builtin_nontemporal_store(hi, reinterpret_cast<u32x4_t*>(ob));

@@ -27,7 +27,7 @@ struct ConvK {
   float* out;
   const float* res1;
   const float* res2;
-  int n, in_h, in_w, ph, pw, cin, in_ld, in_up2;
+  int n, in_h, in_w, ph, pw, cin, in_ld, in_up2;   // (cin: no kernel reads it; without it the kernarg layout shifts and two halo kernels spill more SGPRs: profiles/conv_epilogue.md)
   int cout, kh, kw, stride, pad, out_h, out_w, out_ld;
   int pad_h;      // rows of zero padding above input row 0 (= pad - band_top: fcp_conv_desc.band_top / band_bottom)
   int M, ktiles, ctiles, wrow;
@@ -78,15 +78,198 @@ __device__ __forceinline__ TapPiece make_tap_piece(const ConvK& p, unsigned pbas
   return t;
 }
 
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+
+// Mixed-precision FMA (v_fma_mix_f32: every source is an f32 register or one binary16 half of a register, one rounding):
+//   fcp_mix_sum(h, l, HI)  = float(h.half) + float(l.half)      — exactly what v_cvt_f32_f16 x2 + v_add_f32 give (the conversions
+//   fcp_mix_diff(x, h, HI) = x - float(h.half)                    are exact, so there is one rounding either way), in ONE instruction.
+// The epilogues of every fp16x3 kernel decode / encode 8-16 values per lane and chunk with these; as separate converts and
+// adds that was a third of the bottleneck-chain kernel's epilogue instructions.
+template <int HI>
+__device__ __forceinline__ float fcp_mix_sum(unsigned h, unsigned l) {
+  float r;
+  const float one = 1.0f;
+  if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h), "s"(one), "v"(l));
+  else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h), "s"(one), "v"(l));
+  return r;
+}
+template <int HI>
+__device__ __forceinline__ float fcp_mix_diff(float x, unsigned h) {
+  float r;
+  const float minus_one = -1.0f;
+  if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "s"(minus_one), "v"(x));
+  else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "s"(minus_one), "v"(x));
+  return r;
+}
+
+// 8 fp32 -> 8 hi + 8 lo binary16 (round-toward-zero packs; lo = x - hi is exact in fp32).  Idempotent on
+// values that already are a hi + lo sum, so elementwise kernels may decode / re-encode freely.
+__device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, u32x4_t& hi, u32x4_t& lo) {
+  const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const unsigned hu = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x[2 * q], x[2 * q + 1]));
+    const float r0 = fcp_mix_diff<0>(x[2 * q], hu);
+    const float r1 = fcp_mix_diff<1>(x[2 * q + 1], hu);
+    hi[q] = hu;
+    lo[q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
+  }
+}
+// One pair of split8 (x0 in the low halves of hu / lu), for kernels that own two channels per thread.  split8 is not written
+// over it: the compiler then pairs its eight conversions differently and the chain kernels' code changes.
+__device__ __forceinline__ void split2(float x0, float x1, unsigned& hu, unsigned& lu) {
+  hu = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x0, x1));
+  lu = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(fcp_mix_diff<0>(x0, hu), fcp_mix_diff<1>(x1, hu)));
+}
+// inverse: value = float(hi) + float(lo) (exact)
+__device__ __forceinline__ void join8(const u32x4_t& hi, const u32x4_t& lo, float (&x)[8]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const unsigned hu = hi[q], lu = lo[q];
+    x[2 * q] = fcp_mix_sum<0>(hu, lu);
+    x[2 * q + 1] = fcp_mix_sum<1>(hu, lu);
+  }
+}
+// byte offset of channel c (multiple of 8) inside a split32 pixel: group (c/32)*128 B, hi at (c%32)*2, lo +64
+__device__ __forceinline__ long split_chan_off(int c) { return (long)(c >> 5) * 128 + (c & 31) * 2; }
+
+// 8 consecutive channels of one pixel from an activation tensor of either format
+__device__ __forceinline__ void load8(const float* base, long pix, int ld, int c, int fmt, float (&x)[8]) {
+  if (fmt == 1) {
+    const char* pb = reinterpret_cast<const char*>(base) + pix * ld * 4 + split_chan_off(c);
+    join8(*reinterpret_cast<const u32x4_t*>(pb), *reinterpret_cast<const u32x4_t*>(pb + 64), x);
+  } else {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(base + pix * ld + c);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(base + pix * ld + c + 4);
+    x[0] = a[0]; x[1] = a[1]; x[2] = a[2]; x[3] = a[3]; x[4] = b[0]; x[5] = b[1]; x[6] = b[2]; x[7] = b[3];
+  }
+}
+
+// 8 finished channels of one pixel as the two 16-byte pieces that are stored: split32 hi | lo, or fp32 channels 0-3 | 4-7
+__device__ __forceinline__ void pack8(const float (&v)[8], int fmt, u32x4_t& a, u32x4_t& b) {
+  if (fmt == 1) {
+    split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, a, b);
+  } else {
+    a = __builtin_bit_cast(u32x4_t, f32x4{v[0], v[1], v[2], v[3]});
+    b = __builtin_bit_cast(u32x4_t, f32x4{v[4], v[5], v[6], v[7]});
+  }
+}
+// ... and their store to channels c .. c + 7 of pixel pix; nt: split32 pieces with non-temporal (streaming) stores
+__device__ __forceinline__ void store8(float* base, long pix, int ld, int c, int fmt, int nt, const u32x4_t& a, const u32x4_t& b) {
+  if (fmt == 1) {
+    char* ob = reinterpret_cast<char*>(base) + pix * ld * 4 + split_chan_off(c);
+    if (nt) {
+      __builtin_nontemporal_store(a, reinterpret_cast<u32x4_t*>(ob));
+      __builtin_nontemporal_store(b, reinterpret_cast<u32x4_t*>(ob + 64));
+    } else {
+      *reinterpret_cast<u32x4_t*>(ob) = a;
+      *reinterpret_cast<u32x4_t*>(ob + 64) = b;
+    }
+  } else {
+    float* dst = base + pix * ld + c;
+    *reinterpret_cast<u32x4_t*>(dst) = a;
+    *reinterpret_cast<u32x4_t*>(dst + 4) = b;
+  }
+}
+// both at once (one branch on the format)
+__device__ __forceinline__ void pack_store8(float* base, long pix, int ld, int c, int fmt, int nt, const float (&v)[8]) {
+  u32x4_t a, b;
+  if (fmt == 1) {
+    pack8(v, 1, a, b);
+    store8(base, pix, ld, c, 1, nt, a, b);
+  } else {
+    pack8(v, 0, a, b);
+    store8(base, pix, ld, c, 0, 0, a, b);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The fused epilogue's arithmetic.  This is the ONE statement of how a conv kernel finishes an output value; the staged
+// (conv_epilogue, conv_epilogue8), register (conv_epilogue_regs), halo-tile, bottleneck-chain and stem epilogues all call
+// it, which is what "every tile choice and every fused form returns the same bits" rests on:
+//
+//     x = acc * wscale + bias            conv_scale_bias
+//     if res1 and res1_pre:      x += r1            \
+//     x = x >= 0 ? x : x * act_slope                 |
+//     x = x * alpha                                  |  conv_finish
+//     if res1 and not res1_pre:  x += r1             |
+//     if res2:                   x = x * alpha2 + r2 /
+//
+// Every operation is rounded on its own (the library is built with -ffp-contract=off).  PART OF THE CONTRACT: under
+// act_slope 0 (ReLU) a negative x becomes x * 0.f = -0.0, not +0.0, and `* alpha` keeps that sign; a fused form that wrote
+// max(x, 0) would differ from the stand-alone kernels in the sign bit of its zeros.  So the constant forms below go through
+// the same multiplications (x * 0.f is not foldable: it is -0.0 for a negative x).
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float conv_scale_bias(float acc, float ws, float b) { return acc * ws + b; }
+
+// The settings as plain values: the fused kernels pass constants.  conv_finish / conv_value take them from a ConvEpi or
+// straight from the launch's ConvK (anything with these six members; res1 / res2 only say whether the term is present).
+struct ConvEpi {
+  bool res1, res1_pre, res2;
+  float act_slope, alpha, alpha2;
+};
+template <typename E>
+__device__ __forceinline__ float conv_finish(const E e, float x, float r1, float r2) {   // e by value: see profiles/conv_epilogue.md
+  if (e.res1 && e.res1_pre) x += r1;
+  x = x >= 0.f ? x : x * e.act_slope;
+  x = x * e.alpha;
+  if (e.res1 && !e.res1_pre) x += r1;
+  if (e.res2) x = x * e.alpha2 + r2;
+  return x;
+}
+template <typename E>
+__device__ __forceinline__ float conv_value(const E& e, float acc, float ws, float b, float r1, float r2) {
+  return conv_finish(e, conv_scale_bias(acc, ws, b), r1, r2);
+}
+// ReLU forms of the fused kernels (act_slope 0, alpha 1): relu(x), relu(x + r1) and relu(acc * ws + b); a negative x gives -0.0
+__device__ __forceinline__ float conv_finish_relu(float x) { return conv_finish(ConvEpi{false, false, false, 0.f, 1.f, 1.f}, x, 0.f, 0.f); }
+__device__ __forceinline__ float conv_finish_relu(float x, float r1) { return conv_finish(ConvEpi{true, true, false, 0.f, 1.f, 1.f}, x, r1, 0.f); }
+__device__ __forceinline__ float conv_value_relu(float acc, float ws, float b) { return conv_finish_relu(conv_scale_bias(acc, ws, b)); }
+
+// Pixel of a resized res1 that output pixel m = (ni, ho, wo) adds: nearest neighbour, floor(o * in / out) clamped to the map
+// (hw = out_h * out_w).
+__device__ __forceinline__ long res1_pixel(const ConvK& p, long m, int hw) {
+  const int ni = (int)(m / hw);
+  const int rem = (int)(m - (long)ni * hw);
+  const int ho = rem / p.out_w;
+  const int wo = rem - ho * p.out_w;
+  int sh = (int)floorf(ho * p.res1_sh);
+  int sw = (int)floorf(wo * p.res1_sw);
+  sh = sh < p.res1_h - 1 ? sh : p.res1_h - 1;
+  sw = sw < p.res1_w - 1 ? sw : p.res1_w - 1;
+  return ((long)ni * p.res1_h + sh) * p.res1_w + sw;
+}
+
+// 32x32 MFMA C/D layout: accumulator register rr (0..15) of lane l holds column l & 31 of this row (half = l >> 5).
+// (fcp_bneck_chain.hip spells the sum out at its three sites: through this function, in either association with the tile's
+// first row, the compiler schedules those kernels differently and puts the two-source pair form into scratch.)
+__device__ __forceinline__ constexpr int mfma_c_row(int rr, int half) { return (rr & 3) + 8 * (rr >> 2) + 4 * half; }
+
+// The accumulators of a workgroup tile leave the MFMA layout through the fp32 tile Cs[BM][BN] (the staged epilogues), then
+// the barrier.  (The last main-loop iteration ended with a barrier: the A/B slices are dead.)
+template <int BN, int TM, int TN, int WTM, int WTN>
+__device__ __forceinline__ void stage_acc_tile(const f32x16 (&acc)[TM][TN], float* Cs, int lane, int wm, int wn) {
+  const int half = lane >> 5;
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int rr = 0; rr < 16; ++rr) {
+        const int row = wm * WTM + i * 32 + mfma_c_row(rr, half);
+        Cs[row * BN + wn * WTN + j * 32 + (lane & 31)] = acc[i][j][rr];
+      }
+  __syncthreads();
+}
+
 // Fused epilogue, shared by both MFMA variants.  `acc` is in the 32x32 MFMA C/D layout.
 template <int BN, int TM, int TN, int WTM, int WTN>
 __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][TN], float* smem, int tile_m,
                                               int tile_n, int tid, int lane, int wm, int wn, int hw) {
-  // ---- epilogue.  The accumulators leave the MFMA layout (col = lane & 31,
-  // row = (r&3) + 8*(r>>2) + 4*(lane>>5)) through LDS, so that every lane owns
+  // ---- epilogue.  The accumulators leave the MFMA layout through LDS (stage_acc_tile), so that every lane owns
   // 16-byte row-major chunks: residual loads and output stores are then
   // float4-wide and a wave covers whole 512-byte..1-KiB runs of the NHWC row.
-  // (The last main-loop iteration ended with a barrier: the A/B slices are dead.)
   constexpr int CPR = BN / 4;             // float4 chunks per tile row
   constexpr int RPP = 256 / CPR;          // rows per pass
   constexpr int PASSES = BM / RPP;
@@ -99,19 +282,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][
 
   const bool pre1 = p.res1 != nullptr && !p.res1_resize && vec;
   const bool pre2 = p.res2 != nullptr && vec;
-  {
-    const int half = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          const int row = wm * WTM + i * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
-          Cs[row * BN + wn * WTN + j * 32 + (lane & 31)] = acc[i][j][rr];
-        }
-  }
-  __syncthreads();
+  stage_acc_tile<BN, TM, TN, WTM, WTN>(acc, Cs, lane, wm, wn);
 
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f}, ws4 = {1.f, 1.f, 1.f, 1.f};
   if (p.bias != nullptr) {
@@ -152,20 +323,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][
       if (pre1) {
         r1 = r1v[i];
       } else if (p.res1 != nullptr) {
-        long roff;
-        if (p.res1_resize) {
-          const int ni = (int)(m / hw);
-          const int rem = (int)(m - (long)ni * hw);
-          const int ho = rem / p.out_w;
-          const int wo = rem - ho * p.out_w;
-          int sh = (int)floorf(ho * p.res1_sh);
-          int sw = (int)floorf(wo * p.res1_sw);
-          sh = sh < p.res1_h - 1 ? sh : p.res1_h - 1;
-          sw = sw < p.res1_w - 1 ? sw : p.res1_w - 1;
-          roff = (((long)ni * p.res1_h + sh) * p.res1_w + sw) * p.res1_ld + co;
-        } else {
-          roff = m * p.res1_ld + co;
-        }
+        const long roff = (p.res1_resize ? res1_pixel(p, m, hw) : m) * p.res1_ld + co;
         if (vec) {
           r1 = *reinterpret_cast<const f32x4*>(p.res1 + roff);
         } else {
@@ -182,15 +340,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][
           if (co + e < p.cout) r2[e] = p.res2[m * p.res2_ld + co + e];
       }
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float x = v[e] * ws4[e] + bias4[e];
-        if (p.res1 != nullptr && p.res1_pre) x += r1[e];
-        x = x >= 0.f ? x : x * p.act_slope;
-        x = x * p.alpha;
-        if (p.res1 != nullptr && !p.res1_pre) x += r1[e];
-        if (p.res2 != nullptr) x = x * p.alpha2 + r2[e];
-        v[e] = x;
-      }
+      for (int e = 0; e < 4; ++e) v[e] = conv_value(p, v[e], ws4[e], bias4[e], r1[e], r2[e]);
       float* dst = p.out + m * p.out_ld + co;
       if (vec) {
         *reinterpret_cast<f32x4*>(dst) = v;
@@ -203,100 +353,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][
   }
 }
 
-
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-
-// Mixed-precision FMA (v_fma_mix_f32: every source is an f32 register or one binary16 half of a register, one rounding):
-//   fcp_mix_sum(h, l, HI)  = float(h.half) + float(l.half)      — exactly what v_cvt_f32_f16 x2 + v_add_f32 give (the conversions
-//   fcp_mix_diff(x, h, HI) = x - float(h.half)                    are exact, so there is one rounding either way), in ONE instruction.
-// The epilogues of every fp16x3 kernel decode / encode 8-16 values per lane and chunk with these; as separate converts and
-// adds that was a third of the bottleneck-chain kernel's epilogue instructions.
-template <int HI>
-__device__ __forceinline__ float fcp_mix_sum(unsigned h, unsigned l) {
-  float r;
-  const float one = 1.0f;
-  if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h), "s"(one), "v"(l));
-  else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h), "s"(one), "v"(l));
-  return r;
-}
-template <int HI>
-__device__ __forceinline__ float fcp_mix_diff(float x, unsigned h) {
-  float r;
-  const float minus_one = -1.0f;
-  if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "s"(minus_one), "v"(x));
-  else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "s"(minus_one), "v"(x));
-  return r;
-}
-
-// 8 fp32 -> 8 hi + 8 lo binary16 (round-toward-zero packs; lo = x - hi is exact in fp32).  Idempotent on
-// values that already are a hi + lo sum, so elementwise kernels may decode / re-encode freely.
-__device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, u32x4_t& hi, u32x4_t& lo) {
-  const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const unsigned hu = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x[2 * q], x[2 * q + 1]));
-    const float r0 = fcp_mix_diff<0>(x[2 * q], hu);
-    const float r1 = fcp_mix_diff<1>(x[2 * q + 1], hu);
-    hi[q] = hu;
-    lo[q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-  }
-}
-// inverse: value = float(hi) + float(lo) (exact)
-__device__ __forceinline__ void join8(const u32x4_t& hi, const u32x4_t& lo, float (&x)[8]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const unsigned hu = hi[q], lu = lo[q];
-    x[2 * q] = fcp_mix_sum<0>(hu, lu);
-    x[2 * q + 1] = fcp_mix_sum<1>(hu, lu);
-  }
-}
-// byte offset of channel c (multiple of 8) inside a split32 pixel: group (c/32)*128 B, hi at (c%32)*2, lo +64
-__device__ __forceinline__ long split_chan_off(int c) { return (long)(c >> 5) * 128 + (c & 31) * 2; }
-
-// 8 consecutive channels of one pixel from an activation tensor of either format
-__device__ __forceinline__ void load8(const float* base, long pix, int ld, int c, int fmt, float (&x)[8]) {
-  if (fmt == 1) {
-    const char* pb = reinterpret_cast<const char*>(base) + pix * ld * 4 + split_chan_off(c);
-    join8(*reinterpret_cast<const u32x4_t*>(pb), *reinterpret_cast<const u32x4_t*>(pb + 64), x);
-  } else {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(base + pix * ld + c);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(base + pix * ld + c + 4);
-    x[0] = a[0]; x[1] = a[1]; x[2] = a[2]; x[3] = a[3]; x[4] = b[0]; x[5] = b[1]; x[6] = b[2]; x[7] = b[3];
-  }
-}
-
-// Residual tile of a workgroup, fetched at kernel start so its HBM latency hides under the main loop
-// (the 1x1 "c3" convs of the bottlenecks have 2-8 K slices only: their cost is the epilogue's traffic).
-template <int BN>
-struct ResPrefetch {
-  static constexpr int CPR = BN / 8, RPP = 256 / CPR, PASSES = BM / RPP;
-  u32x4_t a[PASSES], b[PASSES];   // split32: hi, lo chunks; fp32: channels c..c+3, c+4..c+7
-  bool valid;
-};
-
-template <int BN>
-__device__ __forceinline__ void prefetch_res1(const ConvK& p, int tile_m, int tile_n, int tid, ResPrefetch<BN>& r) {
-  constexpr int CPR = BN / 8, RPP = 256 / CPR, PASSES = BM / RPP;
-  const int co = tile_n * BN + (tid % CPR) * 8;
-  const long m0 = (long)tile_m * BM + tid / CPR;
-  r.valid = p.res1 != nullptr && !p.res1_resize && co < p.cout;
-  if (!r.valid) return;
-#pragma unroll
-  for (int g = 0; g < PASSES; ++g) {
-    const long m = m0 + (long)g * RPP;
-    if (m < p.M) {
-      if (p.res1_fmt == 1) {
-        const char* pb = reinterpret_cast<const char*>(p.res1) + m * p.res1_ld * 4 + split_chan_off(co);
-        r.a[g] = *reinterpret_cast<const u32x4_t*>(pb);
-        r.b[g] = *reinterpret_cast<const u32x4_t*>(pb + 64);
-      } else {
-        r.a[g] = *reinterpret_cast<const u32x4_t*>(p.res1 + m * p.res1_ld + co);
-        r.b[g] = *reinterpret_cast<const u32x4_t*>(p.res1 + m * p.res1_ld + co + 4);
-      }
-    }
-  }
-}
 
 template <int I, int N, typename F>
 __device__ __forceinline__ void fcp_static_for(F&& f) {          // f(std::integral_constant<int, I>{}) for I .. N - 1
@@ -353,17 +409,7 @@ __device__ __forceinline__ void conv_epilogue_regs(const ConvK& p, f32x16 (&acc)
         fcp_static_for<0, 2>([&](auto sc) {
           constexpr int set = decltype(sc)::value;
           const int mi = row_of(i, set);
-          if (i < tm_act && mi < m_end && co < co_end) {
-            if (p.out_fmt == 1) {
-              char* ob = reinterpret_cast<char*>(p.out) + (long)mi * p.out_ld * 4 + split_chan_off(co);
-              *reinterpret_cast<u32x4_t*>(ob) = pend_a[i - i0][set];
-              *reinterpret_cast<u32x4_t*>(ob + 64) = pend_b[i - i0][set];
-            } else {
-              float* dst = p.out + (long)mi * p.out_ld + co;
-              *reinterpret_cast<u32x4_t*>(dst) = pend_a[i - i0][set];
-              *reinterpret_cast<u32x4_t*>(dst + 4) = pend_b[i - i0][set];
-            }
-          }
+          if (i < tm_act && mi < m_end && co < co_end) store8(p.out, mi, p.out_ld, co, p.out_fmt, 0, pend_a[i - i0][set], pend_b[i - i0][set]);
         });
       }
     });
@@ -383,18 +429,7 @@ __device__ __forceinline__ void conv_epilogue_regs(const ConvK& p, f32x16 (&acc)
             constexpr int set = decltype(sc)::value;
             const int mi = row_of(i, set);
             const long m = (i < tm_act && mi < m_end && cok) ? (long)mi : (long)m_start;
-            long rpix = m;
-            if (p.res1_resize) {
-              const int ni = (int)(m / hw);
-              const int rem = (int)(m - (long)ni * hw);
-              const int ho = rem / p.out_w;
-              const int wo = rem - ho * p.out_w;
-              int sh = (int)floorf(ho * p.res1_sh);
-              int sw = (int)floorf(wo * p.res1_sw);
-              sh = sh < p.res1_h - 1 ? sh : p.res1_h - 1;
-              sw = sw < p.res1_w - 1 ? sw : p.res1_w - 1;
-              rpix = ((long)ni * p.res1_h + sh) * p.res1_w + sw;
-            }
+            const long rpix = p.res1_resize ? res1_pixel(p, m, hw) : m;
             if (p.res1_fmt == 1) {
               const char* pb = reinterpret_cast<const char*>(p.res1) + rpix * p.res1_ld * 4 + split_chan_off(cc);
               r1a[i - i0][set] = *reinterpret_cast<const u32x4_t*>(pb);
@@ -449,21 +484,8 @@ __device__ __forceinline__ void conv_epilogue_regs(const ConvK& p, f32x16 (&acc)
             load8(p.res2, (i < tm_act && mi < m_end && cok) ? (long)mi : (long)m_start, p.res2_ld, cc, p.res2_fmt, r2);
           }
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            float x = v[e] * ws8[e] + bias8[e];
-            if (p.res1 != nullptr && p.res1_pre) x += r1[e];
-            x = x >= 0.f ? x : x * p.act_slope;
-            x = x * p.alpha;
-            if (p.res1 != nullptr && !p.res1_pre) x += r1[e];
-            if (p.res2 != nullptr) x = x * p.alpha2 + r2[e];
-            v[e] = x;
-          }
-          if (p.out_fmt == 1) {
-            split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, pend_a[i - i0][set], pend_b[i - i0][set]);
-          } else {
-            pend_a[i - i0][set] = __builtin_bit_cast(u32x4_t, f32x4{v[0], v[1], v[2], v[3]});
-            pend_b[i - i0][set] = __builtin_bit_cast(u32x4_t, f32x4{v[4], v[5], v[6], v[7]});
-          }
+          for (int e = 0; e < 8; ++e) v[e] = conv_value(p, v[e], ws8[e], bias8[e], r1[e], r2[e]);
+          pack8(v, p.out_fmt, pend_a[i - i0][set], pend_b[i - i0][set]);
         });
       }
     });
@@ -475,8 +497,7 @@ __device__ __forceinline__ void conv_epilogue_regs(const ConvK& p, f32x16 (&acc)
 // (cout % 8 == 0, all tensors 16-byte aligned).  Same arithmetic as conv_epilogue.
 template <int BN, int TM, int TN, int WTM, int WTN>
 __device__ __forceinline__ void conv_epilogue8(const ConvK& p, f32x16 (&acc)[TM][TN], float* smem, int tile_m,
-                                               int tile_n, int tid, int lane, int wm, int wn, int hw,
-                                               const ResPrefetch<BN>* pre = nullptr) {
+                                               int tile_n, int tid, int lane, int wm, int wn, int hw) {
   constexpr int CPR = BN / 8;
   constexpr int RPP = 256 / CPR;
   constexpr int PASSES = BM / RPP;
@@ -485,19 +506,7 @@ __device__ __forceinline__ void conv_epilogue8(const ConvK& p, f32x16 (&acc)[TM]
   const int crow = tid / CPR;
   const int co = tile_n * BN + ccol;
   const long m0 = (long)tile_m * BM + crow;
-  {
-    const int half = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          const int row = wm * WTM + i * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
-          Cs[row * BN + wn * WTN + j * 32 + (lane & 31)] = acc[i][j][rr];
-        }
-  }
-  __syncthreads();
+  stage_acc_tile<BN, TM, TN, WTM, WTN>(acc, Cs, lane, wm, wn);
   if (co >= p.cout) return;
   float bias8[8], ws8[8];
 #pragma unroll
@@ -505,7 +514,6 @@ __device__ __forceinline__ void conv_epilogue8(const ConvK& p, f32x16 (&acc)[TM]
     bias8[e] = p.bias != nullptr ? p.bias[co + e] : 0.f;
     ws8[e] = p.wscale != nullptr ? p.wscale[co + e] : 1.f;
   }
-  const bool use_pre = pre != nullptr && pre->valid;
 #pragma unroll
   for (int g = 0; g < PASSES; ++g) {
     const int row = crow + g * RPP;
@@ -517,55 +525,11 @@ __device__ __forceinline__ void conv_epilogue8(const ConvK& p, f32x16 (&acc)[TM]
       const f32x4 b = *reinterpret_cast<const f32x4*>(Cs + row * BN + ccol + 4);
       v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
     }
-    if (use_pre) {
-      if (p.res1_fmt == 1) {
-        join8(pre->a[g], pre->b[g], r1);
-      } else {
-        const f32x4 fa = __builtin_bit_cast(f32x4, pre->a[g]), fb = __builtin_bit_cast(f32x4, pre->b[g]);
-        r1[0] = fa[0]; r1[1] = fa[1]; r1[2] = fa[2]; r1[3] = fa[3]; r1[4] = fb[0]; r1[5] = fb[1]; r1[6] = fb[2]; r1[7] = fb[3];
-      }
-    } else if (p.res1 != nullptr) {
-      long rpix = m;
-      if (p.res1_resize) {
-        const int ni = (int)(m / hw);
-        const int rem = (int)(m - (long)ni * hw);
-        const int ho = rem / p.out_w;
-        const int wo = rem - ho * p.out_w;
-        int sh = (int)floorf(ho * p.res1_sh);
-        int sw = (int)floorf(wo * p.res1_sw);
-        sh = sh < p.res1_h - 1 ? sh : p.res1_h - 1;
-        sw = sw < p.res1_w - 1 ? sw : p.res1_w - 1;
-        rpix = ((long)ni * p.res1_h + sh) * p.res1_w + sw;
-      }
-      load8(p.res1, rpix, p.res1_ld, co, p.res1_fmt, r1);
-    }
+    if (p.res1 != nullptr) load8(p.res1, p.res1_resize ? res1_pixel(p, m, hw) : m, p.res1_ld, co, p.res1_fmt, r1);
     if (p.res2 != nullptr) load8(p.res2, m, p.res2_ld, co, p.res2_fmt, r2);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float x = v[e] * ws8[e] + bias8[e];
-      if (p.res1 != nullptr && p.res1_pre) x += r1[e];
-      x = x >= 0.f ? x : x * p.act_slope;
-      x = x * p.alpha;
-      if (p.res1 != nullptr && !p.res1_pre) x += r1[e];
-      if (p.res2 != nullptr) x = x * p.alpha2 + r2[e];
-      v[e] = x;
-    }
-    if (p.out_fmt == 1) {
-      u32x4_t hi, lo;
-      split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);
-      char* ob = reinterpret_cast<char*>(p.out) + m * p.out_ld * 4 + split_chan_off(co);
-      if (p.nt_store) {
-        __builtin_nontemporal_store(hi, reinterpret_cast<u32x4_t*>(ob));
-        __builtin_nontemporal_store(lo, reinterpret_cast<u32x4_t*>(ob + 64));
-      } else {
-        *reinterpret_cast<u32x4_t*>(ob) = hi;
-        *reinterpret_cast<u32x4_t*>(ob + 64) = lo;
-      }
-    } else {
-      float* dst = p.out + m * p.out_ld + co;
-      *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
-      *reinterpret_cast<f32x4*>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    }
+    for (int e = 0; e < 8; ++e) v[e] = conv_value(p, v[e], ws8[e], bias8[e], r1[e], r2[e]);
+    pack_store8(p.out, m, p.out_ld, co, p.out_fmt, p.nt_store, v);
   }
 }
 

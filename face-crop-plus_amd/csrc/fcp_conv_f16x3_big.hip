@@ -39,14 +39,6 @@ __device__ __forceinline__ f16x8 lds_read128(unsigned addr) {
   return v;
 }
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 template <int BN>
 __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
   constexpr int WAVES_N = BN == 256 ? 4 : 2;
@@ -200,12 +192,12 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
     f16x8 fah[2][TMA > 0 ? TMA : 1], fal[2][TMA > 0 ? TMA : 1], fbh[2][TN], fbl[2][TN];   // [fragment set]
   auto read_frags = [&](auto set_c, unsigned stage_xor) {   // set s holds k-half s
     constexpr int set = decltype(set_c)::value;
-    static_for<0, TMA>([&](auto ic) {
+    fcp_static_for<0, TMA>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       fah[set][i] = lds_read128<i * 32 * ROWB>(aH[set] ^ stage_xor);
       fal[set][i] = lds_read128<i * 32 * ROWB>(aL[set] ^ stage_xor);
     });
-    static_for<0, TN>([&](auto jc) {
+    fcp_static_for<0, TN>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
       fbh[set][j] = lds_read128<j * 32 * ROWB>(bH[set] ^ stage_xor);
       fbl[set][j] = lds_read128<j * 32 * ROWB>(bL[set] ^ stage_xor);
@@ -220,7 +212,7 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
   auto mfmas_reads = [&](auto cs_c, auto ls_c, unsigned stage_xor) {
     constexpr int cs = decltype(cs_c)::value, ls = decltype(ls_c)::value;
     constexpr int NM = 3 * TMA * TN, NR = 2 * TMA + 2 * TN;
-    static_for<0, NM>([&](auto mc) {
+    fcp_static_for<0, NM>([&](auto mc) {
       constexpr int m = decltype(mc)::value;
       constexpr int g = m / (TMA * TN), i = (m % (TMA * TN)) / TN, j = m % TN;
       // the filter fragment is the ROW operand: the tile is accumulated transposed (filters x pixels; same products, same
@@ -231,7 +223,7 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
       else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[cs][j], fah[cs][i], acc[i][j], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       // read r is issued after MFMA floor((r + 1) * NM / NR) - 1
-      static_for<0, NR>([&](auto rc) {
+      fcp_static_for<0, NR>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
         if constexpr (((r + 1) * NM) / NR - 1 == m
         ) {
@@ -302,7 +294,7 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  static_for<0, TM + 1>([&](auto tc) {
+  fcp_static_for<0, TM + 1>([&](auto tc) {
     if (tm_act == decltype(tc)::value) main_loop(tc);
   });
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -149,11 +149,6 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : 3)) conv_igemm_f16x3_dma
                                                (int)(woff[i] + (unsigned)(kt * BK * 4)), 0, 0, FCP_AUX_B);
   };
 
-  // residual tile first: its HBM round trip overlaps the whole main loop
-  ResPrefetch<BN> rpre;
-  rpre.valid = false;
-  (void)rpre;
-
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)

@@ -66,14 +66,6 @@ __device__ __forceinline__ f32x4 lds_read128f(unsigned addr) {
   return v;
 }
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 template <int TN>   // 32-filter passes per slice: cout <= 32 * TN
 __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -271,7 +263,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
   __builtin_amdgcn_sched_barrier(0);
 
   // fragments of (block 0, tap 0)
-  static_for<0, 12>([&](auto ic) { read_one(std::integral_constant<int, 0>{}, ic, 0u, 0u); });
+  fcp_static_for<0, 12>([&](auto ic) { read_one(std::integral_constant<int, 0>{}, ic, 0u, 0u); });
 
   // One tap = 12 MFMAs: six on the k-half-0 fragments, six on the k-half-1 fragments.  There is ONE fragment set: the
   // next tap's read of a fragment follows the LAST MFMA that takes the register's old contents (the matrix pipe has its
@@ -281,7 +273,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
   auto tap_step = [&](auto tap_c, auto pass_c, unsigned aoff_n, unsigned boff_n) {
     constexpr int tap = decltype(tap_c)::value, pass = decltype(pass_c)::value;
     constexpr int ntap = (tap + 1) % 9;
-    static_for<0, 2>([&](auto sc) {
+    fcp_static_for<0, 2>([&](auto sc) {
       constexpr int s = decltype(sc)::value;
       asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -323,7 +315,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) {
-          const int row = i * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+          const int row = i * 32 + mfma_c_row(rr, half);
           lds_write32(cs0 + (unsigned)((row * 32 + xl) * 4), acc[n][i][rr]);
         }
       __builtin_amdgcn_sched_barrier(0);
@@ -349,24 +341,15 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
           if (p.res1 != nullptr) load8(p.res1, m, p.res1_ld, cvalid ? ccol : 0, p.res1_fmt, r1);
           if (p.res2 != nullptr) load8(p.res2, m, p.res2_ld, cvalid ? ccol : 0, p.res2_fmt, r2);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            float t = v[e] * w8[e >> 2][e & 3] + b8[e >> 2][e & 3];
-            if (p.res1 != nullptr && p.res1_pre) t += r1[e];
-            t = t >= 0.f ? t : t * p.act_slope;
-            t = t * p.alpha;
-            if (p.res1 != nullptr && !p.res1_pre) t += r1[e];
-            if (p.res2 != nullptr) t = t * p.alpha2 + r2[e];
-            v[e] = t;
-          }
+          for (int e = 0; e < 8; ++e) v[e] = conv_value(p, v[e], w8[e >> 2][e & 3], b8[e >> 2][e & 3], r1[e], r2[e]);
           u32x4_t s0, s1;
           unsigned o0, o1;
           if (p.out_fmt == 1) {
-            split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, s0, s1);
+            pack8(v, 1, s0, s1);
             o0 = (unsigned)(m * p.out_ld * 4 + split_chan_off(ccol));
             o1 = o0 + 64u;
           } else {
-            s0 = __builtin_bit_cast(u32x4_t, f32x4{v[0], v[1], v[2], v[3]});
-            s1 = __builtin_bit_cast(u32x4_t, f32x4{v[4], v[5], v[6], v[7]});
+            pack8(v, 0, s0, s1);
             o0 = (unsigned)((m * p.out_ld + ccol) * 4);
             o1 = o0 + 16u;
           }
@@ -390,7 +373,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
     const bool last_of_tile = blk == nblocks - 1;
     const int nit = it + slots, ntile = xcd * per_x + nit;
     const bool more = nit < per_x && ntile < ntiles;
-    static_for<0, 8>([&](auto tc) { tap_step(tc, pass_c, aoff, boff); });
+    fcp_static_for<0, 8>([&](auto tc) { tap_step(tc, pass_c, aoff, boff); });
     // tap 8's fragments are (about to be) in registers: the block's buffer (and, after the last pass, the slice's
     // stage) is dead for this wave; the loaders arrive when the next block's operands are in LDS
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -668,9 +651,9 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
       __builtin_amdgcn_s_barrier();                      // the block's operands have landed (loaders); the previous block's slots are dead (this wave)
       __builtin_amdgcn_sched_barrier(0);
     }
-    static_for<0, 2>([&](auto sc) {
+    fcp_static_for<0, 2>([&](auto sc) {
       constexpr int s = decltype(sc)::value;
-      static_for<0, TN>([&](auto jc) {
+      fcp_static_for<0, TN>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         constexpr int gi = s * TN + j, set = gi & 1, nset = set ^ 1;
         // This group's filter fragments were the first two reads of the previous group; the pixel fragments it requested
@@ -733,7 +716,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) {
-          const int row = i * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+          const int row = i * 32 + mfma_c_row(rr, half);
           lds_write32(cs0 + (unsigned)((row * 32 + xl) * 4), acc[n][i][rr]);
         }
       __builtin_amdgcn_sched_barrier(0);
@@ -761,32 +744,20 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
             if (p.res1 != nullptr) load8(p.res1, m, p.res1_ld, cvalid ? ccol : 0, p.res1_fmt, r1);
             if (p.res2 != nullptr) load8(p.res2, m, p.res2_ld, cvalid ? ccol : 0, p.res2_fmt, r2);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              float t = v[e] * w8[e >> 2][e & 3] + b8[e >> 2][e & 3];
-              if (p.res1 != nullptr && p.res1_pre) t += r1[e];
-              t = t >= 0.f ? t : t * p.act_slope;
-              t = t * p.alpha;
-              if (p.res1 != nullptr && !p.res1_pre) t += r1[e];
-              if (p.res2 != nullptr) t = t * p.alpha2 + r2[e];
-              v[e] = t;
-            }
-          } else {
+            for (int e = 0; e < 8; ++e) v[e] = conv_value(p, v[e], w8[e >> 2][e & 3], b8[e >> 2][e & 3], r1[e], r2[e]);
+          } else {                                           // no residual inputs (launcher): the terms drop out
+            const ConvEpi plain{false, false, false, p.act_slope, p.alpha, 1.f};
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {                   // the same expressions without the residual terms
-              float t = v[e] * w8[e >> 2][e & 3] + b8[e >> 2][e & 3];
-              t = t >= 0.f ? t : t * p.act_slope;
-              v[e] = t * p.alpha;
-            }
+            for (int e = 0; e < 8; ++e) v[e] = conv_value(plain, v[e], w8[e >> 2][e & 3], b8[e >> 2][e & 3], 0.f, 0.f);
           }
           u32x4_t s0, s1;
           unsigned o0, o1;
           if (p.out_fmt == 1) {
-            split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, s0, s1);
+            pack8(v, 1, s0, s1);
             o0 = (unsigned)(m * p.out_ld * 4 + split_chan_off(ccol));
             o1 = o0 + 64u;
           } else {
-            s0 = __builtin_bit_cast(u32x4_t, f32x4{v[0], v[1], v[2], v[3]});
-            s1 = __builtin_bit_cast(u32x4_t, f32x4{v[4], v[5], v[6], v[7]});
+            pack8(v, 0, s0, s1);
             o0 = (unsigned)((m * p.out_ld + ccol) * 4);
             o1 = o0 + 16u;
           }
@@ -806,7 +777,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
   const int nunits = nslices / 2;
   for (;;) {
     if (unit != 0 || it != slot) make_aaddr();           // (the first unit's are in registers already)
-    static_for<0, 18>([&](auto tc) {
+    fcp_static_for<0, 18>([&](auto tc) {
       constexpr int t = decltype(tc)::value, tn = (t + 1) % 18;
       using OX = std::integral_constant<int, (t / 9) * A_BYTES>;
       using ON = std::integral_constant<int, (tn / 9) * A_BYTES>;
@@ -816,7 +787,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
     });
     {                                                    // 18 taps = whole ring turns + 2: rotate the slot bases by two
       const unsigned b0 = bslot[0], b1 = bslot[1];
-      static_for<0, RS - 2>([&](auto kc) { bslot[decltype(kc)::value] = bslot[decltype(kc)::value + 2]; });
+      fcp_static_for<0, RS - 2>([&](auto kc) { bslot[decltype(kc)::value] = bslot[decltype(kc)::value + 2]; });
       bslot[RS - 2] = b0; bslot[RS - 1] = b1;
     }
     if (++unit == nunits) {

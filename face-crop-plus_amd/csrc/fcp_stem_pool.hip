@@ -323,8 +323,8 @@ __global__ void __launch_bounds__(StemGeo::NT, StemGeo::WGS) stem_pool_kernel(co
         v1 = v1 > 0.f ? v1 : 0.f;
         const long pixel = ((long)ni * p.hp + oy) * p.wp + ox;
         if (p.out_fmt == 1) {
-          const unsigned hu = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v0, v1));   // split8's arithmetic
-          const unsigned lu = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(fcp_mix_diff<0>(v0, hu), fcp_mix_diff<1>(v1, hu)));
+          unsigned hu, lu;
+          split2(v0, v1, hu, lu);
           char* ob = reinterpret_cast<char*>(p.out) + pixel * p.out_ld * 4 + split_chan_off(pc2);
           *reinterpret_cast<unsigned*>(ob) = hu;
           *reinterpret_cast<unsigned*>(ob + 64) = lu;
@@ -379,12 +379,9 @@ __global__ void __launch_bounds__(StemGeo::NT, StemGeo::WGS) stem_pool_kernel(co
         for (int py = 0; py < PH; ++py) {
           const int oy = py0 + py;
           if (oy >= p.hp || ox >= p.wp) continue;
-          float x0 = cv[py][0] * ws1a + b1a, x1 = cv[py][1] * ws1b + b1b;   // the generic epilogue's expressions (act_slope 0, alpha 1)
-          x0 = x0 >= 0.f ? x0 : x0 * 0.f;
-          x1 = x1 >= 0.f ? x1 : x1 * 0.f;
-          x0 = x0 * 1.f; x1 = x1 * 1.f;
-          const unsigned hu = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-          const unsigned lu = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(fcp_mix_diff<0>(x0, hu), fcp_mix_diff<1>(x1, hu)));
+          const float x0 = conv_value_relu(cv[py][0], ws1a, b1a), x1 = conv_value_relu(cv[py][1], ws1b, b1b);   // conv1 + BN + ReLU as the generic epilogue
+          unsigned hu, lu;
+          split2(x0, x1, hu, lu);
           const long pixel = ((long)ni * p.hp + oy) * p.wp + ox;
           char* ob = reinterpret_cast<char*>(p.t1) + pixel * p.t1_ld * 4 + split_chan_off(pc2);
           *reinterpret_cast<unsigned*>(ob) = hu;

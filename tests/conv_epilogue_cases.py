@@ -1,0 +1,186 @@
+"""The cases of tests/test_conv_epilogue_bits_gpu.py and of its fixture generator (tests/golden/make_golden_conv_epilogue.py):
+one list, and the one function that runs a case.
+
+A case is a launch set that ends in every form of the fused conv epilogue (acc * wscale + bias, residual before / after the
+activation, leaky slope, alpha, second residual): the three generic epilogues behind every generic kernel, the halo-tile kernels,
+the bottleneck-chain forms and the fused stem + pool + conv1.  Inputs, filters, bias and residuals come from
+``numpy.random.default_rng(seed)`` (mean zero; the seed is the CRC of the case id); tiles are explicit, so the autotuner plays
+no part.  ``run_case`` returns, per tile choice, the raw bytes of every output buffer as int32 tensors.
+"""
+import zlib
+
+import numpy as np
+
+# epilogue settings of the generic-conv rows: (act_slope, alpha, res1: None | "pre" | "post" | "post_resized", res2 alpha2 | None, bias)
+SETTINGS = {
+    "a_relu": dict(slope=0.0, alpha=1.0, res1=None, alpha2=None, bias=True),
+    "b_relu_res1pre": dict(slope=0.0, alpha=1.0, res1="pre", alpha2=None, bias=True),
+    "c_id_res1post_resized": dict(slope=1.0, alpha=1.0, res1="post_resized", alpha2=None, bias=True),
+    "d_leaky_alpha_res1post_res2": dict(slope=0.2, alpha=0.2, res1="post", alpha2=0.2, bias=True),
+    "e_nobias_id": dict(slope=1.0, alpha=1.0, res1=None, alpha2=None, bias=False),
+}
+NO_RESIZE = ("a_relu", "b_relu_res1pre", "d_leaky_alpha_res1post_res2", "e_nobias_id")     # the halo kernels take same-size residuals only
+NO_RES = ("a_relu", "e_nobias_id")                                                         # halo wide above 64 filters: no residual inputs
+
+T128 = [(128, 32), (128, 64), (128, 128)]
+
+
+def _generic_rows():
+    """(row id, dict(precision, in_fmt, out_fmt, cin, cout, k, n, h, w, tiles, settings[, out_c0, balance]))"""
+    rows = []
+    for cout in (19, 40):                                             # conv_igemm_f32 -> conv_epilogue (19: scalar tail)
+        for k in (3, 1):
+            rows.append((f"f32_c{cout}_k{k}", dict(precision="f32", in_fmt=0, out_fmt=0, cin=32, cout=cout, k=k, n=1, h=9, w=11, tiles=T128)))
+    # an output view that starts at channel 1 of a wider buffer: misaligned rows, vec_ok false
+    rows.append(("f32_c19_k3_view1", dict(precision="f32", in_fmt=0, out_fmt=0, cin=32, cout=19, k=3, n=1, h=9, w=11, tiles=T128, out_c0=1, out_ld=24)))
+    for cout in (19, 40):                                             # conv_igemm_f16x3, fp32 tensors -> conv_epilogue
+        rows.append((f"f16x3_f32_c{cout}", dict(precision="f16x3", in_fmt=0, out_fmt=0, cin=32, cout=cout, k=3, n=1, h=9, w=11, tiles=T128)))
+    for cout in (32, 96):                                             # conv_igemm_f16x3, fp32 in, split32 out / residuals -> conv_epilogue8
+        rows.append((f"f16x3_split_c{cout}", dict(precision="f16x3", in_fmt=0, out_fmt=1, cin=32, cout=cout, k=3, n=1, h=9, w=11, tiles=T128)))
+    for cout in (64, 96):                                             # conv_igemm_f16x3_dma: out_fmt 0 -> conv_epilogue, 1 -> conv_epilogue_regs
+        for fmt in (0, 1):
+            rows.append((f"dma_c{cout}_out{fmt}", dict(precision="f16x3", in_fmt=1, out_fmt=fmt, cin=64, cout=cout, k=3, n=2, h=9, w=11, tiles=T128)))
+    for cout in (128, 192, 256):                                      # conv_igemm_f16x3_big: 396 rows = one whole + one ragged 256-row tile
+        big = [(256, 128)] + ([(256, 192)] if cout == 192 else []) + ([(256, 256)] if cout == 256 else [])
+        tiles = [(128, 128)] + big + [(tm, tn, "bal") for tm, tn in big]
+        rows.append((f"big_c{cout}", dict(precision="f16x3", in_fmt=1, out_fmt=1, cin=64, cout=cout, k=1, n=1, h=18, w=22, tiles=tiles)))
+    for h, w in ((5, 7), (9, 33)):                                    # 9 x 33 crosses the 8 x 32 patch on both axes
+        for cout in (24, 32, 64):                                     # halo (1, 32); 64 filters: two passes
+            tiles = [(128, 64), (1, 32)] + ([(128, 32)] if cout <= 32 else [])
+            rows.append((f"halo_c{cout}_{h}x{w}", dict(precision="f16x3", in_fmt=1, out_fmt=int(cout % 32 == 0), cin=64, cout=cout, k=3, n=2, h=h, w=w,
+                                                       tiles=tiles, settings=NO_RESIZE)))
+        rows.append((f"halowide64_{h}x{w}", dict(precision="f16x3", in_fmt=1, out_fmt=1, cin=64, cout=64, k=3, n=2, h=h, w=w,
+                                                 tiles=[(128, 64), (1, 64)], settings=NO_RESIZE)))
+        for cout in (72, 128):                                        # halo wide (1, 128): no residual inputs
+            rows.append((f"halowide128_c{cout}_{h}x{w}", dict(precision="f16x3", in_fmt=1, out_fmt=int(cout % 32 == 0), cin=128, cout=cout, k=3, n=2, h=h, w=w,
+                                                              tiles=[(128, 64), (128, 128), (1, 128)], settings=NO_RES)))
+    return rows
+
+
+def cases():
+    """[(case id, kind, spec)] — kind: "conv" | "chain" | "stem"."""
+    out = []
+    for rid, spec in _generic_rows():
+        for sid in spec.get("settings", tuple(SETTINGS)):
+            out.append((f"{rid}-{sid}", "conv", dict(spec, setting=sid)))
+    # the forms and smallest sizes of tests/test_chain_gpu.py
+    out.append(("chain_conv2_cn64", "chain", dict(form="conv2", cn=64, n=1, h=5, w=3)))
+    out.append(("chain_conv2_cn128", "chain", dict(form="conv2", cn=128, n=1, h=9, w=17)))
+    out.append(("chain_pair_128_512", "chain", dict(form="pair", n=1, h=16, w=16)))
+    out.append(("chain_two_source", "chain", dict(form="two_source", n=1, h=7, w=5)))
+    out.append(("chain_expand_256_1024", "chain", dict(form="expand", n=1, h=7, w=5)))
+    out.append(("stem_1x9x11", "stem", dict(n=1, h=9, w=11)))
+    out.append(("stem_2x75x131", "stem", dict(n=2, h=75, w=131)))
+    return out
+
+
+def slope0(kind, spec):
+    """The case's activation is ReLU through the shared arithmetic: its outputs must hold -0.0 (and positive values)."""
+    return kind != "conv" or SETTINGS[spec["setting"]]["slope"] == 0.0
+
+
+def _rng(case_id):
+    return np.random.default_rng(zlib.crc32(case_id.encode()))
+
+
+def _act(E, torch, device, rng, n, h, w, c, fmt):
+    a = E.Act(torch.from_numpy(rng.standard_normal((n, h, w, c), dtype=np.float32)).to(device))
+    return E.f32_to_split32(a) if fmt == 1 else a
+
+
+def _raw(torch, t):
+    return t.contiguous().view(torch.int32).clone()
+
+
+def _conv(E, torch, device, case_id, s):
+    rng = _rng(case_id)
+    st = SETTINGS[s["setting"]]
+    n, h, w, cin, cout, k = s["n"], s["h"], s["w"], s["cin"], s["cout"], s["k"]
+    wt = rng.standard_normal((cout, cin, k, k), dtype=np.float32) * np.float32((2.0 / (cin * k * k)) ** 0.5)
+    bias = rng.standard_normal(cout, dtype=np.float32) * np.float32(0.5) if st["bias"] else None
+    pc = E.pack_conv(wt, bias, None, 1, k // 2, device, precision=s["precision"])
+    x = _act(E, torch, device, rng, n, h, w, cin, s["in_fmt"])
+    rfmt = s["out_fmt"]                                               # residuals in the output's format
+    res1 = res2 = None
+    if st["res1"] is not None:
+        rh, rw = ((h + 1) // 2, (w + 1) // 2) if st["res1"] == "post_resized" else (h, w)      # 9 x 11 -> 5 x 6
+        res1 = _act(E, torch, device, rng, n, rh, rw, cout, rfmt)
+    if st["alpha2"] is not None:
+        res2 = _act(E, torch, device, rng, n, h, w, cout, rfmt)
+    outs = {}
+    for tile in s["tiles"]:
+        ld, c0 = s.get("out_ld", cout), s.get("out_c0", 0)
+        buf = torch.full((n, h, w, ld), 7.0, dtype=torch.float32, device=device)      # sentinel: channels outside the view keep it
+        out = E.Act(buf, c0, cout, s["out_fmt"])
+        E.conv(pc, x, out, act_slope=st["slope"], alpha=st["alpha"], res1=res1, res1_pre=st["res1"] == "pre", res2=res2,
+               alpha2=st["alpha2"] if st["alpha2"] is not None else 1.0, tile_m=tile[0], tile_n=tile[1], balance_tail=len(tile) > 2)
+        outs["x".join(map(str, tile))] = [_raw(torch, buf)]
+    torch.cuda.synchronize()
+    info = dict(fmt=s["out_fmt"], view=(s.get("out_c0", 0), cout),
+                res1_smaller=None if st["res1"] != "post_resized" else (res1.h < h and res1.w < w))
+    return outs, info
+
+
+def _chain(E, torch, device, case_id, s):
+    rng = _rng(case_id)
+    n, h, w, form = s["n"], s["h"], s["w"], s["form"]
+
+    def pack(co, ci, k):
+        wt = rng.standard_normal((co, ci, k, k), dtype=np.float32) * np.float32((2.0 / (ci * k * k)) ** 0.5)
+        return E.pack_conv(wt, rng.standard_normal(co, dtype=np.float32) * np.float32(0.1), None, 1, k // 2, device, precision="f16x3")
+    if form == "conv2":
+        pc2, pc3, pc1 = pack(64, 64, 3), pack(256, 64, 1), pack(s["cn"], 256, 1)
+        t1, res = _act(E, torch, device, rng, n, h, w, 64, 1), _act(E, torch, device, rng, n, h, w, 256, 1)
+        run = lambda tm: E.bottleneck_chain(pc2, pc3, pc1, t1, res, tile_m=tm)
+        tiles = (0, 128, 16, 256, 32)                                 # tile_m is a hint the library may ignore: same bits
+    elif form == "pair":
+        pc3, pc1 = pack(512, 128, 1), pack(128, 512, 1)
+        t1, res = _act(E, torch, device, rng, n, h, w, 128, 1), _act(E, torch, device, rng, n, h, w, 512, 1)
+        run = lambda tm: E.bottleneck_chain(None, pc3, pc1, t1, res, tile_m=tm)
+        tiles = (0,)
+    elif form == "two_source":
+        pc3, pc1 = pack(512, 384, 1), pack(128, 512, 1)
+        t1, t1b = _act(E, torch, device, rng, n, h, w, 128, 1), _act(E, torch, device, rng, n, 2 * h - 1, 2 * w, 256, 1)
+        run = lambda tm: E.bottleneck_chain(None, pc3, pc1, t1, None, t1b=t1b, t1b_stride=2, tile_m=tm)
+        tiles = (0,)
+    else:
+        pc3 = pack(1024, 256, 1)
+        t1, res = _act(E, torch, device, rng, n, h, w, 256, 1), _act(E, torch, device, rng, n, h, w, 1024, 1)
+        run = lambda tm: E.bottleneck_chain(None, pc3, None, t1, res, tile_m=tm)
+        tiles = (0,)
+    outs = {}
+    for tm in tiles:
+        out, t1n = run(tm)
+        outs[f"tile_m{tm}"] = [_raw(torch, out.buf)] + ([_raw(torch, t1n.buf)] if t1n is not None else [])
+    torch.cuda.synchronize()
+    return outs, dict(fmt=1, view=None, res1_smaller=None)
+
+
+def _stem(E, torch, device, case_id, s):
+    rng = _rng(case_id)
+    wt = rng.standard_normal((64, 3, 7, 7), dtype=np.float32) / np.float32(12)
+    bn = {"weight": rng.random(64, dtype=np.float32) + np.float32(0.5), "bias": rng.standard_normal(64, dtype=np.float32) * np.float32(0.1),
+          "running_mean": rng.standard_normal(64, dtype=np.float32) * np.float32(0.1), "running_var": rng.random(64, dtype=np.float32) + np.float32(0.5)}
+    ps = E.pack_stem_fused(wt, bn, device)
+    c1 = E.pack_conv(rng.standard_normal((64, 64, 1, 1), dtype=np.float32) / np.float32(8), rng.standard_normal(64, dtype=np.float32) * np.float32(0.1),
+                     None, 1, 0, device, precision="f16x3")
+    img = torch.from_numpy(rng.integers(0, 256, (s["n"], s["h"], s["w"], 3), dtype=np.uint8)).to(device)
+    out, t1 = E.stem_relu_pool_u8(ps, img, conv1=c1)
+    torch.cuda.synchronize()
+    # (the pooled map itself comes from the stem's pool-then-scale path, max(v, 0): no -0.0 there; t1 is first so the sign check reads it)
+    return {"fused": [_raw(torch, t1.buf), _raw(torch, out.buf)]}, dict(fmt=1, view=None, res1_smaller=None)
+
+
+def run_case(case_id, kind, spec, device):
+    """-> ({tile label: [int32 tensor per output buffer]}, info)"""
+    import torch
+    from face_crop_plus_amd import engine as E
+    return {"conv": _conv, "chain": _chain, "stem": _stem}[kind](E, torch, device, case_id, spec)
+
+
+def digest(tensors):
+    import hashlib
+    hs = hashlib.sha256()
+    for t in tensors:
+        hs.update(t.cpu().numpy().tobytes())
+    return hs.hexdigest()
