@@ -62,6 +62,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="keep the background of the crops and blur it: sigma in output pixels, 0.5..16, of a Gaussian over "
                         "the background pixels alone (not with --background; --foreground / --feather apply); by default "
                         "the crops keep their background")
+    p.add_argument("-rf", "--refine", type=int, default=argparse.SUPPRESS,
+                   help="follow the image's edges with the matte: window radius in output pixels, 1..16, of a guided filter "
+                        "of the mask (with --background or --background-blur, in place of --feather); by default the edge is "
+                        "the feathered mask")
+    p.add_argument("-re", "--refine-eps", type=int, default=argparse.SUPPRESS,
+                   help="regulariser of --refine in gray levels squared, 1..4096 (default 64)")
     p.add_argument("-cl", "--clahe", type=float, default=argparse.SUPPRESS,
                    help="equalise the contrast of the crops: clip limit (> 0, usually 2.0) of a contrast-limited adaptive "
                         "histogram equalisation of their luma; by default the crops keep their contrast")

@@ -63,6 +63,8 @@ class Cropper:
         foreground: list[int] | None = None,
         feather: int | None = None,
         background_blur: float | None = None,
+        refine: int | None = None,
+        refine_eps: int | None = None,
         clahe: float | None = None,
         clahe_grid: int | None = None,
         interpolation: str = "linear",
@@ -113,6 +115,16 @@ class Cropper:
         INTEGRATION.md section 2i).  It sits where ``background`` sits, cannot be combined with it (ValueError), creates
         the parser and needs aligned crops like it; a face without a background pixel is written unchanged.  None (the
         default) launches nothing.
+        ``refine``: follow the image's edges with the matte — the window radius, in output pixels (an int 1..16), of a
+        guided filter (He, Sun, Tang) of the parser's hard mask with the gray of the crop as the guide: the alpha stays
+        the parser's over flat regions and snaps to the crop's own edges along hair, ears and shoulders, where the label
+        map is a few pixels off and staircase-shaped.  ``refine_eps`` (an int 1..4096, in gray levels squared; None: 64)
+        is the filter's regulariser: below it a variation of the guide counts as flat.  It is stated in integers and held
+        byte for byte to a numpy reference (``matte.refine_alpha``).  It needs ``background``
+        or ``background_blur`` and replaces the Gaussian feather as their soft edge: an explicit ``feather`` beside it
+        raises ValueError and ``Cropper.feather`` is 0; ``refine_eps`` without ``refine`` raises ValueError.  Everything
+        else about the two modes is unchanged: the guide is the crop the composite uses (after ``clahe``), the blurred
+        background still comes from the hard mask, mask files are untouched.  None (the default) launches nothing.
         ``clahe``: equalise the contrast of every crop — the clip limit (finite, > 0; 2.0 is the usual value) of a
         contrast-limited adaptive histogram equalisation of the luma on a ``clahe_grid`` x ``clahe_grid`` tiling (1..16;
         None: 8), ``cv2.createCLAHE(clahe, (grid, grid)).apply(Y)`` between ``cv2.cvtColor(crop, COLOR_RGB2YCrCb)`` and
@@ -156,9 +168,20 @@ class Cropper:
         if self.background is not None and self.background_blur is not None:
             raise ValueError("background and background_blur exclude each other: the background is filled or blurred")
         self.blur_taps = None if self.background_blur is None else matting.blur_taps(self.background_blur)
+        self.refine = matting.check_refine(refine)
+        if self.refine is None:
+            if refine_eps is not None:
+                raise ValueError("refine_eps needs refine: without it it would do nothing")
+            self.refine_eps = None
+        else:
+            self.refine_eps = matting.check_refine_eps(refine_eps)
+            if feather is not None:
+                raise ValueError("refine and feather exclude each other: the soft edge is the guided filter's or the Gaussian's")
         if self.background is None and self.background_blur is None:
             if foreground is not None or feather is not None:
                 raise ValueError("foreground / feather need background or background_blur: without one they would do nothing")
+            if self.refine is not None:
+                raise ValueError("refine needs background or background_blur: without one it would do nothing")
             self.foreground, self.foreground_bits, self.feather = None, 0, None
         else:
             if det_threshold is None and landmarks is None:
@@ -167,7 +190,7 @@ class Cropper:
                                  "themselves")
             self.foreground_bits = matting.check_foreground(foreground)
             self.foreground = tuple(c for c in range(matting.NUM_CLASSES) if self.foreground_bits >> c & 1)
-            self.feather = matting.check_feather(feather)
+            self.feather = 0 if self.refine is not None else matting.check_feather(feather)
         self.clahe = equalizing.check_clahe(clahe)
         if self.clahe is None:
             if clahe_grid is not None:
@@ -335,7 +358,8 @@ class Cropper:
         """What ``background`` does, for crops and label maps one already has: (F,H,W,3) uint8 RGB crops and (F,H,W)
         uint8 labels -> (the composited crops (F,H,W,3) uint8, the alpha (F,H,W) uint8), with this Cropper's
         ``background`` / ``foreground`` / ``feather`` (``matte.matte``), or with its ``background_blur``
-        (``matte.matte_blur``).  The alpha is what an RGBA file needs."""
+        (``matte.matte_blur``); with ``refine`` the alpha is the guided filter's (``matte.refine_alpha``) and the
+        composite goes through it.  The alpha is what an RGBA file needs."""
         if self.background is None and self.background_blur is None:
             raise ValueError("Cropper.matte needs a Cropper with background=... or background_blur=...")
         crops, labels = np.ascontiguousarray(crops), np.ascontiguousarray(labels)
@@ -347,13 +371,19 @@ class Cropper:
             return np.zeros(crops.shape, np.uint8), np.zeros(labels.shape, np.uint8)
         with torch.cuda.device(self.device):
             crops_dev, labels_dev = torch.from_numpy(crops).to(self.device), torch.from_numpy(labels).to(self.device)
-            if self.background_blur is not None:
-                out, alpha = matting.matte_blur(crops_dev, labels_dev, self.foreground_bits, self.feather, self.blur_taps,
-                                                with_alpha=True)
-            else:
-                out, alpha = matting.matte(crops_dev, labels_dev, self.foreground_bits, self.feather, self.background,
-                                           with_alpha=True)
+            out, alpha = self._matte_device(crops_dev, labels_dev, with_alpha=True)
             return out.cpu().numpy(), alpha.cpu().numpy()
+
+    def _matte_device(self, crops_dev, labels_dev, with_alpha=False):
+        """The matte step on device tensors: the refined alpha first when ``refine`` is set, then the composite."""
+        refined = {}
+        if getattr(self, "refine", None) is not None:
+            refined["alpha"] = matting.refine_alpha(crops_dev, labels_dev, self.foreground_bits, self.refine, self.refine_eps)
+        if self.background_blur is not None:
+            return matting.matte_blur(crops_dev, labels_dev, self.foreground_bits, self.feather, self.blur_taps,
+                                      with_alpha=with_alpha, **refined)
+        return matting.matte(crops_dev, labels_dev, self.foreground_bits, self.feather, self.background,
+                             with_alpha=with_alpha, **refined)
 
     def equalize(self, crops: np.ndarray) -> np.ndarray:
         """What ``clahe`` does, for crops one already has: (F,H,W,3) uint8 RGB -> the equalised crops (F,H,W,3) uint8,
@@ -624,11 +654,7 @@ class Cropper:
                         faces_dev = equalizing.clahe(faces_dev, self.clahe, self.clahe_grid)
                 if labels is not None:
                     with trace.range("fcp:matte"):
-                        if self.background_blur is not None:
-                            faces_dev, _ = matting.matte_blur(faces_dev, labels, self.foreground_bits, self.feather,
-                                                              self.blur_taps)
-                        else:
-                            faces_dev, _ = matting.matte(faces_dev, labels, self.foreground_bits, self.feather, self.background)
+                        faces_dev, _ = self._matte_device(faces_dev, labels)
                 # the host copy, if the host encoder needs one, is the equalised / matted crop as well
                 faces = None if self.encoder == "device" else faces_dev.cpu().numpy()
             if self.encoder == "device" and isinstance(faces_dev, torch.Tensor):

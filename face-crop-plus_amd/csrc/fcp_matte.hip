@@ -7,6 +7,8 @@
 // and two such groups per lane.  A workgroup stages the mask of its tile and runs the horizontal pass into LDS
 // (fcp_feather.h: Tile::stage); then a lane runs the vertical pass of a group in registers, reads the 12 crop bytes of
 // the group, composites and writes out (and alpha) once.  feather 0 is its own instantiation with no LDS and no barrier.
+// fcp_matte_alpha_u8 is the same composite with an alpha the caller has (the refined one of fcp_matte_refine.hip): the
+// feather-0 instantiation once more, a group's four alpha bytes read from the plane where that one reads four labels.
 // Every output byte has one writer and depends on its own crop pixel and on labels only, so out may be the crops
 // themselves and the result is the same from run to run.
 //
@@ -35,11 +37,12 @@ constexpr int kThreads = 256;
 constexpr int kTileW = 64;             // output pixels of a tile row: 16 groups of four
 constexpr int kTileH = 32;
 
-// crops and out may be the same array: neither is __restrict__.
-template <int R>
+// crops and out may be the same array: neither is __restrict__.  Plane (with R == 0): labels is an alpha plane, read as it is.
+template <int R, bool Plane = false>
 __global__ void __launch_bounds__(kThreads) matte_kernel(const uint8_t* crops, const uint8_t* __restrict__ labels, int h, int w,
                                                          int tiles_x, uint32_t bits, uint32_t fill, uint8_t* out,
                                                          uint8_t* alpha) {
+  static_assert(!Plane || R == 0, "a given alpha has no feather");
   using Feather = Tile<R, kTileW, kTileH>;
   extern __shared__ uint2 lds[];         // R > 0: the feather's tile; R == 0: none
   const int f = blockIdx.y;
@@ -59,8 +62,12 @@ __global__ void __launch_bounds__(kThreads) matte_kernel(const uint8_t* crops, c
     const int npx = min(4, w - x);
     const size_t pixel = ((size_t)f * h + y) * w + x;
     uint32_t a[4];
-    Feather::alpha(lds, r, g, labels + pixel, npx, bits, a);
-    if (alpha != nullptr) store_u8(alpha + pixel, npx, a);
+    if constexpr (Plane) {
+      load_u8(labels + pixel, npx, a);
+    } else {
+      Feather::alpha(lds, r, g, labels + pixel, npx, bits, a);
+      if (alpha != nullptr) store_u8(alpha + pixel, npx, a);
+    }
 
     uint32_t c[3];
     load_rgb(crops + pixel * 3, npx, c);
@@ -74,13 +81,13 @@ __global__ void __launch_bounds__(kThreads) matte_kernel(const uint8_t* crops, c
   }
 }
 
-template <int R>
+template <int R, bool Plane = false>
 void launch(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t bits, uint32_t fill, uint8_t* out,
             uint8_t* alpha, hipStream_t stream) {
   const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
   constexpr size_t lds = Tile<R, kTileW, kTileH>::kBytes;
-  hipLaunchKernelGGL(matte_kernel<R>, dim3(tiles_x * tiles_y, f), dim3(kThreads), lds, stream, crops, labels, h, w, tiles_x, bits,
-                     fill, out, alpha);
+  hipLaunchKernelGGL((matte_kernel<R, Plane>), dim3(tiles_x * tiles_y, f), dim3(kThreads), lds, stream, crops, labels, h, w,
+                     tiles_x, bits, fill, out, alpha);
 }
 
 }  // namespace
@@ -105,6 +112,22 @@ extern "C" int fcp_matte_u8(const uint8_t* crops, const uint8_t* labels, int f, 
     case 5: launch<2>(crops, labels, f, h, w, class_bits, fill, out, alpha, s); break;
     default: launch<3>(crops, labels, f, h, w, class_bits, fill, out, alpha, s); break;
   }
+  FCP_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int fcp_matte_alpha_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, int bg_r, int bg_g, int bg_b,
+                                  uint8_t* out, fcp_stream_t stream) {
+  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "matte_alpha: bad sizes (f %d, h %d, w %d)", f, h, w);
+  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "matte_alpha: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h,
+              w);
+  FCP_REQUIRE(f <= 65535, "matte_alpha: at most 65535 crops per call (got %d)", f);
+  FCP_REQUIRE(bg_r >= 0 && bg_r <= 255 && bg_g >= 0 && bg_g <= 255 && bg_b >= 0 && bg_b <= 255,
+              "matte_alpha: fill components must be 0..255 (got %d, %d, %d)", bg_r, bg_g, bg_b);
+  if (f == 0) return 0;
+  FCP_REQUIRE(crops && alpha && out, "matte_alpha: null pointer");
+  const uint32_t fill = (uint32_t)bg_r | ((uint32_t)bg_g << 8) | ((uint32_t)bg_b << 16);
+  launch<0, true>(crops, alpha, f, h, w, 0u, fill, out, nullptr, (hipStream_t)stream);
   FCP_LAUNCH_OK();
   return 0;
 }

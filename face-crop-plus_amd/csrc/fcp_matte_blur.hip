@@ -132,12 +132,14 @@ constexpr size_t cols_lds_bytes(int radius) {
          (2 * kMaxRadius + 1) * sizeof(uint32_t);
 }
 
-// crops and out may be the same array: neither is __restrict__.
-template <int R>
+// crops and out may be the same array: neither is __restrict__.  Plane (with R == 0, fcp_matte_blur_alpha_u8): labels is an
+// alpha plane the caller has (the refined one of fcp_matte_refine.hip), read as it is; N and D are those of the rows pass.
+template <int R, bool Plane = false>
 __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crops, const uint8_t* __restrict__ labels,
                                                              const uint4* __restrict__ sums, int h, int w, int tiles_x,
                                                              uint32_t bits, BlurTaps taps, int radius, uint8_t* out,
                                                              uint8_t* alpha) {
+  static_assert(!Plane || R == 0, "a given alpha has no feather");
   using Feather = Tile<R, kTileW, kTileH>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* col = reinterpret_cast<uint4*>(smem);                                    // (kTileH + 2 r) rows of kTileW sums
@@ -183,8 +185,12 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
     }
 
     uint32_t a[4];
-    Feather::alpha(hsum, r, g, labels + pixel, npx, bits, a);
-    if (alpha != nullptr) store_u8(alpha + pixel, npx, a);
+    if constexpr (Plane) {
+      load_u8(labels + pixel, npx, a);
+    } else {
+      Feather::alpha(hsum, r, g, labels + pixel, npx, bits, a);
+      if (alpha != nullptr) store_u8(alpha + pixel, npx, a);
+    }
 
     uint32_t c[3];
     load_rgb(crops + pixel * 3, npx, c);
@@ -200,12 +206,12 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
   }
 }
 
-template <int R>
+template <int R, bool Plane = false>
 void launch_cols(const uint8_t* crops, const uint8_t* labels, const uint4* sums, int f, int h, int w, uint32_t bits,
                  const BlurTaps& taps, int radius, uint8_t* out, uint8_t* alpha, hipStream_t stream) {
   const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
-  hipLaunchKernelGGL(blur_cols_kernel<R>, dim3(tiles_x * tiles_y, f), dim3(kThreads), cols_lds_bytes<R>(radius), stream, crops,
-                     labels, sums, h, w, tiles_x, bits, taps, radius, out, alpha);
+  hipLaunchKernelGGL((blur_cols_kernel<R, Plane>), dim3(tiles_x * tiles_y, f), dim3(kThreads), cols_lds_bytes<R>(radius), stream,
+                     crops, labels, sums, h, w, tiles_x, bits, taps, radius, out, alpha);
 }
 
 }  // namespace
@@ -215,34 +221,37 @@ extern "C" int64_t fcp_matte_blur_workspace_bytes(int f, int h, int w) {
   return (int64_t)f * h * w * (int64_t)sizeof(uint4);
 }
 
-extern "C" int fcp_matte_blur_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits,
-                                 int feather, const uint16_t* taps, int radius, uint8_t* out, uint8_t* alpha, void* workspace,
-                                 int64_t workspace_bytes, fcp_stream_t stream) {
-  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "matte_blur: bad sizes (f %d, h %d, w %d)", f, h, w);
-  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "matte_blur: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h,
-              w);
-  FCP_REQUIRE(f <= 65535, "matte_blur: at most 65535 crops per call (got %d)", f);
-  FCP_REQUIRE(feather == 0 || feather == 3 || feather == 5 || feather == 7, "matte_blur: feather must be 0, 3, 5 or 7 (got %d)",
+namespace {
+
+// Both entry points: `alpha_in` null is fcp_matte_blur_u8 (the feathered alpha, written to `alpha` when asked for), else
+// fcp_matte_blur_alpha_u8 (the composite through the given plane).
+int matte_blur(const char* who, const uint8_t* crops, const uint8_t* labels, const uint8_t* alpha_in, bool given, int f, int h, int w,
+               uint32_t class_bits, int feather, const uint16_t* taps, int radius, uint8_t* out, uint8_t* alpha, void* workspace,
+               int64_t workspace_bytes, fcp_stream_t stream) {
+  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "%s: bad sizes (f %d, h %d, w %d)", who, f, h, w);
+  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "%s: crops of at most %d x %d px (got h %d, w %d)", who, kMaxSide, kMaxSide, h, w);
+  FCP_REQUIRE(f <= 65535, "%s: at most 65535 crops per call (got %d)", who, f);
+  FCP_REQUIRE(feather == 0 || feather == 3 || feather == 5 || feather == 7, "%s: feather must be 0, 3, 5 or 7 (got %d)", who,
               feather);
-  FCP_REQUIRE((class_bits >> kClasses) == 0, "matte_blur: class_bits 0x%x names a class at or above %d", class_bits, kClasses);
-  FCP_REQUIRE(radius >= kMinRadius && radius <= kMaxRadius, "matte_blur: radius must be %d..%d (got %d)", kMinRadius, kMaxRadius,
+  FCP_REQUIRE((class_bits >> kClasses) == 0, "%s: class_bits 0x%x names a class at or above %d", who, class_bits, kClasses);
+  FCP_REQUIRE(radius >= kMinRadius && radius <= kMaxRadius, "%s: radius must be %d..%d (got %d)", who, kMinRadius, kMaxRadius,
               radius);
-  FCP_REQUIRE(taps != nullptr, "matte_blur: null taps");
+  FCP_REQUIRE(taps != nullptr, "%s: null taps", who);
   // the 32-bit sums of the kernels hold because of this
   BlurTaps t = {};
   uint32_t total = 0;
   for (int k = 0; k <= radius; ++k) {
-    FCP_REQUIRE(taps[k] >= 1, "matte_blur: tap %d is 0: every tap must be at least 1", k);
+    FCP_REQUIRE(taps[k] >= 1, "%s: tap %d is 0: every tap must be at least 1", who, k);
     t.t[k] = taps[k];
     total += (k == 0 ? 1u : 2u) * taps[k];
   }
-  FCP_REQUIRE(total == kTapSum, "matte_blur: the taps must sum to %u over the window (got %u)", kTapSum, total);
+  FCP_REQUIRE(total == kTapSum, "%s: the taps must sum to %u over the window (got %u)", who, kTapSum, total);
   if (f == 0) return 0;
-  FCP_REQUIRE(crops && labels && out, "matte_blur: null pointer");
+  FCP_REQUIRE(crops && labels && out && (!given || alpha_in), "%s: null pointer", who);
   const int64_t need = fcp_matte_blur_workspace_bytes(f, h, w);
-  FCP_REQUIRE(workspace != nullptr && workspace_bytes >= need, "matte_blur: the workspace needs %lld bytes (got %lld)",
+  FCP_REQUIRE(workspace != nullptr && workspace_bytes >= need, "%s: the workspace needs %lld bytes (got %lld)", who,
               (long long)need, (long long)workspace_bytes);
-  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "matte_blur: the workspace must be 16-byte aligned");
+  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
   uint4* sums = static_cast<uint4*>(workspace);
   const int row_tiles_x = fcp_cdiv(w, kRowTileW), row_tiles_y = fcp_cdiv(h, kRowTileH);
@@ -250,12 +259,32 @@ extern "C" int fcp_matte_blur_u8(const uint8_t* crops, const uint8_t* labels, in
                      (kRowTileH * kRowPitch + 2 * kMaxRadius + 1) * sizeof(uint32_t), s, crops, labels, h, w, row_tiles_x,
                      class_bits, t, radius, sums);
   FCP_LAUNCH_OK();
-  switch (feather) {
-    case 0: launch_cols<0>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
-    case 3: launch_cols<1>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
-    case 5: launch_cols<2>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
-    default: launch_cols<3>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+  if (given) {
+    launch_cols<0, true>(crops, alpha_in, sums, f, h, w, class_bits, t, radius, out, nullptr, s);
+  } else {
+    switch (feather) {
+      case 0: launch_cols<0>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+      case 3: launch_cols<1>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+      case 5: launch_cols<2>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+      default: launch_cols<3>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
+    }
   }
   FCP_LAUNCH_OK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int fcp_matte_blur_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather,
+                                 const uint16_t* taps, int radius, uint8_t* out, uint8_t* alpha, void* workspace,
+                                 int64_t workspace_bytes, fcp_stream_t stream) {
+  return matte_blur("matte_blur", crops, labels, nullptr, false, f, h, w, class_bits, feather, taps, radius, out, alpha, workspace,
+                    workspace_bytes, stream);
+}
+
+extern "C" int fcp_matte_blur_alpha_u8(const uint8_t* crops, const uint8_t* labels, const uint8_t* alpha, int f, int h, int w,
+                                       uint32_t class_bits, const uint16_t* taps, int radius, uint8_t* out, void* workspace,
+                                       int64_t workspace_bytes, fcp_stream_t stream) {
+  return matte_blur("matte_blur_alpha", crops, labels, alpha, true, f, h, w, class_bits, 0, taps, radius, out, nullptr, workspace,
+                    workspace_bytes, stream);
 }

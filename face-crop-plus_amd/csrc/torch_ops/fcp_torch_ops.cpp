@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / matte / clahe / matte_blur
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -525,6 +525,78 @@ std::tuple<Tensor, Tensor> matte_blur(const Tensor& crops, const Tensor& labels,
   return {out, alpha};
 }
 
+// The shape checks the matte family shares: crops (f,h,w,3) and a plane (f,h,w) of its own, both uint8 on one device.
+static void crops_and_plane(const Tensor& crops, const Tensor& plane, const char* name, int64_t& f, int64_t& h, int64_t& w) {
+  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
+  f = crops.size(0), h = crops.size(1), w = crops.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
+  TORCH_CHECK(plane.get_device() == crops.get_device() && plane.dim() == 3 && plane.size(0) == f && plane.size(1) == h &&
+                  plane.size(2) == w, name, " must be (", f, ",", h, ",", w, ") uint8 on the device of the crops");
+}
+
+// The guided-filter alpha (f,h,w) uint8 of crops (f,h,w,3) uint8 and their label maps (f,h,w) uint8
+// (fcp_matte_refine_u8); the 8-bytes-per-pixel workspace lives for the call.
+Tensor matte_refine(const Tensor& crops, const Tensor& labels, int64_t class_bits, int64_t radius, int64_t eps) {
+  dev(crops, "crops", at::kByte);
+  dev(labels, "labels", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  int64_t f, h, w;
+  crops_and_plane(crops, labels, "labels", f, h, w);
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  for (int64_t v : {radius, eps}) TORCH_CHECK(v >= INT_MIN && v <= INT_MAX, "radius / eps past int");
+  Tensor alpha = at::empty({f, h, w}, crops.options());
+  const int64_t need = fcp_matte_refine_workspace_bytes((int)f, (int)h, (int)w);
+  Tensor work = at::empty({need < 0 ? 0 : need}, crops.options());
+  ok(fcp_matte_refine_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits,
+                         (int)radius, (int)eps, alpha.data_ptr<uint8_t>(), work.data_ptr(), work.numel(), cur_stream()),
+     "fcp::matte_refine");
+  return alpha;
+}
+
+// Crops (f,h,w,3) uint8 over a uniform fill through an alpha plane (f,h,w) uint8 of the caller's (fcp_matte_alpha_u8).
+Tensor matte_alpha(const Tensor& crops, const Tensor& alpha, int64_t bg_r, int64_t bg_g, int64_t bg_b) {
+  dev(crops, "crops", at::kByte);
+  dev(alpha, "alpha", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  int64_t f, h, w;
+  crops_and_plane(crops, alpha, "alpha", f, h, w);
+  for (int64_t v : {bg_r, bg_g, bg_b}) TORCH_CHECK(v >= INT_MIN && v <= INT_MAX, "fill past int");
+  Tensor out = at::empty_like(crops);
+  ok(fcp_matte_alpha_u8(crops.data_ptr<uint8_t>(), alpha.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (int)bg_r, (int)bg_g,
+                        (int)bg_b, out.data_ptr<uint8_t>(), cur_stream()),
+     "fcp::matte_alpha");
+  return out;
+}
+
+// Crops (f,h,w,3) uint8 over their own mask-normalised background blur (the hard mask of labels) through an alpha plane
+// (f,h,w) uint8 of the caller's (fcp_matte_blur_alpha_u8).  taps as in matte_blur.
+Tensor matte_blur_alpha(const Tensor& crops, const Tensor& labels, const Tensor& alpha, int64_t class_bits, at::IntArrayRef taps) {
+  dev(crops, "crops", at::kByte);
+  dev(labels, "labels", at::kByte);
+  dev(alpha, "alpha", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  int64_t f, h, w;
+  crops_and_plane(crops, labels, "labels", f, h, w);
+  crops_and_plane(crops, alpha, "alpha", f, h, w);
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  const int64_t radius = (int64_t)taps.size() - 1;
+  TORCH_CHECK(radius >= 3 && radius <= 48, "matte_blur_alpha: taps must be t[0..radius] with radius 3..48 (got ", taps.size(),
+              " taps)");
+  uint16_t t16[49];
+  for (int64_t k = 0; k <= radius; ++k) {
+    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, "matte_blur_alpha: tap ", k, " past 16 bits");
+    t16[k] = (uint16_t)taps[k];
+  }
+  Tensor out = at::empty_like(crops);
+  const int64_t need = fcp_matte_blur_workspace_bytes((int)f, (int)h, (int)w);
+  Tensor work = at::empty({need < 0 ? 0 : need}, crops.options());
+  ok(fcp_matte_blur_alpha_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), alpha.data_ptr<uint8_t>(), (int)f, (int)h,
+                             (int)w, (uint32_t)class_bits, t16, (int)radius, out.data_ptr<uint8_t>(), work.data_ptr(),
+                             work.numel(), cur_stream()),
+     "fcp::matte_blur_alpha");
+  return out;
+}
+
 // Crops (f,h,w,3) uint8 with the luma equalised by CLAHE on a grid x grid tiling (fcp_clahe_u8); the LUT workspace
 // lives for the call.
 Tensor clahe(const Tensor& crops, int64_t grid, double clip_limit) {
@@ -608,6 +680,9 @@ TORCH_LIBRARY(fcp, m) {
         "-> (Tensor, Tensor)");
   m.def("clahe(Tensor crops, int grid, float clip_limit) -> Tensor");
   m.def("matte_blur(Tensor crops, Tensor labels, int class_bits, int feather, int[] taps, bool with_alpha) -> (Tensor, Tensor)");
+  m.def("matte_refine(Tensor crops, Tensor labels, int class_bits, int radius, int eps) -> Tensor");
+  m.def("matte_alpha(Tensor crops, Tensor alpha, int bg_r, int bg_g, int bg_b) -> Tensor");
+  m.def("matte_blur_alpha(Tensor crops, Tensor labels, Tensor alpha, int class_bits, int[] taps) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -638,6 +713,9 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("matte", &matte);
   m.impl("clahe", &clahe);
   m.impl("matte_blur", &matte_blur);
+  m.impl("matte_refine", &matte_refine);
+  m.impl("matte_alpha", &matte_alpha);
+  m.impl("matte_blur_alpha", &matte_blur_alpha);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

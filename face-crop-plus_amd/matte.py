@@ -11,6 +11,10 @@ are on the device already (``fcp_matte_u8`` / ``torch.ops.fcp.matte``).
 
     B     = (N + D // 2) // D,  N and D the Gaussian window sums of the BACKGROUND pixels' colours and of their count
             (``fcp_matte_blur_u8`` / ``torch.ops.fcp.matte_blur``, two launches), with integer taps made here from sigma
+
+``Cropper(refine=R)`` (section 2k) replaces the Gaussian feather by a guided filter of the hard mask, the gray of the
+crop as the guide (``refine_alpha``: ``fcp_matte_refine_u8`` / ``torch.ops.fcp.matte_refine``, two launches); ``matte``
+and ``matte_blur`` then composite through that plane (``alpha=``).
 """
 from __future__ import annotations
 
@@ -29,6 +33,8 @@ NUM_CLASSES = 19            # bise.NUM_CLASSES: the label maps are BiSeNet's
 MIN_SIGMA, MAX_SIGMA = 0.5, 16.0
 MIN_RADIUS, MAX_RADIUS = 3, 48
 TAP_SUM = 4096
+MIN_REFINE, MAX_REFINE = 1, 16
+MIN_REFINE_EPS, MAX_REFINE_EPS, DEFAULT_REFINE_EPS = 1, 4096, 64
 
 
 def _is_int(v) -> bool:
@@ -85,6 +91,26 @@ def check_blur(sigma):
     return float(sigma)
 
 
+def check_refine(refine):
+    """``refine`` of the Cropper -> None (off) or the window radius of the guided filter in output pixels, an int 1..16."""
+    if refine is None:
+        return None
+    if not _is_int(refine) or not MIN_REFINE <= int(refine) <= MAX_REFINE:
+        raise ValueError(f"refine must be None or an int {MIN_REFINE}..{MAX_REFINE} (a radius in pixels), not {refine!r}")
+    return int(refine)
+
+
+def check_refine_eps(refine_eps) -> int:
+    """``refine_eps`` of the Cropper -> the regulariser of the guided filter in gray levels squared, an int 1..4096
+    (None: 64, about 1e-3 of the [0, 1] range squared)."""
+    if refine_eps is None:
+        return DEFAULT_REFINE_EPS
+    if not _is_int(refine_eps) or not MIN_REFINE_EPS <= int(refine_eps) <= MAX_REFINE_EPS:
+        raise ValueError(f"refine_eps must be None or an int {MIN_REFINE_EPS}..{MAX_REFINE_EPS} (gray levels squared), "
+                         f"not {refine_eps!r}")
+    return int(refine_eps)
+
+
 def blur_taps(sigma) -> list:
     """sigma -> the integer taps t[0..r] of the background blur, in float64: r = min(48, max(3, ceil(3 sigma))),
     g_k = exp(-k^2 / (2 sigma^2)), s = g_0 + 2 sum g_k, t_k = max(1, floor(4096 g_k / s)) for k >= 1 and t_0 the rest of
@@ -101,14 +127,45 @@ def blur_taps(sigma) -> list:
     return t
 
 
-def matte_blur(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, feather: int, taps, with_alpha: bool = False):
+def _check_alpha(alpha, crops_dev):
+    assert alpha.dtype == torch.uint8 and alpha.is_contiguous() and tuple(alpha.shape) == tuple(crops_dev.shape[:3])
+    assert alpha.device == crops_dev.device
+
+
+def refine_alpha(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, radius: int, eps: int) -> torch.Tensor:
+    """crops (F,H,W,3) u8 and labels (F,H,W) u8, device -> alpha (F,H,W) u8, device: the hard mask of the labels filtered by
+    a guided filter of window radius ``radius`` (1..16) and regulariser ``eps`` (1..4096) with the gray of the crop as the
+    guide, in integers.  Two launches and a workspace of 8 bytes per pixel that lives for the
+    call; H, W <= 8192."""
+    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
+    assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and tuple(labels_dev.shape) == tuple(crops_dev.shape[:3])
+    if T.ENABLED:
+        return T.load().matte_refine(crops_dev, labels_dev, int(class_bits), int(radius), int(eps))
+    f, h, w, _ = crops_dev.shape
+    alpha = torch.empty((f, h, w), dtype=torch.uint8, device=crops_dev.device)
+    need = max(int(N.lib().fcp_matte_refine_workspace_bytes(f, h, w)), 0)
+    work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
+    N.check(N.lib().fcp_matte_refine_u8(N.ptr(crops_dev), N.ptr(labels_dev), f, h, w, int(class_bits), int(radius), int(eps),
+                                        N.ptr(alpha), N.ptr(work), need, N.stream_ptr()), "fcp_matte_refine_u8")
+    return alpha
+
+
+def matte_blur(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, feather: int, taps, with_alpha: bool = False,
+               alpha: torch.Tensor | None = None):
     """crops (F,H,W,3) u8 and labels (F,H,W) u8, device -> (out (F,H,W,3) u8, alpha (F,H,W) u8 or None), device: the
     crops over their own mask-normalised background blur with the taps t[0..r] of ``blur_taps``.  Two launches and a
-    workspace of 16 bytes per pixel that lives for the call; H, W <= 8192."""
+    workspace of 16 bytes per pixel that lives for the call; H, W <= 8192.  With ``alpha`` (F,H,W) u8 (``refine_alpha``'s)
+    the composite goes through that plane instead of the feathered mask: ``feather`` is not used, and the plane itself
+    comes back where ``with_alpha`` asks for one."""
     assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
     assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and tuple(labels_dev.shape) == tuple(crops_dev.shape[:3])
     taps = [int(t) for t in taps]
-    if T.ENABLED:
+    if alpha is not None:
+        _check_alpha(alpha, crops_dev)
+        if T.ENABLED:
+            out = T.load().matte_blur_alpha(crops_dev, labels_dev, alpha, int(class_bits), taps)
+            return out, (alpha if with_alpha else None)
+    elif T.ENABLED:
         out, alpha = T.load().matte_blur(crops_dev, labels_dev, int(class_bits), int(feather), taps, bool(with_alpha))
         return out, (alpha if with_alpha else None)
     if not MIN_RADIUS + 1 <= len(taps) <= MAX_RADIUS + 1 or min(taps) < 0 or max(taps) > 65535:
@@ -116,22 +173,39 @@ def matte_blur(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: in
                            f"(got {len(taps)} taps)")
     f, h, w, _ = crops_dev.shape
     out = torch.empty_like(crops_dev)
-    alpha = torch.empty((f, h, w), dtype=torch.uint8, device=crops_dev.device) if with_alpha else None
     need = max(int(N.lib().fcp_matte_blur_workspace_bytes(f, h, w)), 0)
     work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
     t16 = (ctypes.c_uint16 * len(taps))(*taps)
+    if alpha is not None:
+        N.check(N.lib().fcp_matte_blur_alpha_u8(N.ptr(crops_dev), N.ptr(labels_dev), N.ptr(alpha), f, h, w, int(class_bits), t16,
+                                                len(taps) - 1, N.ptr(out), N.ptr(work), need, N.stream_ptr()),
+                "fcp_matte_blur_alpha_u8")
+        return out, (alpha if with_alpha else None)
+    alpha = torch.empty((f, h, w), dtype=torch.uint8, device=crops_dev.device) if with_alpha else None
     N.check(N.lib().fcp_matte_blur_u8(N.ptr(crops_dev), N.ptr(labels_dev), f, h, w, int(class_bits), int(feather), t16,
                                       len(taps) - 1, N.ptr(out), N.ptr(alpha), N.ptr(work), need, N.stream_ptr()),
             "fcp_matte_blur_u8")
     return out, alpha
 
 
-def matte(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, feather: int, fill, with_alpha: bool = False):
+def matte(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, feather: int, fill, with_alpha: bool = False,
+          alpha: torch.Tensor | None = None):
     """crops (F,H,W,3) u8 and labels (F,H,W) u8, device -> (out (F,H,W,3) u8, alpha (F,H,W) u8 or None), device.  One
-    launch; H, W <= 8192."""
+    launch; H, W <= 8192.  With ``alpha`` (F,H,W) u8 (``refine_alpha``'s) the composite goes through that plane: the
+    labels, ``class_bits`` and ``feather`` are not used, and the plane itself comes back where ``with_alpha`` asks for one."""
     assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
     assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and tuple(labels_dev.shape) == tuple(crops_dev.shape[:3])
     r, g, b = (int(v) for v in fill)
+    if alpha is not None:
+        _check_alpha(alpha, crops_dev)
+        if T.ENABLED:
+            out = T.load().matte_alpha(crops_dev, alpha, r, g, b)
+        else:
+            f, h, w, _ = crops_dev.shape
+            out = torch.empty_like(crops_dev)
+            N.check(N.lib().fcp_matte_alpha_u8(N.ptr(crops_dev), N.ptr(alpha), f, h, w, r, g, b, N.ptr(out), N.stream_ptr()),
+                    "fcp_matte_alpha_u8")
+        return out, (alpha if with_alpha else None)
     if T.ENABLED:
         out, alpha = T.load().matte(crops_dev, labels_dev, int(class_bits), int(feather), r, g, b, bool(with_alpha))
         return out, (alpha if with_alpha else None)

@@ -591,6 +591,52 @@ int fcp_matte_blur_u8(const uint8_t* crops, const uint8_t* labels, int f, int h,
                       const uint16_t* taps, int radius, uint8_t* out, uint8_t* alpha, void* workspace, int64_t workspace_bytes,
                       fcp_stream_t stream);
 
+/* Guided-filter matte edge: the hard mask m of
+ * fcp_matte_u8 for class_bits, filtered with the gray of the crop as the
+ * guide, in integers throughout.  n = (2 radius + 1)^2, 1 <= radius <= 16,
+ * 1 <= eps <= 4096 (gray levels squared);
+ *   I     = (9798 R + 19235 G + 3735 B + 16384) >> 15,   p = m (0 / 255);
+ *   box(v) = the sum of v over the (2 radius + 1)^2 window, indices through
+ *           BORDER_REFLECT_101 iterated: n terms at every pixel;
+ *   cov   = n box(I p) - box(I) box(p),  var = n box(I I) - box(I)^2,
+ *   den   = var + eps n n;
+ *   rdiv(u, d) = sign(u) ((|u| + d / 2) / d);
+ *   A     = rdiv(4096 cov, den),  B = rdiv(4096 box(p) - A box(I), n);
+ *   q     = ((box(A) I + box(B) + 2048 n) >> 12) div n   (arithmetic shift,
+ *           floor division);   alpha = min(255, max(0, q)).
+ * workspace: fcp_matte_refine_workspace_bytes(f,h,w) = 8 f h w bytes of
+ * device memory, 16-byte aligned, contents irrelevant ((A, B) of every
+ * pixel); it must not overlap the other arrays.  alpha_out (f,h,w) is
+ * written once, by ordinary stores; crops, labels and alpha_out may start at
+ * any byte; nothing outside alpha_out and the workspace is written.  Two
+ * launches on `stream`, nothing allocated, no float, no atomics, the same
+ * bytes from run to run.
+ * f == 0 is a no-op; f < 0, h or w < 1 or > 8192, f > 65535, a radius outside
+ * 1..16, an eps outside 1..4096, a bit of class_bits at or above 19, or
+ * (f > 0) a null crops / labels / alpha_out, a workspace that is null, too
+ * small or misaligned fail with a message, before any HIP call
+ * (fcp_matte_refine_workspace_bytes then returns -1). */
+int64_t fcp_matte_refine_workspace_bytes(int f, int h, int w);
+int fcp_matte_refine_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int radius, int eps,
+                        uint8_t* alpha_out, void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
+
+/* The composites of fcp_matte_u8 and fcp_matte_blur_u8 through an alpha
+ * plane (f,h,w) uint8 of the caller's (fcp_matte_refine_u8's) in place of
+ * the feathered mask:
+ *   fcp_matte_alpha_u8:       out = (c * alpha + bg * (255 - alpha) + 127) / 255;
+ *   fcp_matte_blur_alpha_u8:  the same with B_ch of fcp_matte_blur_u8 as bg:
+ *       N, D and B_ch come from the HARD mask of labels and class_bits, as
+ *       there; where D == 0 (no background pixel in the window) B_ch = c_ch
+ *       and the pixel keeps its crop whatever its alpha.
+ * out MAY BE crops; alpha must not overlap out.  Arguments, workspace (16
+ * bytes per pixel for the blur), alignment, launches (one; two) and failures
+ * are those of the two siblings, less the feather; a null alpha fails too. */
+int fcp_matte_alpha_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, int bg_r, int bg_g, int bg_b, uint8_t* out,
+                       fcp_stream_t stream);
+int fcp_matte_blur_alpha_u8(const uint8_t* crops, const uint8_t* labels, const uint8_t* alpha, int f, int h, int w,
+                            uint32_t class_bits, const uint16_t* taps, int radius, uint8_t* out, void* workspace,
+                            int64_t workspace_bytes, fcp_stream_t stream);
+
 /* Contrast-limited adaptive histogram equalisation of the luma of crops
  * (f,h,w,3) uint8 RGB: cv2.createCLAHE(clip_limit,
  * (grid, grid)).apply(Y) between cv2.cvtColor(COLOR_RGB2YCrCb) and
