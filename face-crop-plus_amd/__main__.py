@@ -68,6 +68,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "the feathered mask")
     p.add_argument("-re", "--refine-eps", type=int, default=argparse.SUPPRESS,
                    help="regulariser of --refine in gray levels squared, 1..4096 (default 64)")
+    p.add_argument("-su", "--subject", choices=["largest"], default=argparse.SUPPRESS,
+                   help="keep one connected subject in the matte: 'largest' keeps the largest 8-connected component of the "
+                        "foreground, so other people and specks become background (with --background or --background-blur); "
+                        "by default every foreground pixel counts")
+    p.add_argument("-fh", "--fill-holes", type=int, default=argparse.SUPPRESS,
+                   help="fill the matte's pinholes: the largest enclosed background region, in output pixels "
+                        "(1..67108864), that becomes foreground (with --background or --background-blur); by default holes "
+                        "stay")
     p.add_argument("-cl", "--clahe", type=float, default=argparse.SUPPRESS,
                    help="equalise the contrast of the crops: clip limit (> 0, usually 2.0) of a contrast-limited adaptive "
                         "histogram equalisation of their luma; by default the crops keep their contrast")

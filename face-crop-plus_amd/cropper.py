@@ -65,6 +65,8 @@ class Cropper:
         background_blur: float | None = None,
         refine: int | None = None,
         refine_eps: int | None = None,
+        subject: str | None = None,
+        fill_holes: int | None = None,
         clahe: float | None = None,
         clahe_grid: int | None = None,
         interpolation: str = "linear",
@@ -125,6 +127,18 @@ class Cropper:
         raises ValueError and ``Cropper.feather`` is 0; ``refine_eps`` without ``refine`` raises ValueError.  Everything
         else about the two modes is unchanged: the guide is the crop the composite uses (after ``clahe``), the blurred
         background still comes from the hard mask, mask files are untouched.  None (the default) launches nothing.
+        ``subject`` / ``fill_holes``: keep one connected subject, whole — two repairs of the parser's hard mask before
+        either background mode (and ``refine``) sees it.  ``subject="largest"`` keeps the largest 8-connected component
+        of the foreground (among equal areas the one whose first pixel comes first in raster order), so that the
+        neighbours' heads and shoulders and the parser's specks become background; ``fill_holes=N`` (an int
+        1..67108864, in output pixels) then turns every 4-connected background region of at most N pixels that does not
+        touch the crop's border into foreground, so that the fill or the blur no longer shows through highlights on
+        glasses or between strands of hair.  The subject comes first: an island inside a hole counts in its area.  Both
+        are connected-component labelling on the device, in integers, held byte for byte to a numpy reference
+        (``matte.subject_mask``); the cleaned 0 / 1 map takes the label map's place for the
+        feather, the guided filter, the composite and the blur's background sums.  They need ``background`` or
+        ``background_blur`` (ValueError); mask files are untouched and a face without a foreground pixel behaves as
+        before.  None (the default) launches nothing.
         ``clahe``: equalise the contrast of every crop — the clip limit (finite, > 0; 2.0 is the usual value) of a
         contrast-limited adaptive histogram equalisation of the luma on a ``clahe_grid`` x ``clahe_grid`` tiling (1..16;
         None: 8), ``cv2.createCLAHE(clahe, (grid, grid)).apply(Y)`` between ``cv2.cvtColor(crop, COLOR_RGB2YCrCb)`` and
@@ -177,11 +191,15 @@ class Cropper:
             self.refine_eps = matting.check_refine_eps(refine_eps)
             if feather is not None:
                 raise ValueError("refine and feather exclude each other: the soft edge is the guided filter's or the Gaussian's")
+        self.subject = matting.check_subject(subject)
+        self.fill_holes = matting.check_fill_holes(fill_holes)
         if self.background is None and self.background_blur is None:
             if foreground is not None or feather is not None:
                 raise ValueError("foreground / feather need background or background_blur: without one they would do nothing")
             if self.refine is not None:
                 raise ValueError("refine needs background or background_blur: without one it would do nothing")
+            if self.subject is not None or self.fill_holes is not None:
+                raise ValueError("subject / fill_holes need background or background_blur: without one they would do nothing")
             self.foreground, self.foreground_bits, self.feather = None, 0, None
         else:
             if det_threshold is None and landmarks is None:
@@ -359,7 +377,8 @@ class Cropper:
         uint8 labels -> (the composited crops (F,H,W,3) uint8, the alpha (F,H,W) uint8), with this Cropper's
         ``background`` / ``foreground`` / ``feather`` (``matte.matte``), or with its ``background_blur``
         (``matte.matte_blur``); with ``refine`` the alpha is the guided filter's (``matte.refine_alpha``) and the
-        composite goes through it.  The alpha is what an RGBA file needs."""
+        composite goes through it; with ``subject`` / ``fill_holes`` the mask is cleaned first (``matte.subject_mask``).
+        The alpha is what an RGBA file needs."""
         if self.background is None and self.background_blur is None:
             raise ValueError("Cropper.matte needs a Cropper with background=... or background_blur=...")
         crops, labels = np.ascontiguousarray(crops), np.ascontiguousarray(labels)
@@ -375,15 +394,19 @@ class Cropper:
             return out.cpu().numpy(), alpha.cpu().numpy()
 
     def _matte_device(self, crops_dev, labels_dev, with_alpha=False):
-        """The matte step on device tensors: the refined alpha first when ``refine`` is set, then the composite."""
+        """The matte step on device tensors: the cleaned mask first when ``subject`` / ``fill_holes`` are set (it takes
+        the label map's place, as class 1), the refined alpha when ``refine`` is set, then the composite."""
+        bits = self.foreground_bits
+        subject, fill_holes = getattr(self, "subject", None), getattr(self, "fill_holes", None)
+        if subject is not None or fill_holes is not None:
+            labels_dev = matting.subject_mask(labels_dev, bits, subject is not None, fill_holes or 0)
+            bits = matting.SUBJECT_BITS
         refined = {}
         if getattr(self, "refine", None) is not None:
-            refined["alpha"] = matting.refine_alpha(crops_dev, labels_dev, self.foreground_bits, self.refine, self.refine_eps)
+            refined["alpha"] = matting.refine_alpha(crops_dev, labels_dev, bits, self.refine, self.refine_eps)
         if self.background_blur is not None:
-            return matting.matte_blur(crops_dev, labels_dev, self.foreground_bits, self.feather, self.blur_taps,
-                                      with_alpha=with_alpha, **refined)
-        return matting.matte(crops_dev, labels_dev, self.foreground_bits, self.feather, self.background,
-                             with_alpha=with_alpha, **refined)
+            return matting.matte_blur(crops_dev, labels_dev, bits, self.feather, self.blur_taps, with_alpha=with_alpha, **refined)
+        return matting.matte(crops_dev, labels_dev, bits, self.feather, self.background, with_alpha=with_alpha, **refined)
 
     def equalize(self, crops: np.ndarray) -> np.ndarray:
         """What ``clahe`` does, for crops one already has: (F,H,W,3) uint8 RGB -> the equalised crops (F,H,W,3) uint8,

@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -597,6 +597,26 @@ Tensor matte_blur_alpha(const Tensor& crops, const Tensor& labels, const Tensor&
   return out;
 }
 
+// The cleaned binary label map (f,h,w) uint8, 0 / 1, of label maps (f,h,w) uint8: the largest 8-connected component of
+// the hard mask and / or its holes of at most max_hole pixels filled (fcp_subject_mask_u8); the 12-bytes-per-pixel
+// workspace lives for the call.
+Tensor subject_mask(const Tensor& labels, int64_t class_bits, bool keep_largest, int64_t max_hole) {
+  dev(labels, "labels", at::kByte);
+  FCP_DEVICE_GUARD(labels);
+  TORCH_CHECK(labels.dim() == 3, "labels (f,h,w) uint8");
+  const int64_t f = labels.size(0), h = labels.size(1), w = labels.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "labels (f,h,w): sizes past int");
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  TORCH_CHECK(max_hole >= INT_MIN && max_hole <= INT_MAX, "max_hole past int");
+  Tensor out = at::empty_like(labels);
+  const int64_t need = fcp_subject_mask_workspace_bytes((int)f, (int)h, (int)w);
+  Tensor work = at::empty({need < 0 ? 0 : need}, labels.options());
+  ok(fcp_subject_mask_u8(labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits, keep_largest ? 1 : 0,
+                         (int)max_hole, out.data_ptr<uint8_t>(), work.data_ptr(), work.numel(), cur_stream()),
+     "fcp::subject_mask");
+  return out;
+}
+
 // Crops (f,h,w,3) uint8 with the luma equalised by CLAHE on a grid x grid tiling (fcp_clahe_u8); the LUT workspace
 // lives for the call.
 Tensor clahe(const Tensor& crops, int64_t grid, double clip_limit) {
@@ -683,6 +703,7 @@ TORCH_LIBRARY(fcp, m) {
   m.def("matte_refine(Tensor crops, Tensor labels, int class_bits, int radius, int eps) -> Tensor");
   m.def("matte_alpha(Tensor crops, Tensor alpha, int bg_r, int bg_g, int bg_b) -> Tensor");
   m.def("matte_blur_alpha(Tensor crops, Tensor labels, Tensor alpha, int class_bits, int[] taps) -> Tensor");
+  m.def("subject_mask(Tensor labels, int class_bits, bool keep_largest, int max_hole) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -716,6 +737,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("matte_refine", &matte_refine);
   m.impl("matte_alpha", &matte_alpha);
   m.impl("matte_blur_alpha", &matte_blur_alpha);
+  m.impl("subject_mask", &subject_mask);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

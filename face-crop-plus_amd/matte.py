@@ -15,6 +15,20 @@ are on the device already (``fcp_matte_u8`` / ``torch.ops.fcp.matte``).
 ``Cropper(refine=R)`` (section 2k) replaces the Gaussian feather by a guided filter of the hard mask, the gray of the
 crop as the guide (``refine_alpha``: ``fcp_matte_refine_u8`` / ``torch.ops.fcp.matte_refine``, two launches); ``matte``
 and ``matte_blur`` then composite through that plane (``alpha=``).
+
+``Cropper(subject="largest", fill_holes=N)`` (section 2l) cleans the hard mask before any of that (``subject_mask``:
+``fcp_subject_mask_u8`` / ``torch.ops.fcp.subject_mask``), every face on its own, H and W the crop's size:
+
+    m0(y,x) = 1 where labels(y,x) < 19 and bit labels(y,x) of class_bits is set, else 0
+    subject="largest": the 8-connected components of {m0 = 1}; a component's key is (its pixel count, then the SMALLER
+            raster index y*W + x of its first pixel in raster order); m1 = the component with the largest count, among
+            equal counts the one whose first pixel comes first; no foreground pixel: m1 = m0.  Otherwise m1 = m0.
+    fill_holes=N: the 4-connected components of {m1 = 0}; a hole is one that has no pixel in row 0, row H-1, column 0
+            or column W-1; m2 = m1, plus every hole of at most N pixels.  Otherwise m2 = m1.
+    out(y,x) = m2(y,x), one byte, 0 or 1
+
+The subject comes first, then the holes: an island inside a hole is background by then and counts in the hole's area.
+``out`` takes the label map's place downstream, with the class bit set ``SUBJECT_BITS`` (class 1).
 """
 from __future__ import annotations
 
@@ -35,6 +49,9 @@ MIN_RADIUS, MAX_RADIUS = 3, 48
 TAP_SUM = 4096
 MIN_REFINE, MAX_REFINE = 1, 16
 MIN_REFINE_EPS, MAX_REFINE_EPS, DEFAULT_REFINE_EPS = 1, 4096, 64
+SUBJECTS = ("largest",)
+MAX_FILL_HOLES = 8192 * 8192   # the largest crop the kernels take
+SUBJECT_BITS = 1 << 1          # the class bit set that reads ``subject_mask``'s 0 / 1 output as a label map: class 1
 
 
 def _is_int(v) -> bool:
@@ -111,6 +128,25 @@ def check_refine_eps(refine_eps) -> int:
     return int(refine_eps)
 
 
+def check_subject(subject):
+    """``subject`` of the Cropper -> None (off) or "largest"."""
+    if subject is None:
+        return None
+    if not isinstance(subject, str) or subject not in SUBJECTS:
+        raise ValueError(f"subject must be None or one of {SUBJECTS}, not {subject!r}")
+    return subject
+
+
+def check_fill_holes(fill_holes):
+    """``fill_holes`` of the Cropper -> None (off) or the largest hole that is filled, in output pixels: an int
+    1..67108864."""
+    if fill_holes is None:
+        return None
+    if not _is_int(fill_holes) or not 1 <= int(fill_holes) <= MAX_FILL_HOLES:
+        raise ValueError(f"fill_holes must be None or an int 1..{MAX_FILL_HOLES} (an area in pixels), not {fill_holes!r}")
+    return int(fill_holes)
+
+
 def blur_taps(sigma) -> list:
     """sigma -> the integer taps t[0..r] of the background blur, in float64: r = min(48, max(3, ceil(3 sigma))),
     g_k = exp(-k^2 / (2 sigma^2)), s = g_0 + 2 sum g_k, t_k = max(1, floor(4096 g_k / s)) for k >= 1 and t_0 the rest of
@@ -148,6 +184,23 @@ def refine_alpha(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: 
     N.check(N.lib().fcp_matte_refine_u8(N.ptr(crops_dev), N.ptr(labels_dev), f, h, w, int(class_bits), int(radius), int(eps),
                                         N.ptr(alpha), N.ptr(work), need, N.stream_ptr()), "fcp_matte_refine_u8")
     return alpha
+
+
+def subject_mask(labels_dev: torch.Tensor, class_bits: int, keep_largest: bool, max_hole: int) -> torch.Tensor:
+    """labels (F,H,W) u8, device -> out (F,H,W) u8 of 0 / 1, device: the hard mask of the labels, reduced to its largest
+    8-connected component where ``keep_largest``, then with its holes of at most ``max_hole`` pixels (0: none) filled, in
+    integers.  One launch for (False, 0), five for the subject, four for the holes, and a
+    workspace of 12 bytes per pixel that lives for the call; H, W <= 8192."""
+    assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and labels_dev.dim() == 3
+    if T.ENABLED:
+        return T.load().subject_mask(labels_dev, int(class_bits), bool(keep_largest), int(max_hole))
+    f, h, w = labels_dev.shape
+    out = torch.empty_like(labels_dev)
+    need = max(int(N.lib().fcp_subject_mask_workspace_bytes(f, h, w)), 0)
+    work = torch.empty((need,), dtype=torch.uint8, device=labels_dev.device)
+    N.check(N.lib().fcp_subject_mask_u8(N.ptr(labels_dev), f, h, w, int(class_bits), int(bool(keep_largest)), int(max_hole),
+                                        N.ptr(out), N.ptr(work), need, N.stream_ptr()), "fcp_subject_mask_u8")
+    return out
 
 
 def matte_blur(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, feather: int, taps, with_alpha: bool = False,

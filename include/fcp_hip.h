@@ -637,6 +637,42 @@ int fcp_matte_blur_alpha_u8(const uint8_t* crops, const uint8_t* labels, const u
                             uint32_t class_bits, const uint16_t* taps, int radius, uint8_t* out, void* workspace,
                             int64_t workspace_bytes, fcp_stream_t stream);
 
+/* One connected subject in a matte: connected-component
+ * labelling of the hard mask of label maps (f,h,w) uint8, every face on its
+ * own, in integers.  H = h, W = w:
+ *   m0(y,x) = 1 where labels(y,x) < 19 and bit labels(y,x) of class_bits is
+ *             set, else 0 (the hard mask of fcp_matte_u8; label bytes at or
+ *             above 19 are background, as there);
+ *   keep_largest = 1: the 8-connected components of {m0 = 1}; a component's
+ *             key is (its pixel count, then the SMALLER raster index y W + x
+ *             of its first pixel in raster order); m1 = the component with
+ *             the largest count, among equal counts the one whose first
+ *             pixel comes first; no foreground pixel: m1 = m0.
+ *             keep_largest = 0: m1 = m0;
+ *   max_hole = N > 0: the 4-connected components of {m1 = 0}; a hole is one
+ *             that has no pixel in row 0, row H - 1, column 0 or column
+ *             W - 1; m2 = m1, plus every hole of at most N pixels.
+ *             max_hole = 0: m2 = m1;
+ *   out(y,x) = m2(y,x), one byte, 0 or 1.
+ * The subject comes first, then the holes: an island that lay inside a hole
+ * is background by then and counts towards that hole's area.
+ * keep_largest = 0, max_hole = 0 is legal and writes m0.
+ * workspace: fcp_subject_mask_workspace_bytes(f,h,w) = 12 f h w bytes of
+ * device memory (three int32 planes), 16-byte aligned, contents irrelevant;
+ * it must not overlap the other arrays.  labels and out may start at any
+ * byte; nothing outside out and the workspace is written.  1 launch for
+ * (0, 0), 5 for the subject, 4 for the holes, 9 for both, on `stream`;
+ * nothing allocated, no float; the atomics are integer min / add / or whose
+ * result does not depend on their order: the same bytes from run to run.
+ * f == 0 is a no-op; f < 0, h or w < 1 or > 8192, f > 65535, a bit of
+ * class_bits at or above 19, a keep_largest outside {0, 1}, a max_hole
+ * outside 0..67108864, or (f > 0) a null labels / out, a workspace that is
+ * null, too small or misaligned fail with a "subject_mask:" message, before
+ * any HIP call (fcp_subject_mask_workspace_bytes then returns -1). */
+int64_t fcp_subject_mask_workspace_bytes(int f, int h, int w);
+int fcp_subject_mask_u8(const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int keep_largest, int max_hole, uint8_t* out,
+                        void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
+
 /* Contrast-limited adaptive histogram equalisation of the luma of crops
  * (f,h,w,3) uint8 RGB: cv2.createCLAHE(clip_limit,
  * (grid, grid)).apply(Y) between cv2.cvtColor(COLOR_RGB2YCrCb) and
