@@ -50,6 +50,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-enc", "--encoder", type=str, default=argparse.SUPPRESS, choices=("host", "device"),
                    help="where output files are compressed: 'host' (default, Pillow on the I/O pool) or 'device' (JPEG "
                         "files of aligned crops and masks are encoded on the GPU, byte for byte the same files)")
+    p.add_argument("-penc", "--png-encoder", type=str, default=argparse.SUPPRESS, choices=("host", "device"),
+                   help="where PNG files are compressed: 'host' (default, Pillow on the I/O pool) or 'device' (PNG files of "
+                        "aligned crops and masks are filtered and deflated on the GPU: the same pixels, not the same bytes)")
     p.add_argument("-bg", "--background", type=_background, default=argparse.SUPPRESS,
                    help="replace the background of the crops with a uniform fill: 'R,G,B' or a single gray level, each "
                         "0..255; by default the crops keep their background")

@@ -91,6 +91,8 @@ SIGNATURES = {
     "fcp_jpeg_encode_u8": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _P, _P, _L, _P],
     "fcp_jpeg_encode_ex_u8": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _L, _P, _P, _P, _L, _P],
     "fcp_jpeg_huffman_tables": [_P, _I, _P, _P, _P],
+    "fcp_png_encode_u8": [_P, _I, _I, _I, _I, _P, _L, _L, _P, _P, _L, _P],
+    "fcp_png_huffman_lengths": [_P, _I, _P, _P, _P],
     "fcp_matte_u8": [_P, _P, _I, _I, _I, C.c_uint32, _I, _I, _I, _I, _P, _P, _P],
     "fcp_clahe_u8": [_P, _I, _I, _I, _I, C.c_double, _P, _P, _P],
     "fcp_matte_blur_u8": [_P, _P, _I, _I, _I, C.c_uint32, _I, _P, _I, _P, _P, _P, _L, _P],
@@ -101,7 +103,7 @@ SIGNATURES = {
 }
 EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes", "fcp_jpeg_workspace_bytes",
            "fcp_jpeg_workspace_bytes_ex", "fcp_matte_blur_workspace_bytes", "fcp_matte_refine_workspace_bytes",
-           "fcp_subject_mask_workspace_bytes"] + list(SIGNATURES)
+           "fcp_subject_mask_workspace_bytes", "fcp_png_workspace_bytes"] + list(SIGNATURES)
 
 
 def lib():
@@ -124,6 +126,8 @@ def lib():
     l.fcp_jpeg_workspace_bytes.restype = C.c_int64
     l.fcp_jpeg_workspace_bytes_ex.argtypes = [C.c_int] * 6
     l.fcp_jpeg_workspace_bytes_ex.restype = C.c_int64
+    l.fcp_png_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    l.fcp_png_workspace_bytes.restype = C.c_int64
     l.fcp_matte_blur_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     l.fcp_matte_blur_workspace_bytes.restype = C.c_int64
     l.fcp_matte_refine_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]

@@ -56,6 +56,7 @@ class Cropper:
         warp_family: str | None = None,
         crop_source: str = "batch",
         encoder: str = "host",
+        png_encoder: str = "host",
         jpeg_quality: int = 95,
         jpeg_subsampling: str = "4:2:0",
         jpeg_optimize: bool = False,
@@ -98,6 +99,13 @@ class Cropper:
         same files byte for byte — so that the lengths and the compressed streams come back instead of the pixels and the
         I/O pool only writes.  Every other file (other formats, the images of "no alignment", a crop whose stream
         outgrows its slot) is encoded on the host as before.
+        ``png_encoder``: the same choice for the PNG files (.png) of aligned crops and parse masks, independent of
+        ``encoder``: "device" filters and deflates them on the GPU (``pngenc.encode_png``), so
+        that the lengths and the zlib streams come back instead of the pixels.  The files decode to exactly the pixels
+        the host's files decode to, but they are NOT the host's bytes (a deflate stream has many valid encodings; this one
+        is mostly smaller than zlib's level 1, which the host writes).  The images of "no alignment", a face whose
+        stream outgrows its slot and faces larger than the kernels take keep the host encoder.  "host" (the default)
+        changes nothing.  ``Cropper.encode_png`` applies it to crops one already has.
         ``background``: replace what is behind the subject — an int 0..255 (gray) or three of them (R, G, B) fills every
         pixel the face parser does not label as one of the ``foreground`` classes (BiSeNet indices; None: every class but
         0), through a soft edge of ``feather`` pixels (0, 3, 5 or 7; None: 5): the Gaussian of that size over the hard
@@ -158,6 +166,9 @@ class Cropper:
         if encoder not in ("host", "device"):
             raise ValueError(f"unknown encoder {encoder!r}: choose 'host' or 'device'")
         self.encoder = encoder
+        if png_encoder not in ("host", "device"):
+            raise ValueError(f"unknown png_encoder {png_encoder!r}: choose 'host' or 'device'")
+        self.png_encoder = png_encoder
         self.jpeg = check_jpeg_settings(jpeg_quality, jpeg_subsampling, jpeg_optimize)
         self.jpeg_quality, self.jpeg_subsampling, self.jpeg_optimize = self.jpeg
         explicit_family = warp_family if warp_family is not None else (os.environ.get("FCP_WARP_FAMILY") or None)
@@ -306,7 +317,7 @@ class Cropper:
             from .bise import BiSeNet
             self.par_model = BiSeNet(self.attr_groups, self.mask_groups, self.batch_size)
             self.par_model.load(self.device, self.weights.get("bisenet"), self.precision)
-            self.par_model.masks_on_device = self.encoder == "device"
+            self.par_model.masks_on_device = self._encodes_on_device()
 
     def _init_landmarks_target(self):
         if self.num_std_landmarks != 5:
@@ -433,6 +444,22 @@ class Cropper:
         with torch.cuda.device(self.device):
             return jpegenc.encode_jpeg(torch.from_numpy(crops).to(self.device), **self._jpeg_kw())
 
+    def encode_png(self, crops: np.ndarray) -> list:
+        """What ``png_encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F PNG files as
+        bytes, each of which decodes to those pixels (``pngenc.encode_png``); not the host encoder's bytes."""
+        from . import pngenc
+        crops = np.ascontiguousarray(crops)
+        if crops.dtype != np.uint8 or not (crops.ndim == 3 or (crops.ndim == 4 and crops.shape[3] == 3)):
+            raise ValueError(f"crops must be (F,H,W,3) or (F,H,W) uint8, not {crops.dtype} {crops.shape}")
+        if crops.shape[0] == 0:
+            return []
+        with torch.cuda.device(self.device):
+            return pngenc.encode_png(torch.from_numpy(crops).to(self.device))
+
+    def _encodes_on_device(self) -> bool:
+        """Whether some format is compressed on the GPU: then crops and masks stay there until they are saved."""
+        return self.encoder == "device" or getattr(self, "png_encoder", "host") == "device"
+
     def _jpeg_kw(self) -> dict:
         """Keywords of ``jpegenc.encode_jpeg`` for this Cropper's settings; none at all for the defaults."""
         jpeg = getattr(self, "jpeg", None)
@@ -531,21 +558,34 @@ class Cropper:
             return np.full(len(file_names), ("." + self.output_format).lower() in JPEG_EXTENSIONS)
         return np.array([os.path.splitext(str(n))[1].lower() in JPEG_EXTENSIONS for n in file_names], bool)
 
+    def _is_png_target(self, file_names):
+        """Per source file name: whether the face cut from it is written as a PNG (``_target_paths``' extension rule)."""
+        from .pngenc import PNG_EXTENSIONS
+        if self.output_format is not None:
+            return np.full(len(file_names), ("." + self.output_format).lower() in PNG_EXTENSIONS)
+        return np.array([os.path.splitext(str(n))[1].lower() in PNG_EXTENSIONS for n in file_names], bool)
+
     def _encode_on_device(self, pixels_dev, pixels, names):
-        """``encoder="device"``: (F,H,W[,3]) u8 device pixels (and their host copy, if one exists already) of the faces
-        or masks cut from ``names`` -> a list with the JPEG file (bytes) of every face that becomes one and the host
-        pixels of every other.  The pixels are read back only when some target is not a JPEG."""
-        from . import jpegenc
-        jpeg = self._is_jpeg_target(names)
+        """``encoder="device"`` / ``png_encoder="device"``: (F,H,W[,3]) u8 device pixels (and their host copy, if one
+        exists already) of the faces or masks cut from ``names`` -> a list with the encoded file (bytes) of every face
+        whose format is compressed on the GPU — JPEG targets by ``encoder``, PNG targets by ``png_encoder`` — and the
+        host pixels of every other.  The pixels are read back only when some target needs the host."""
+        from . import jpegenc, pngenc
+        none = np.zeros(len(names), bool)
+        jpeg = self._is_jpeg_target(names) if self.encoder == "device" else none
+        png = self._is_png_target(names) if getattr(self, "png_encoder", "host") == "device" else none
         out = [None] * len(names)
-        if jpeg.any():
-            with trace.range("fcp:jpeg"):
-                rows = pixels_dev if jpeg.all() else pixels_dev[torch.from_numpy(jpeg).to(pixels_dev.device)].contiguous()
-                for i, data in zip(np.nonzero(jpeg)[0], jpegenc.encode_jpeg(rows, **self._jpeg_kw())):
-                    out[i] = data
-        if not jpeg.all():
+        for which, label, encode in ((jpeg, "fcp:jpeg", lambda rows: jpegenc.encode_jpeg(rows, **self._jpeg_kw())),
+                                     (png, "fcp:png", pngenc.encode_png)):
+            if which.any():
+                with trace.range(label):
+                    rows = pixels_dev if which.all() else pixels_dev[torch.from_numpy(which).to(pixels_dev.device)].contiguous()
+                    for i, data in zip(np.nonzero(which)[0], encode(rows)):
+                        out[i] = data
+        on_host = ~(jpeg | png)
+        if on_host.any():
             host = pixels if pixels is not None else pixels_dev.cpu().numpy()
-            for i in np.nonzero(~jpeg)[0]:
+            for i in np.nonzero(on_host)[0]:
                 out[i] = host[i]
         return out
 
@@ -630,8 +670,8 @@ class Cropper:
                     keep = ok.cpu().numpy() != 0
                     crops_dev = crops_dev[torch.from_numpy(keep).to(self.device)]
                     indices = [i for i, k in zip(indices, keep) if k]
-                    # encoder="device": the pixels stay where they are; what is read back is decided when they are saved
-                    faces_dev, faces = crops_dev, (None if self.encoder == "device" else crops_dev.cpu().numpy())
+                    # a device encoder: the pixels stay where they are; what is read back is decided when they are saved
+                    faces_dev, faces = crops_dev, (None if self._encodes_on_device() else crops_dev.cpu().numpy())
                 elif images_dev is not None:
                     with trace.range("fcp:align"):
                         crops_dev, ok = self._crop_align_device(
@@ -640,8 +680,8 @@ class Cropper:
                     keep = ok.cpu().numpy() != 0
                     crops_dev = crops_dev[torch.from_numpy(keep).to(self.device)]
                     indices = [i for i, k in zip(indices, keep) if k]
-                    # encoder="device": the pixels stay where they are; what is read back is decided when they are saved
-                    faces_dev, faces = crops_dev, (None if self.encoder == "device" else crops_dev.cpu().numpy())
+                    # a device encoder: the pixels stay where they are; what is read back is decided when they are saved
+                    faces_dev, faces = crops_dev, (None if self._encodes_on_device() else crops_dev.cpu().numpy())
                 else:
                     with trace.range("fcp:align"):
                         faces = self.crop_align(images, paddings, indices, landmarks)
@@ -679,10 +719,10 @@ class Cropper:
                     with trace.range("fcp:matte"):
                         faces_dev, _ = self._matte_device(faces_dev, labels)
                 # the host copy, if the host encoder needs one, is the equalised / matted crop as well
-                faces = None if self.encoder == "device" else faces_dev.cpu().numpy()
-            if self.encoder == "device" and isinstance(faces_dev, torch.Tensor):
+                faces = None if self._encodes_on_device() else faces_dev.cpu().numpy()
+            if self._encodes_on_device() and isinstance(faces_dev, torch.Tensor):
                 # aligned crops (and their masks): same size, on the device.  Faces and mask rows become lists that hold
-                # the encoded file of every JPEG target, in the order save_groups indexes them
+                # the encoded file of every target a device encoder takes, in the order save_groups indexes them
                 names = file_names[indices]
                 faces = self._encode_on_device(faces_dev, faces, names) if len(indices) > 0 else []
                 if groups[1] is not None:

@@ -27,6 +27,7 @@
 // run the 4:2:0 instances.  An MCU that overhangs an odd Y block grid carries dummy blocks: all AC zero and the DC of the
 // block before them, i.e. a zero DC difference and an end-of-block, and the DC prediction passes through them unchanged.
 // They are never transformed.
+#include "fcp_block_scan.h"
 #include "fcp_common.h"
 #include "fcp_hip.h"
 
@@ -363,27 +364,6 @@ __device__ __forceinline__ void load_tables(const HuffArg& hf, const uint32_t* f
   __syncthreads();
 }
 
-// Exclusive scan of one value per lane over the workgroup; *total (same for every lane) is the sum.
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wave_sums, uint32_t* total) {
-  uint32_t incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t up = __shfl_up(incl, off, 64);
-    if ((threadIdx.x & 63) >= off) incl += up;
-  }
-  __syncthreads();                                             // wave_sums may still be read from the round before
-  if ((threadIdx.x & 63) == 63) wave_sums[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < kThreads / 64; ++k) {
-    if (k < (int)(threadIdx.x >> 6)) before += wave_sums[k];
-    all += wave_sums[k];
-  }
-  *total = all;
-  return before + incl - v;
-}
-
 template <int SS>
 __global__ void __launch_bounds__(kThreads) jpeg_count_scan_kernel(const int16_t* __restrict__ coefs, Geometry g, HuffArg hf,
                                                                    const uint32_t* __restrict__ codes,
@@ -400,7 +380,7 @@ __global__ void __launch_bounds__(kThreads) jpeg_count_scan_kernel(const int16_t
     sink.t = &tabs;
     if (b < g.nblk) code_block<SS>(g, face_coefs, b, sink);
     uint32_t total;
-    const uint32_t excl = block_exclusive_scan(sink.bits, wave_sums, &total);
+    const uint32_t excl = fcp_block_exclusive_scan<kThreads>(sink.bits, wave_sums, &total);
     if (b < g.nblk) off[b] = carry + excl;
     carry += total;
   }
@@ -607,7 +587,7 @@ __global__ void __launch_bounds__(kThreads) jpeg_stuff_kernel(const uint32_t* __
     for (int j = 0; j < 16; ++j)
       ffs += (first + j < nbytes && ((words[j >> 2] >> (24 - 8 * (j & 3))) & 255u) == 255u) ? 1u : 0u;
     uint32_t total;
-    const uint32_t excl = block_exclusive_scan(ffs, wave_sums, &total);
+    const uint32_t excl = fcp_block_exclusive_scan<kThreads>(ffs, wave_sums, &total);
     long long p = (long long)first + carry + excl;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {

@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -469,6 +469,49 @@ std::tuple<Tensor, Tensor> jpeg_huffman_tables(const Tensor& freq, bool with_cod
   return {tables, codes};
 }
 
+// zlib streams for PNG files of faces (f,h,w,3) or (f,h,w) uint8 into the rows of `out` (f, capacity) uint8 — rows may
+// be a view of a wider buffer (unit stride inside a row) — and the true lengths (f,) int32, which may exceed the capacity
+// (fcp_png_encode_u8; the file around a stream is written on the host).  The workspace comes from the caching allocator.
+Tensor png_encode(const Tensor& pixels, const Tensor& out) {
+  dev(pixels, "pixels", at::kByte);
+  FCP_DEVICE_GUARD(pixels);
+  TORCH_CHECK((pixels.dim() == 4 && (pixels.size(3) == 3 || pixels.size(3) == 1)) || pixels.dim() == 3,
+              "pixels (f,h,w,3) or (f,h,w) uint8");
+  const int64_t f = pixels.size(0), h = pixels.size(1), w = pixels.size(2), c = pixels.dim() == 4 ? pixels.size(3) : 1;
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "pixels: sizes past int");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kByte && out.get_device() == pixels.get_device(),
+              "out must be a uint8 tensor on the device of the pixels");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == f, "out must be (", f, ", capacity)");
+  const int64_t capacity = out.size(1), stride = f > 1 ? out.stride(0) : capacity;
+  TORCH_CHECK(capacity == 0 || out.stride(1) == 1, "out: the bytes of a row must be contiguous");
+  TORCH_CHECK(stride >= capacity, "out: rows overlap");
+  Tensor lengths = at::empty({f}, pixels.options().dtype(at::kInt));
+  const int64_t need = fcp_png_workspace_bytes((int)f, (int)h, (int)w, (int)c);
+  ok(need < 0 ? -1 : 0, "fcp::png_encode");
+  Tensor work = at::empty({need}, pixels.options());
+  ok(fcp_png_encode_u8(pixels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (int)c,
+                       capacity > 0 ? out.data_ptr<uint8_t>() : nullptr, stride, capacity, lengths.data_ptr<int32_t>(),
+                       work.data_ptr(), need, cur_stream()),
+     "fcp::png_encode");
+  return lengths;
+}
+
+// Rows of 286 literal/length counts (n,286) int32 -> their deflate code lengths (n,286) uint8 and, with `with_codes`,
+// bit-reversed code | length << 16 by symbol (n,286) int32 (else an empty tensor) (fcp_png_huffman_lengths).
+std::tuple<Tensor, Tensor> png_huffman_lengths(const Tensor& freq, bool with_codes) {
+  dev(freq, "freq", at::kInt);
+  FCP_DEVICE_GUARD(freq);
+  TORCH_CHECK(freq.dim() == 2 && freq.size(1) == 286 && freq.is_contiguous(), "freq (n,286) int32, contiguous");
+  const int64_t n = freq.size(0);
+  TORCH_CHECK(n <= INT_MAX, "freq: rows past int");
+  Tensor lengths = at::empty({n, 286}, freq.options().dtype(at::kByte));
+  Tensor codes = with_codes ? at::empty({n, 286}, freq.options()) : at::empty({0}, freq.options());
+  ok(fcp_png_huffman_lengths(reinterpret_cast<const uint32_t*>(freq.data_ptr<int32_t>()), (int)n, lengths.data_ptr<uint8_t>(),
+                             with_codes ? reinterpret_cast<uint32_t*>(codes.data_ptr<int32_t>()) : nullptr, cur_stream()),
+     "fcp::png_huffman_lengths");
+  return {lengths, codes};
+}
+
 // Crops (f,h,w,3) uint8 over a uniform fill through the soft mask of their label maps (f,h,w) uint8: the composited
 // crops and, with `with_alpha`, the alpha (f,h,w) uint8 (else an empty tensor) (fcp_matte_u8).
 std::tuple<Tensor, Tensor> matte(const Tensor& crops, const Tensor& labels, int64_t class_bits, int64_t feather, int64_t bg_r,
@@ -696,6 +739,8 @@ TORCH_LIBRARY(fcp, m) {
   m.def("jpeg_encode(Tensor crops, int quality, int subsampling, Tensor(a!) out) -> Tensor");
   m.def("jpeg_encode_ex(Tensor crops, int quality, int subsampling, Tensor(a!) out, Tensor(b!)? tables) -> Tensor");
   m.def("jpeg_huffman_tables(Tensor freq, bool with_codes) -> (Tensor, Tensor)");
+  m.def("png_encode(Tensor pixels, Tensor(a!) out) -> Tensor");
+  m.def("png_huffman_lengths(Tensor freq, bool with_codes) -> (Tensor, Tensor)");
   m.def("matte(Tensor crops, Tensor labels, int class_bits, int feather, int bg_r, int bg_g, int bg_b, bool with_alpha) "
         "-> (Tensor, Tensor)");
   m.def("clahe(Tensor crops, int grid, float clip_limit) -> Tensor");
@@ -731,6 +776,8 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("jpeg_encode", &jpeg_encode);
   m.impl("jpeg_encode_ex", &jpeg_encode_ex);
   m.impl("jpeg_huffman_tables", &jpeg_huffman_tables);
+  m.impl("png_encode", &png_encode);
+  m.impl("png_huffman_lengths", &png_huffman_lengths);
   m.impl("matte", &matte);
   m.impl("clahe", &clahe);
   m.impl("matte_blur", &matte_blur);

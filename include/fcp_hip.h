@@ -530,6 +530,61 @@ int fcp_jpeg_encode_ex_u8(const uint8_t* crops, int f, int h, int w, int channel
  * a misaligned freq / codes fail with a message, before any HIP call. */
 int fcp_jpeg_huffman_tables(const uint32_t* freq, int n, uint8_t* tables, uint32_t* codes, fcp_stream_t stream);
 
+/* zlib streams for PNG files of faces (f,h,w,channels) uint8, channels 3 (RGB)
+ * or 1 (gray), on the device (where the stream is defined;
+ * tests/png_ref.py states it in Python): face i's stream, 78 01, one dynamic
+ * Huffman block, Adler-32, goes to out + i * out_stride; the host wraps it
+ * into a file (pngenc.png_file).  Every scanline takes the PNG filter 0..4
+ * with the smallest sum of min(v, 256 - v) over its filtered bytes (the
+ * lowest type among equals); per filtered row, type byte included, a maximal
+ * run of n equal bytes is n literals when n < 4, else one literal and matches
+ * at distance 1 over the other n - 1 bytes (258 while at least 3 stay behind,
+ * else all but 3, then the rest); the literal/length code is that of
+ * fcp_png_huffman_lengths over the token counts with the end-of-block symbol
+ * counted once; there is one distance code (code 0, length 1) and a fixed
+ * code-length code.  The streams inflate to the filtered rows, i.e. the files
+ * decode to exactly the pixels; they are NOT the bytes zlib would write.
+ * lengths[i] is the TRUE length of the stream even when it exceeds capacity;
+ * then only its first capacity bytes are written and the caller encodes the
+ * face some other way.  Nothing is written at or past out + i * out_stride +
+ * capacity, every byte below min(lengths[i], capacity) is written (out need
+ * not be zeroed).  h * (w * channels + 1) + 1024 bytes hold any stream whose
+ * codes average 9 bits or less; 15 bits a byte plus 270 bytes always do.
+ * workspace: fcp_png_workspace_bytes(f,h,w,channels) bytes of device memory,
+ * 16-byte aligned, contents irrelevant (per filtered byte 4 bytes of run list
+ * and 15 bits of stream; per row 24 + 4 bytes; per face 2.5 KiB).
+ * One memset and six launches; no host round trip, one stream, nothing
+ * allocated, the same bytes from run to run.  f == 0 is a no-op.  Refused with
+ * a message, before any HIP call: h, w < 1 or > 8192, f < 0 or > 65535,
+ * channels other than 1 / 3, capacity < 0 or > out_stride, a null pointer, a
+ * workspace too small or not 16-byte aligned, and a face with
+ * h * (w * channels + 1) + 1 >= 9 227 464 (one below the 35th Fibonacci
+ * number: below it no Huffman tree is deeper than 32, the range of the
+ * lengths before the limit; about 1750 x 1750 RGB).  fcp_png_workspace_bytes
+ * then returns -1. */
+int64_t fcp_png_workspace_bytes(int f, int h, int w, int channels);
+int fcp_png_encode_u8(const uint8_t* pixels, int f, int h, int w, int channels,
+                      uint8_t* out, int64_t out_stride, int64_t capacity, int32_t* lengths,
+                      void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
+
+/* Deflate code lengths of n rows of 286 literal/length frequencies (device
+ * memory, 4-byte aligned), one wave per row: the merge of
+ * fcp_jpeg_huffman_tables without its pseudo-symbol (while two non-zero
+ * entries are left: c1 the smallest non-zero frequency, the LARGEST index
+ * among equals, c2 the same search without c1; freq[c1] += freq[c2],
+ * freq[c2] = 0, every symbol under c1 and c2 grows by one bit); the same
+ * bits[] adjustment, down to 15 bits; the limited lengths go to the symbols in
+ * order of (length before the limit, symbol).  lengths (n,286) uint8.  codes
+ * (n,286), or NULL: bit-reversed canonical code (RFC 1951 3.2.2) | length << 16
+ * by symbol, 0 for a symbol without a code.  A row with fewer than two
+ * non-zero entries has no tree: all of its lengths are 0.
+ * Precondition: a row sums to less than 2^32 (no tree over such counts is
+ * deeper than 44; the lengths before the limit may reach 48); beyond it the
+ * lengths mean nothing, but nothing outside lengths and codes is written.
+ * One launch.  n == 0 is a no-op; n < 0 or > 65535, a null freq / lengths or a
+ * misaligned freq / codes fail with a message, before any HIP call. */
+int fcp_png_huffman_lengths(const uint32_t* freq, int n, uint8_t* lengths, uint32_t* codes, fcp_stream_t stream);
+
 /* Background replacement of crops (f,h,w,3) uint8 RGB from label maps
  * (f,h,w) uint8, in integers throughout:
  *   m     = 255 where the label is below 32 and that bit of class_bits is
