@@ -55,7 +55,8 @@ def build_parser() -> argparse.ArgumentParser:
                         "aligned crops and masks are filtered and deflated on the GPU: the same pixels, not the same bytes)")
     p.add_argument("-bg", "--background", type=_background, default=argparse.SUPPRESS,
                    help="replace the background of the crops with a uniform fill: 'R,G,B' or a single gray level, each "
-                        "0..255; by default the crops keep their background")
+                        "0..255; or 'transparent': RGBA cut-outs with the matte as their alpha channel (needs "
+                        "--output-format png); by default the crops keep their background")
     p.add_argument("-fg", "--foreground", type=json.loads, default=argparse.SUPPRESS,
                    help="JSON list of the face parser's class indices that count as the subject (with --background; default "
                         "every class but 0)")
@@ -79,6 +80,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="fill the matte's pinholes: the largest enclosed background region, in output pixels "
                         "(1..67108864), that becomes foreground (with --background or --background-blur); by default holes "
                         "stay")
+    p.add_argument("-dc", "--decontaminate", type=float, default=argparse.SUPPRESS,
+                   help="give the soft edge of the matte the subject's own colour in place of its mix with the old "
+                        "background: sigma in output pixels, 0.5..16, about the width of the soft edge or more (with "
+                        "--background, fill or 'transparent'); by default the edge keeps the crop's colour")
     p.add_argument("-cl", "--clahe", type=float, default=argparse.SUPPRESS,
                    help="equalise the contrast of the crops: clip limit (> 0, usually 2.0) of a contrast-limited adaptive "
                         "histogram equalisation of their luma; by default the crops keep their contrast")
@@ -95,7 +100,9 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def _background(text: str):
-    """'R,G,B' -> [R, G, B], 'V' -> V."""
+    """'R,G,B' -> [R, G, B], 'V' -> V, 'transparent' -> itself."""
+    if text == "transparent":
+        return text
     parts = [int(v) for v in text.split(",")]
     return parts[0] if len(parts) == 1 else parts
 

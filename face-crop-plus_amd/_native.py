@@ -100,10 +100,12 @@ SIGNATURES = {
     "fcp_matte_alpha_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "fcp_matte_blur_alpha_u8": [_P, _P, _P, _I, _I, _I, C.c_uint32, _P, _I, _P, _P, _L, _P],
     "fcp_subject_mask_u8": [_P, _I, _I, _I, C.c_uint32, _I, _I, _P, _P, _L, _P],
+    "fcp_feather_alpha_u8": [_P, _I, _I, _I, C.c_uint32, _I, _P, _P],
+    "fcp_cutout_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _L, _P],
 }
 EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes", "fcp_jpeg_workspace_bytes",
            "fcp_jpeg_workspace_bytes_ex", "fcp_matte_blur_workspace_bytes", "fcp_matte_refine_workspace_bytes",
-           "fcp_subject_mask_workspace_bytes", "fcp_png_workspace_bytes"] + list(SIGNATURES)
+           "fcp_subject_mask_workspace_bytes", "fcp_png_workspace_bytes", "fcp_cutout_workspace_bytes"] + list(SIGNATURES)
 
 
 def lib():
@@ -134,6 +136,8 @@ def lib():
     l.fcp_matte_refine_workspace_bytes.restype = C.c_int64
     l.fcp_subject_mask_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     l.fcp_subject_mask_workspace_bytes.restype = C.c_int64
+    l.fcp_cutout_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    l.fcp_cutout_workspace_bytes.restype = C.c_int64
     for name, args in SIGNATURES.items():
         fn = getattr(l, name)
         fn.argtypes = args

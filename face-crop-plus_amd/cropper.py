@@ -60,7 +60,7 @@ class Cropper:
         jpeg_quality: int = 95,
         jpeg_subsampling: str = "4:2:0",
         jpeg_optimize: bool = False,
-        background: int | tuple[int, int, int] | list[int] | None = None,
+        background: int | tuple[int, int, int] | list[int] | str | None = None,
         foreground: list[int] | None = None,
         feather: int | None = None,
         background_blur: float | None = None,
@@ -68,6 +68,7 @@ class Cropper:
         refine_eps: int | None = None,
         subject: str | None = None,
         fill_holes: int | None = None,
+        decontaminate: float | None = None,
         clahe: float | None = None,
         clahe_grid: int | None = None,
         interpolation: str = "linear",
@@ -147,6 +148,24 @@ class Cropper:
         feather, the guided filter, the composite and the blur's background sums.  They need ``background`` or
         ``background_blur`` (ValueError); mask files are untouched and a face without a foreground pixel behaves as
         before.  None (the default) launches nothing.
+        ``background="transparent"``: write RGBA cut-outs — no fill at all: every crop becomes ``(colour, alpha)`` with the
+        matte as its alpha channel and ``(0, 0, 0, 0)`` wherever the alpha is 0, so that nothing of the old background ships
+        in the file (``matte.cutout``).  It is a background mode like the fill: it creates the
+        parser, needs aligned crops, ``foreground`` / ``feather`` / ``refine`` / ``subject`` / ``fill_holes`` apply, it
+        excludes ``background_blur`` and mask files are unchanged.  Only PNG keeps an alpha channel among the formats
+        written here, so it requires ``output_format="png"`` (any letter case; ValueError otherwise, at construction);
+        the files are colour type 6, through either ``png_encoder``.
+        ``decontaminate``: give the soft edge the subject's own colour — the sigma, in output pixels (0.5..16), of the
+        "blur fusion" estimate.  In the soft edge the crop's colour is already ``alpha F + (1 - alpha) B_old``: shipping it
+        beside the alpha, or compositing it over a new fill, carries the old background along as a halo.  The estimate is
+        two mask-normalised Gaussians of that sigma, one over the pixels whose alpha is exactly 255 (certainly subject)
+        and one over those whose alpha is exactly 0 (certainly background), and one integer correction that makes
+        ``alpha F + (1 - alpha) B`` meet the crop again; where the window holds no pixel of a kind the crop's colour
+        stands in for it.  Pixels with alpha 255 keep the crop's colour.  A useful sigma is about the width of the soft
+        edge or more: below it the windows do not reach the certain pixels on both sides.  It works with
+        ``background="transparent"`` and with a fill ``background=(R, G, B)`` (``matte.cutout``); with
+        ``background_blur`` or without a background it raises ValueError.  None (the default) launches nothing new: a
+        fill composites the crop's colour, byte for byte as before.
         ``clahe``: equalise the contrast of every crop — the clip limit (finite, > 0; 2.0 is the usual value) of a
         contrast-limited adaptive histogram equalisation of the luma on a ``clahe_grid`` x ``clahe_grid`` tiling (1..16;
         None: 8), ``cv2.createCLAHE(clahe, (grid, grid)).apply(Y)`` between ``cv2.cvtColor(crop, COLOR_RGB2YCrCb)`` and
@@ -193,6 +212,15 @@ class Cropper:
         if self.background is not None and self.background_blur is not None:
             raise ValueError("background and background_blur exclude each other: the background is filled or blurred")
         self.blur_taps = None if self.background_blur is None else matting.blur_taps(self.background_blur)
+        if self.background == matting.TRANSPARENT and (not isinstance(output_format, str) or output_format.lower() != "png"):
+            raise ValueError(f"background='transparent' needs output_format='png', the one format written here that keeps an "
+                             f"alpha channel, not {output_format!r}")
+        self.decontaminate = matting.check_decontaminate(decontaminate)
+        if self.decontaminate is not None and self.background_blur is not None:
+            raise ValueError("decontaminate and background_blur exclude each other: the blurred background keeps the crop's colours")
+        if self.decontaminate is not None and self.background is None:
+            raise ValueError("decontaminate needs background (a fill or 'transparent'): without one it would do nothing")
+        self.decontaminate_taps = None if self.decontaminate is None else matting.blur_taps(self.decontaminate)
         self.refine = matting.check_refine(refine)
         if self.refine is None:
             if refine_eps is not None:
@@ -389,7 +417,8 @@ class Cropper:
         ``background`` / ``foreground`` / ``feather`` (``matte.matte``), or with its ``background_blur``
         (``matte.matte_blur``); with ``refine`` the alpha is the guided filter's (``matte.refine_alpha``) and the
         composite goes through it; with ``subject`` / ``fill_holes`` the mask is cleaned first (``matte.subject_mask``).
-        The alpha is what an RGBA file needs."""
+        With ``background="transparent"`` the first array is the RGBA cut-out (F,H,W,4) itself; with ``decontaminate`` its
+        colours, or those composited over the fill, are the estimated subject colours (``matte.cutout``)."""
         if self.background is None and self.background_blur is None:
             raise ValueError("Cropper.matte needs a Cropper with background=... or background_blur=...")
         crops, labels = np.ascontiguousarray(crops), np.ascontiguousarray(labels)
@@ -417,6 +446,13 @@ class Cropper:
             refined["alpha"] = matting.refine_alpha(crops_dev, labels_dev, bits, self.refine, self.refine_eps)
         if self.background_blur is not None:
             return matting.matte_blur(crops_dev, labels_dev, bits, self.feather, self.blur_taps, with_alpha=with_alpha, **refined)
+        transparent = self.background == matting.TRANSPARENT
+        taps = getattr(self, "decontaminate_taps", None)       # absent on a Cropper made with __new__, like refine above
+        if transparent or taps is not None:
+            # the cut-out and the decontaminated composite read an alpha plane: the refined one, or the feathered mask
+            alpha = refined["alpha"] if refined else matting.feather_alpha(labels_dev, bits, self.feather)
+            out = matting.cutout(crops_dev, alpha, None if transparent else self.background, taps)
+            return out, (alpha if with_alpha else None)
         return matting.matte(crops_dev, labels_dev, bits, self.feather, self.background, with_alpha=with_alpha, **refined)
 
     def equalize(self, crops: np.ndarray) -> np.ndarray:
@@ -445,12 +481,13 @@ class Cropper:
             return jpegenc.encode_jpeg(torch.from_numpy(crops).to(self.device), **self._jpeg_kw())
 
     def encode_png(self, crops: np.ndarray) -> list:
-        """What ``png_encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F PNG files as
-        bytes, each of which decodes to those pixels (``pngenc.encode_png``); not the host encoder's bytes."""
+        """What ``png_encoder="device"`` writes, for crops one already has: (F,H,W,3), (F,H,W,4) (RGBA cut-outs) or
+        (F,H,W) uint8 -> F PNG files as bytes, each of which decodes to those pixels (``pngenc.encode_png``); not the host
+        encoder's bytes."""
         from . import pngenc
         crops = np.ascontiguousarray(crops)
-        if crops.dtype != np.uint8 or not (crops.ndim == 3 or (crops.ndim == 4 and crops.shape[3] == 3)):
-            raise ValueError(f"crops must be (F,H,W,3) or (F,H,W) uint8, not {crops.dtype} {crops.shape}")
+        if crops.dtype != np.uint8 or not (crops.ndim == 3 or (crops.ndim == 4 and crops.shape[3] in (3, 4))):
+            raise ValueError(f"crops must be (F,H,W,3), (F,H,W,4) or (F,H,W) uint8, not {crops.dtype} {crops.shape}")
         if crops.shape[0] == 0:
             return []
         with torch.cuda.device(self.device):
@@ -566,7 +603,7 @@ class Cropper:
         return np.array([os.path.splitext(str(n))[1].lower() in PNG_EXTENSIONS for n in file_names], bool)
 
     def _encode_on_device(self, pixels_dev, pixels, names):
-        """``encoder="device"`` / ``png_encoder="device"``: (F,H,W[,3]) u8 device pixels (and their host copy, if one
+        """``encoder="device"`` / ``png_encoder="device"``: (F,H,W[,3 or 4]) u8 device pixels (and their host copy, if one
         exists already) of the faces or masks cut from ``names`` -> a list with the encoded file (bytes) of every face
         whose format is compressed on the GPU — JPEG targets by ``encoder``, PNG targets by ``png_encoder`` — and the
         host pixels of every other.  The pixels are read back only when some target needs the host."""

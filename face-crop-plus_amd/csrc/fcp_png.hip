@@ -1,4 +1,4 @@
-// zlib streams of uint8 faces (f,h,w,c), c = 1 (gray) or 3 (RGB), for PNG files, on the device (INTEGRATION.md section
+// zlib streams of uint8 faces (f,h,w,c), c = 1 (gray), 3 (RGB) or 4 (RGBA), for PNG files, on the device (INTEGRATION.md section
 // 2m; the definition is stated once more in tests/png_ref.py, which these kernels are held to byte for byte; the file
 // around the stream is pngenc.png_file, on the host).  Six kernels after one memset:
 //
@@ -631,7 +631,8 @@ Layout layout_of(int f, int h, int w, int c) {
 
 int check_sizes(int f, int h, int w, int channels) {
   FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "png_encode: bad sizes (f %d, h %d, w %d)", f, h, w);
-  FCP_REQUIRE(channels == 1 || channels == 3, "png_encode: 1 (gray) or 3 (RGB) channels, not %d", channels);
+  FCP_REQUIRE(channels == 1 || channels == 3 || channels == 4, "png_encode: 1 (gray), 3 (RGB) or 4 (RGBA) channels, not %d",
+              channels);
   FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "png_encode: faces of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h,
               w);
   const long long symbols = (long long)h * ((long long)w * channels + 1) + 1;

@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -469,14 +469,14 @@ std::tuple<Tensor, Tensor> jpeg_huffman_tables(const Tensor& freq, bool with_cod
   return {tables, codes};
 }
 
-// zlib streams for PNG files of faces (f,h,w,3) or (f,h,w) uint8 into the rows of `out` (f, capacity) uint8 — rows may
+// zlib streams for PNG files of faces (f,h,w,3), (f,h,w,4) or (f,h,w) uint8 into the rows of `out` (f, capacity) uint8 — rows may
 // be a view of a wider buffer (unit stride inside a row) — and the true lengths (f,) int32, which may exceed the capacity
 // (fcp_png_encode_u8; the file around a stream is written on the host).  The workspace comes from the caching allocator.
 Tensor png_encode(const Tensor& pixels, const Tensor& out) {
   dev(pixels, "pixels", at::kByte);
   FCP_DEVICE_GUARD(pixels);
-  TORCH_CHECK((pixels.dim() == 4 && (pixels.size(3) == 3 || pixels.size(3) == 1)) || pixels.dim() == 3,
-              "pixels (f,h,w,3) or (f,h,w) uint8");
+  TORCH_CHECK((pixels.dim() == 4 && (pixels.size(3) == 3 || pixels.size(3) == 4 || pixels.size(3) == 1)) || pixels.dim() == 3,
+              "pixels (f,h,w,3), (f,h,w,4) or (f,h,w) uint8");
   const int64_t f = pixels.size(0), h = pixels.size(1), w = pixels.size(2), c = pixels.dim() == 4 ? pixels.size(3) : 1;
   TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "pixels: sizes past int");
   TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kByte && out.get_device() == pixels.get_device(),
@@ -640,6 +640,50 @@ Tensor matte_blur_alpha(const Tensor& crops, const Tensor& labels, const Tensor&
   return out;
 }
 
+// The feathered alpha (f,h,w) uint8 of label maps (f,h,w) uint8: fcp_matte_u8's alpha alone (fcp_feather_alpha_u8).
+Tensor feather_alpha(const Tensor& labels, int64_t class_bits, int64_t feather) {
+  dev(labels, "labels", at::kByte);
+  FCP_DEVICE_GUARD(labels);
+  TORCH_CHECK(labels.dim() == 3, "labels (f,h,w) uint8");
+  const int64_t f = labels.size(0), h = labels.size(1), w = labels.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "labels (f,h,w): sizes past int");
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  TORCH_CHECK(feather >= INT_MIN && feather <= INT_MAX, "feather past int");
+  Tensor alpha = at::empty_like(labels);
+  ok(fcp_feather_alpha_u8(labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits, (int)feather,
+                          alpha.data_ptr<uint8_t>(), cur_stream()),
+     "fcp::feather_alpha");
+  return alpha;
+}
+
+// Crops (f,h,w,3) uint8 and an alpha plane (f,h,w) uint8 -> the RGBA cut-out (f,h,w,4) (mode 0) or the composite over a
+// uniform fill (f,h,w,3) (mode 1), with the subject's colour estimated through taps = t[0..radius] (empty: no estimate,
+// RGBA only) (fcp_cutout_u8); the 32-bytes-per-pixel workspace lives for the call.
+Tensor cutout(const Tensor& crops, const Tensor& alpha, int64_t mode, int64_t bg_r, int64_t bg_g, int64_t bg_b, at::IntArrayRef taps) {
+  dev(crops, "crops", at::kByte);
+  dev(alpha, "alpha", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  int64_t f, h, w;
+  crops_and_plane(crops, alpha, "alpha", f, h, w);
+  for (int64_t v : {mode, bg_r, bg_g, bg_b}) TORCH_CHECK(v >= INT_MIN && v <= INT_MAX, "mode / fill past int");
+  const int64_t radius = (int64_t)taps.size() - 1;
+  TORCH_CHECK(taps.empty() || (radius >= 3 && radius <= 48), "cutout: taps must be empty or t[0..radius] with radius 3..48 (got ",
+              taps.size(), " taps)");
+  uint16_t t16[49] = {};
+  for (int64_t k = 0; k <= radius; ++k) {
+    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, "cutout: tap ", k, " past 16 bits");
+    t16[k] = (uint16_t)taps[k];
+  }
+  Tensor out = at::empty({f, h, w, mode == FCP_CUTOUT_RGBA ? 4 : 3}, crops.options());
+  const int64_t need = taps.empty() ? 0 : fcp_cutout_workspace_bytes((int)f, (int)h, (int)w);
+  Tensor work = at::empty({need < 0 ? 0 : need}, crops.options());
+  ok(fcp_cutout_u8(crops.data_ptr<uint8_t>(), alpha.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (int)mode, (int)bg_r, (int)bg_g,
+                   (int)bg_b, t16, taps.empty() ? 0 : (int)radius, out.data_ptr<uint8_t>(), work.data_ptr(), work.numel(),
+                   cur_stream()),
+     "fcp::cutout");
+  return out;
+}
+
 // The cleaned binary label map (f,h,w) uint8, 0 / 1, of label maps (f,h,w) uint8: the largest 8-connected component of
 // the hard mask and / or its holes of at most max_hole pixels filled (fcp_subject_mask_u8); the 12-bytes-per-pixel
 // workspace lives for the call.
@@ -749,6 +793,8 @@ TORCH_LIBRARY(fcp, m) {
   m.def("matte_alpha(Tensor crops, Tensor alpha, int bg_r, int bg_g, int bg_b) -> Tensor");
   m.def("matte_blur_alpha(Tensor crops, Tensor labels, Tensor alpha, int class_bits, int[] taps) -> Tensor");
   m.def("subject_mask(Tensor labels, int class_bits, bool keep_largest, int max_hole) -> Tensor");
+  m.def("feather_alpha(Tensor labels, int class_bits, int feather) -> Tensor");
+  m.def("cutout(Tensor crops, Tensor alpha, int mode, int bg_r, int bg_g, int bg_b, int[] taps) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -785,6 +831,8 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("matte_alpha", &matte_alpha);
   m.impl("matte_blur_alpha", &matte_blur_alpha);
   m.impl("subject_mask", &subject_mask);
+  m.impl("feather_alpha", &feather_alpha);
+  m.impl("cutout", &cutout);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

@@ -29,6 +29,17 @@ and ``matte_blur`` then composite through that plane (``alpha=``).
 
 The subject comes first, then the holes: an island inside a hole is background by then and counts in the hole's area.
 ``out`` takes the label map's place downstream, with the class bit set ``SUBJECT_BITS`` (class 1).
+
+``Cropper(background="transparent")`` (section 2n) writes no fill at all: the crop becomes an RGBA cut-out
+``(colour, alpha)``, ``(0, 0, 0, 0)`` where alpha is 0 (``feather_alpha`` + ``cutout``: ``fcp_feather_alpha_u8``,
+``fcp_cutout_u8``).  ``Cropper(decontaminate=sigma)`` replaces the crop's colour in the soft edge, which is already mixed
+with the old background, by an estimate of the subject's own, for the cut-out and for the composite over a uniform fill:
+
+    sF, sB = 1 where alpha == 255 / where alpha == 0: the pixels that are certainly subject / certainly background
+    F^, B^ = the mask-normalised Gaussians of the crop over sF / over sB (``blur_taps(sigma)``; the crop's colour where
+             the window holds no such pixel)
+    R      = 255 c - (alpha F^ + (255 - alpha) B^)
+    F      = clamp((65025 F^ + alpha R + 32512) // 65025, 0, 255) where 0 < alpha < 255, else c
 """
 from __future__ import annotations
 
@@ -52,6 +63,8 @@ MIN_REFINE_EPS, MAX_REFINE_EPS, DEFAULT_REFINE_EPS = 1, 4096, 64
 SUBJECTS = ("largest",)
 MAX_FILL_HOLES = 8192 * 8192   # the largest crop the kernels take
 SUBJECT_BITS = 1 << 1          # the class bit set that reads ``subject_mask``'s 0 / 1 output as a label map: class 1
+TRANSPARENT = "transparent"    # ``check_background``'s answer for the RGBA cut-out: no fill, the alpha ships in the file
+CUTOUT_RGBA, CUTOUT_FILL = 0, 1   # fcp_hip.h: FCP_CUTOUT_RGBA, FCP_CUTOUT_FILL
 
 
 def _is_int(v) -> bool:
@@ -61,12 +74,15 @@ def _is_int(v) -> bool:
 
 
 def check_background(background):
-    """``background`` of the Cropper -> None (off) or the fill (r, g, b): an int 0..255 (gray) or three of them."""
+    """``background`` of the Cropper -> None (off), the fill (r, g, b): an int 0..255 (gray) or three of them, or
+    ``TRANSPARENT`` for the string "transparent" (an RGBA cut-out in place of a fill)."""
     if background is None:
         return None
+    if isinstance(background, str) and background == TRANSPARENT:
+        return TRANSPARENT
     values = [background] * 3 if _is_int(background) else background
     if isinstance(values, (str, bytes)) or not hasattr(values, "__len__") or len(values) != 3 or not all(_is_int(v) for v in values):
-        raise ValueError(f"background must be None, an int 0..255 or three of them (R, G, B), not {background!r}")
+        raise ValueError(f"background must be None, an int 0..255, three of them (R, G, B) or {TRANSPARENT!r}, not {background!r}")
     fill = tuple(int(v) for v in values)
     if min(fill) < 0 or max(fill) > 255:
         raise ValueError(f"background components must be 0..255, not {background!r}")
@@ -105,6 +121,17 @@ def check_blur(sigma):
     if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or \
             not np.isfinite(sigma) or not MIN_SIGMA <= sigma <= MAX_SIGMA:
         raise ValueError(f"background_blur must be None or a finite sigma in [{MIN_SIGMA}, {MAX_SIGMA}] pixels, not {sigma!r}")
+    return float(sigma)
+
+
+def check_decontaminate(sigma):
+    """``decontaminate`` of the Cropper -> None (off) or sigma in output pixels as a float: finite, 0.5..16, the range of
+    ``background_blur`` (the taps are ``blur_taps``' too)."""
+    if sigma is None:
+        return None
+    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(sigma) or not MIN_SIGMA <= sigma <= MAX_SIGMA:
+        raise ValueError(f"decontaminate must be None or a finite sigma in [{MIN_SIGMA}, {MAX_SIGMA}] pixels, not {sigma!r}")
     return float(sigma)
 
 
@@ -200,6 +227,47 @@ def subject_mask(labels_dev: torch.Tensor, class_bits: int, keep_largest: bool, 
     work = torch.empty((need,), dtype=torch.uint8, device=labels_dev.device)
     N.check(N.lib().fcp_subject_mask_u8(N.ptr(labels_dev), f, h, w, int(class_bits), int(bool(keep_largest)), int(max_hole),
                                         N.ptr(out), N.ptr(work), need, N.stream_ptr()), "fcp_subject_mask_u8")
+    return out
+
+
+def feather_alpha(labels_dev: torch.Tensor, class_bits: int, feather: int) -> torch.Tensor:
+    """labels (F,H,W) u8, device -> alpha (F,H,W) u8, device: the feathered mask ``matte`` composites through, alone.  One
+    launch; H, W <= 8192."""
+    assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and labels_dev.dim() == 3
+    if T.ENABLED:
+        return T.load().feather_alpha(labels_dev, int(class_bits), int(feather))
+    f, h, w = labels_dev.shape
+    alpha = torch.empty_like(labels_dev)
+    N.check(N.lib().fcp_feather_alpha_u8(N.ptr(labels_dev), f, h, w, int(class_bits), int(feather), N.ptr(alpha), N.stream_ptr()),
+            "fcp_feather_alpha_u8")
+    return alpha
+
+
+def cutout(crops_dev: torch.Tensor, alpha: torch.Tensor, fill=None, taps=None) -> torch.Tensor:
+    """crops (F,H,W,3) u8 and an alpha plane (F,H,W) u8 (``feather_alpha``'s or ``refine_alpha``'s), device ->
+    ``fill`` None: the RGBA cut-out (F,H,W,4) u8, ``(colour, alpha)`` where alpha > 0 and zeros where it is 0;
+    ``fill`` (r, g, b): the composite (F,H,W,3) u8 of the colour over that fill.  The colour is the crop's without
+    ``taps`` (RGBA only: over a fill that is ``matte``), else the subject's colour estimated with the taps t[0..r] of
+    ``blur_taps``: its weights are the pixels whose alpha is exactly 255 (subject) and exactly 0 (background), and where
+    the window holds neither kind the crop's colour stands.  One launch without taps; two and a workspace of 32 bytes per
+    pixel that lives for the call with them; H, W <= 8192."""
+    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
+    _check_alpha(alpha, crops_dev)
+    mode = CUTOUT_RGBA if fill is None else CUTOUT_FILL
+    r, g, b = (0, 0, 0) if fill is None else (int(v) for v in fill)
+    taps = [] if taps is None else [int(t) for t in taps]
+    if T.ENABLED:
+        return T.load().cutout(crops_dev, alpha, mode, r, g, b, taps)
+    if taps and (not MIN_RADIUS + 1 <= len(taps) <= MAX_RADIUS + 1 or min(taps) < 0 or max(taps) > 65535):
+        raise RuntimeError(f"fcp_cutout_u8: taps must be empty or t[0..radius] with radius {MIN_RADIUS}..{MAX_RADIUS}, each 16 "
+                           f"bits (got {len(taps)} taps)")
+    f, h, w, _ = crops_dev.shape
+    out = torch.empty((f, h, w, 4 if fill is None else 3), dtype=torch.uint8, device=crops_dev.device)
+    need = max(int(N.lib().fcp_cutout_workspace_bytes(f, h, w)), 0) if taps else 0
+    work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
+    t16 = (ctypes.c_uint16 * max(len(taps), 1))(*taps)
+    N.check(N.lib().fcp_cutout_u8(N.ptr(crops_dev), N.ptr(alpha), f, h, w, mode, r, g, b, t16, max(len(taps) - 1, 0), N.ptr(out),
+                                  N.ptr(work), need, N.stream_ptr()), "fcp_cutout_u8")
     return out
 
 

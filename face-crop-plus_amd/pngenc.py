@@ -27,8 +27,21 @@ def supported(h: int, w: int, c: int) -> bool:
     return 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE and c in (1, 3) and h * (w * c + 1) + 1 < MAX_SYMBOLS
 
 
+def supported_rgba(h: int, w: int) -> bool:
+    """``supported`` for RGBA faces (F,H,W,4): the same limits at c = 4, h * (4 w + 1) + 1 < 9227464, so 1500 x 1500 fits
+    and 1520 x 1520 does not.  (``supported`` keeps answering for gray and RGB alone.)"""
+    return 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE and h * (w * 4 + 1) + 1 < MAX_SYMBOLS
+
+
 def _chunk(kind: bytes, data: bytes) -> bytes:
     return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data))
+
+
+def _file(h: int, w: int, colour_type: int, stream: bytes) -> bytes:
+    if not (1 <= h < 2 ** 31 and 1 <= w < 2 ** 31):
+        raise ValueError(f"a PNG image is 1..2^31-1 px on each side, not {h} x {w}")
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, colour_type, 0, 0, 0)
+    return b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", bytes(stream)) + _chunk(b"IEND", b"")
 
 
 def png_file(h: int, w: int, c: int, stream: bytes) -> bytes:
@@ -36,14 +49,16 @@ def png_file(h: int, w: int, c: int, stream: bytes) -> bytes:
     c = 3; no interlace), one IDAT, IEND.  The chunk CRC-32 is zlib's, on the host, over bytes that are already here."""
     if c not in (1, 3):
         raise ValueError(f"channels must be 1 or 3, not {c!r}")
-    if not (1 <= h < 2 ** 31 and 1 <= w < 2 ** 31):
-        raise ValueError(f"a PNG image is 1..2^31-1 px on each side, not {h} x {w}")
-    ihdr = struct.pack(">IIBBBBB", w, h, 8, 0 if c == 1 else 2, 0, 0, 0)
-    return b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", bytes(stream)) + _chunk(b"IEND", b"")
+    return _file(h, w, 0 if c == 1 else 2, stream)
+
+
+def png_file_rgba(h: int, w: int, stream: bytes) -> bytes:
+    """``png_file`` around the zlib stream of RGBA scanlines: IHDR colour type 6 (8 bit, no interlace)."""
+    return _file(h, w, 6, stream)
 
 
 def encode_streams(pixels_dev: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-    """pixels (F,H,W,3) or (F,H,W) u8 device, out (F, capacity) u8 device (rows may be a view of a wider buffer) ->
+    """pixels (F,H,W,3), (F,H,W,4) or (F,H,W) u8 device, out (F, capacity) u8 device (rows may be a view of a wider buffer) ->
     lengths (F,) int32 device.  Row i receives face i's zlib stream, at most ``capacity`` bytes of it; the length is the
     true one even then.  One memset and six launches."""
     assert pixels_dev.dtype == torch.uint8 and pixels_dev.is_contiguous() and pixels_dev.dim() in (3, 4)
@@ -89,7 +104,8 @@ def _host_png(pixels: np.ndarray) -> bytes:
 
 
 def encode_png(pixels_dev: torch.Tensor, capacity: int | None = None) -> list:
-    """pixels (F,H,W,3) or (F,H,W) u8 device -> F complete PNG files (bytes) that decode to those pixels.
+    """pixels (F,H,W,3), (F,H,W,4) (RGBA: colour type 6) or (F,H,W) u8 device -> F complete PNG files (bytes) that decode
+    to those pixels.
     ``capacity``: bytes of a face's slot on the device (default: H * (W * C + 1) + 1024, which no stream whose codes
     average 9 bits or less outgrows); what comes back to the host is the lengths and the used part of the slots — not
     the pixels.  A face whose stream is longer than its slot is read back alone and encoded on the host with
@@ -102,7 +118,7 @@ def encode_png(pixels_dev: torch.Tensor, capacity: int | None = None) -> list:
     def on_host(i):
         px = pixels_dev[i].cpu().numpy()
         return _host_png(px[..., 0] if px.ndim == 3 and c == 1 else px)
-    if not supported(h, w, c):
+    if not (supported_rgba(h, w) if c == 4 else supported(h, w, c)):
         return [on_host(i) for i in range(f)]
     capacity = h * (w * c + 1) + 1024 if capacity is None else int(capacity)
     out = torch.empty((f, capacity), dtype=torch.uint8, device=pixels_dev.device)
@@ -110,4 +126,5 @@ def encode_png(pixels_dev: torch.Tensor, capacity: int | None = None) -> list:
     fits = lengths <= capacity
     used = int(lengths[fits].max()) if fits.any() else 0
     streams = out[:, :used].cpu().numpy() if used else None
-    return [png_file(h, w, c, streams[i, :lengths[i]].tobytes()) if fits[i] else on_host(i) for i in range(f)]
+    wrap = (lambda data: png_file_rgba(h, w, data)) if c == 4 else (lambda data: png_file(h, w, c, data))
+    return [wrap(streams[i, :lengths[i]].tobytes()) if fits[i] else on_host(i) for i in range(f)]

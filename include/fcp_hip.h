@@ -530,8 +530,8 @@ int fcp_jpeg_encode_ex_u8(const uint8_t* crops, int f, int h, int w, int channel
  * a misaligned freq / codes fail with a message, before any HIP call. */
 int fcp_jpeg_huffman_tables(const uint32_t* freq, int n, uint8_t* tables, uint32_t* codes, fcp_stream_t stream);
 
-/* zlib streams for PNG files of faces (f,h,w,channels) uint8, channels 3 (RGB)
- * or 1 (gray), on the device (where the stream is defined;
+/* zlib streams for PNG files of faces (f,h,w,channels) uint8, channels 3 (RGB),
+ * 4 (RGBA) or 1 (gray), on the device (where the stream is defined;
  * tests/png_ref.py states it in Python): face i's stream, 78 01, one dynamic
  * Huffman block, Adler-32, goes to out + i * out_stride; the host wraps it
  * into a file (pngenc.png_file).  Every scanline takes the PNG filter 0..4
@@ -556,11 +556,11 @@ int fcp_jpeg_huffman_tables(const uint32_t* freq, int n, uint8_t* tables, uint32
  * One memset and six launches; no host round trip, one stream, nothing
  * allocated, the same bytes from run to run.  f == 0 is a no-op.  Refused with
  * a message, before any HIP call: h, w < 1 or > 8192, f < 0 or > 65535,
- * channels other than 1 / 3, capacity < 0 or > out_stride, a null pointer, a
+ * channels other than 1 / 3 / 4, capacity < 0 or > out_stride, a null pointer, a
  * workspace too small or not 16-byte aligned, and a face with
  * h * (w * channels + 1) + 1 >= 9 227 464 (one below the 35th Fibonacci
  * number: below it no Huffman tree is deeper than 32, the range of the
- * lengths before the limit; about 1750 x 1750 RGB).  fcp_png_workspace_bytes
+ * lengths before the limit; about 1750 x 1750 RGB, 1500 x 1500 RGBA).  fcp_png_workspace_bytes
  * then returns -1. */
 int64_t fcp_png_workspace_bytes(int f, int h, int w, int channels);
 int fcp_png_encode_u8(const uint8_t* pixels, int f, int h, int w, int channels,
@@ -691,6 +691,54 @@ int fcp_matte_alpha_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h,
 int fcp_matte_blur_alpha_u8(const uint8_t* crops, const uint8_t* labels, const uint8_t* alpha, int f, int h, int w,
                             uint32_t class_bits, const uint16_t* taps, int radius, uint8_t* out, void* workspace,
                             int64_t workspace_bytes, fcp_stream_t stream);
+
+/* RGBA cut-outs and the subject's own edge colours, in
+ * integers throughout.
+ * fcp_feather_alpha_u8: alpha_out (f,h,w) = the alpha of fcp_matte_u8 for
+ * labels, class_bits and feather, alone.  One launch, no workspace; labels
+ * and alpha_out may start at any byte and must not overlap.  f == 0 is a
+ * no-op; the sizes, feather, class_bits and null pointers fail as there, with
+ * a "feather_alpha:" message, before any HIP call.
+ * fcp_cutout_u8: crops (f,h,w,3) and an alpha plane (f,h,w) of the caller's
+ * (fcp_feather_alpha_u8's or fcp_matte_refine_u8's) ->
+ *   mode FCP_CUTOUT_RGBA: out (f,h,w,4): (F_r, F_g, F_b, alpha) where
+ *       alpha > 0 and (0,0,0,0) where alpha == 0;
+ *   mode FCP_CUTOUT_FILL: out (f,h,w,3):
+ *       (F * alpha + bg * (255 - alpha) + 127) / 255 per channel.
+ * radius == 0: F = c, the crop's colour (RGBA only: the fill mode without an
+ * estimate is fcp_matte_alpha_u8 and is refused here).  radius 3..48 with
+ * taps as in fcp_matte_blur_u8: F is the "blur fusion" estimate of the
+ * subject's colour.  sF = 1 where alpha == 255, sB = 1 where alpha == 0;
+ *   D_F   = sum_j sum_i t|j| t|i| sF(y+j, x+i) over the positions inside the
+ *           image, N_F,ch the same sum of sF c_ch; D_B, N_B,ch with sB;
+ *   F^_ch = D_F > 0 ? (N_F,ch + D_F / 2) / D_F : c_ch;  B^_ch likewise;
+ *   R_ch  = 255 c_ch - (alpha F^_ch + (255 - alpha) B^_ch);
+ *   E_ch  = clamp(floor((65025 F^_ch + alpha R_ch + 32512) / 65025), 0, 255);
+ *   F_ch  = c_ch where alpha == 255, E_ch where 0 < alpha < 255.
+ * The sums are unsigned 32 bits with the bounds of fcp_matte_blur_u8; the
+ * correction stays below 2^25 in magnitude.
+ * workspace: fcp_cutout_workspace_bytes(f,h,w) = 32 f h w bytes of device
+ * memory, 16-byte aligned, contents irrelevant (the eight horizontal sums of
+ * every pixel); not read with radius 0, where it may be NULL.  out is its own
+ * array: it must not overlap crops, alpha or the workspace.  crops and alpha
+ * may start at any byte; an RGBA out must be 4-byte aligned (one dword store
+ * per pixel), a fill out may start at any byte; nothing outside out and the
+ * workspace is written.  One launch with radius 0, else two, on `stream`;
+ * nothing allocated, the same bytes from run to run.
+ * f == 0 is a no-op; f < 0, h or w < 1 or > 8192, f > 65535, a mode other
+ * than the two, a radius outside {0, 3..48}, the fill mode with radius 0, a
+ * fill component outside 0..255, (radius > 0) null taps, a tap of 0, taps
+ * that do not sum to 4096, or (f > 0) a null crops / alpha / out, a
+ * misaligned RGBA out, (radius > 0) a workspace that is null, too small or
+ * misaligned fail with a "cutout:" message, before any HIP call
+ * (fcp_cutout_workspace_bytes then returns -1). */
+#define FCP_CUTOUT_RGBA 0
+#define FCP_CUTOUT_FILL 1
+int fcp_feather_alpha_u8(const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather, uint8_t* alpha_out,
+                         fcp_stream_t stream);
+int64_t fcp_cutout_workspace_bytes(int f, int h, int w);
+int fcp_cutout_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, int mode, int bg_r, int bg_g, int bg_b,
+                  const uint16_t* taps, int radius, uint8_t* out, void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
 
 /* One connected subject in a matte: connected-component
  * labelling of the hard mask of label maps (f,h,w) uint8, every face on its
