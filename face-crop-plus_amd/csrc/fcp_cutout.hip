@@ -6,12 +6,10 @@
 // the same in numpy; the kernels are held to it byte for byte.
 //
 //   c (F,H,W,3) u8, a (F,H,W) u8: the alpha the mode already has (fcp_feather_alpha_u8's, or fcp_matte_refine_u8's)
-//   t[0..r]   : all >= 1, t[0] + 2 sum(t[1..r]) == 4096, 3 <= r <= 48; made on the host from sigma (matte.blur_taps)
+//   t[0..r]   : the taps of fcp_masked_blur.h, made on the host from sigma (matte.blur_taps)
 //   sF(p)     = 1 where a(p) == 255 else 0                                              "certainly subject"
 //   sB(p)     = 1 where a(p) == 0   else 0                                              "certainly background"
-//   D_F(y,x)  = sum_j sum_i t|j| t|i| sF(y+j, x+i)                                      taps inside the image only
-//   N_F,ch    = sum_j sum_i t|j| t|i| sF(y+j, x+i) c_ch(y+j, x+i)                       the same taps; D_B, N_B,ch with sB
-//   F^_ch     = D_F > 0 ? (N_F,ch + D_F / 2) / D_F : c_ch                               B^_ch likewise with D_B, N_B
+//   F^_ch, B^_ch = the mask-normalised Gaussians B_ch of fcp_masked_blur.h over the sides sF (side 0) and sB (side 1)
 //   R_ch      = 255 c_ch - (a F^_ch + (255 - a) B^_ch)                                  in [-65025, 65025]
 //   E_ch      = clamp(floor((65025 F^_ch + a R_ch + 32512) / 65025), 0, 255)
 //   F_ch      = c_ch where a == 255;  E_ch where 0 < a < 255;  (unused) where a == 0
@@ -21,22 +19,17 @@
 //   fill, radius r : (F_ch a + fill_ch (255 - a) + 127) / 255, three channels           fcp_feather.h's over255
 //   fill, radius 0 : refused: that is fcp_matte_alpha_u8, which stays the one statement of it
 //
-// Bounds.  The sums are those of fcp_matte_blur.hip with another indicator, unsigned 32 bits: a horizontal sum is at
-// most 255 * 4096 < 2^20, N <= 255 * 4096^2 = 4 278 190 080 and N + D / 2 <= 4 286 578 688 < 2^32, which is why taps that
-// do not sum to 4096 are refused; N <= 255 D, so F^, B^ <= 255.  The correction is signed 32 bits: |a R| <= 254 * 65025
-// and 65025 F^ <= 255 * 65025, so the numerator lies in (-255 * 65025, 2^25); the floor division adds 255 * 65025
-// (the numerator is then positive), divides and takes 255 off again.
+// Bounds.  The sums and their unsigned 32-bit bounds are fcp_masked_blur.h's; F^, B^ <= 255.  The correction is signed
+// 32 bits: |a R| <= 254 * 65025 and 65025 F^ <= 255 * 65025, so the numerator lies in (-255 * 65025, 2^25); the floor
+// division adds 255 * 65025 (the numerator is then positive), divides and takes 255 off again.
 //
-// fcp_feather_alpha_u8: labels + class bits + feather -> the alpha plane of fcp_matte_u8, alone.  matte_kernel's tile
-// (64 x 32, fcp_feather.h: Tile::stage / Tile::alpha) and its LDS: 7600 B at feather 7, none at feather 0.
+// The alpha plane comes from fcp_feather_alpha_u8 (fcp_matte.hip) or fcp_matte_refine_u8.
 //
 // fcp_cutout_u8 with a radius: two launches and a workspace of 32 bytes per pixel (the caller's).
 //
-//   cutout_rows_kernel, workgroups of 256 lanes over (4 rows x 256 columns, face): blur_rows_kernel with two staged
-//   dwords per pixel, (s, s c_r, s c_g, s c_b) as four bytes for the subject side and for the background side, zero
-//   outside the image and where the indicator is 0; a lane per output pixel runs the 2 r + 1 taps over consecutive
-//   8-byte entries and stores the eight sums as two 16-byte stores, subject side first.  LDS per workgroup:
-//   4 x (256 + 96) x 8 B + 97 taps x 4 B = 11652 B: 14 workgroups would fit a CU, the 32 wave slots allow 8.
+//   cutout_rows_kernel, workgroups of 256 lanes over (4 rows x 256 columns, face): fcp_masked_blur.h's rows_pass with
+//   two staged dwords per pixel, the subject side first.  LDS per workgroup: 4 x (256 + 96) x 8 B + 97 taps x 4 B =
+//   11652 B: 14 workgroups would fit a CU, the 32 wave slots allow 8.
 //
 //   cutout_cols_kernel, workgroups of 256 lanes over (128 rows x 8 columns, face), four pixels of a row per lane, one
 //   group per lane.  Two sets of sums double the 16 bytes per staged pixel of blur_cols_kernel: its 64 x 16 tile would
@@ -63,27 +56,17 @@
 // byte: the same bytes from run to run.
 #include "fcp_common.h"
 #include "fcp_crop_bytes.h"
+#include "fcp_crop_checks.h"
 #include "fcp_feather.h"
 #include "fcp_hip.h"
+#include "fcp_masked_blur.h"
 
 namespace {
 
 using namespace fcp_crop_bytes;
+using namespace fcp_crop_checks;
 using namespace fcp_feather;
-
-constexpr int kThreads = 256;
-constexpr int kMinRadius = 3;
-constexpr int kMaxRadius = 48;
-constexpr uint32_t kTapSum = 4096;
-
-// feather alpha: matte_kernel's tile
-constexpr int kAlphaTileW = 64;
-constexpr int kAlphaTileH = 32;
-
-// rows pass
-constexpr int kRowTileW = 256;
-constexpr int kRowTileH = 4;
-constexpr int kRowPitch = kRowTileW + 2 * kMaxRadius;   // 8-byte entries of a staged row
+using namespace fcp_masked_blur;
 
 // columns pass
 constexpr int kTileW = 8;               // output pixels of a tile row: 2 groups of four
@@ -91,50 +74,6 @@ constexpr int kTileH = 128;
 constexpr int kGroups = kTileW / 4;
 constexpr int kColPitch = 2 * kTileW + 1;   // uint4 of a staged row: (subject, background) per pixel and the pad
 static_assert(kTileH * kGroups == kThreads, "one group per lane");
-
-struct CutoutTaps {
-  uint16_t t[kMaxRadius + 1];           // 49 x 16 bit in the kernel argument block
-};
-
-// the mirrored tap table, 2 r + 1 dwords: entry k is t|k - r|
-__device__ __forceinline__ void stage_taps(uint32_t* tl, const CutoutTaps& taps, int radius) {
-  const int k = threadIdx.x;
-  if (k <= 2 * radius) tl[k] = taps.t[k < radius ? radius - k : k - radius];
-}
-
-template <int R>
-__global__ void __launch_bounds__(kThreads) feather_alpha_kernel(const uint8_t* __restrict__ labels, int h, int w, int tiles_x,
-                                                                 uint32_t bits, uint8_t* __restrict__ alpha) {
-  using Feather = Tile<R, kAlphaTileW, kAlphaTileH>;
-  extern __shared__ uint2 lds[];         // R > 0: the feather's tile; R == 0: none
-  const int f = blockIdx.y;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int x0 = tx * kAlphaTileW, y0 = ty * kAlphaTileH;
-  const int nrows = min(kAlphaTileH, h - y0);
-  const int groups = (min(kAlphaTileW, w - x0) + 3) >> 2;
-
-  if constexpr (R > 0) {
-    Feather::stage(lds, labels + (size_t)f * h * w, h, w, x0, y0, nrows, groups, bits, kThreads);
-    __syncthreads();
-  }
-  for (int i = threadIdx.x; i < nrows * groups; i += kThreads) {
-    const int r = i / groups, g = i - r * groups;
-    const int x = x0 + 4 * g;
-    const int npx = min(4, w - x);
-    const size_t pixel = ((size_t)f * h + (y0 + r)) * w + x;
-    uint32_t a[4];
-    Feather::alpha(lds, r, g, labels + pixel, npx, bits, a);
-    store_u8(alpha + pixel, npx, a);
-  }
-}
-
-template <int R>
-void launch_alpha(const uint8_t* labels, int f, int h, int w, uint32_t bits, uint8_t* alpha, hipStream_t stream) {
-  const int tiles_x = fcp_cdiv(w, kAlphaTileW), tiles_y = fcp_cdiv(h, kAlphaTileH);
-  constexpr size_t lds = Tile<R, kAlphaTileW, kAlphaTileH>::kBytes;
-  hipLaunchKernelGGL((feather_alpha_kernel<R>), dim3(tiles_x * tiles_y, f), dim3(kThreads), lds, stream, labels, h, w, tiles_x,
-                     bits, alpha);
-}
 
 // byte k of an RGB group (pixel k / 3, channel k % 3)
 __device__ __forceinline__ uint32_t rgb_byte(const uint32_t c[3], int k) { return (c[k >> 2] >> (8 * (k & 3))) & 255u; }
@@ -162,59 +101,10 @@ __global__ void __launch_bounds__(kThreads) cutout_plain_kernel(const uint8_t* _
 }
 
 __global__ void __launch_bounds__(kThreads) cutout_rows_kernel(const uint8_t* __restrict__ crops, const uint8_t* __restrict__ alpha,
-                                                               int h, int w, int tiles_x, CutoutTaps taps, int radius,
+                                                               int h, int w, int tiles_x, Taps taps, int radius,
                                                                uint4* __restrict__ sums) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  uint2* stage = reinterpret_cast<uint2*>(smem);          // kRowTileH rows of kRowPitch (subject, background) entries
-  uint32_t* tl = reinterpret_cast<uint32_t*>(stage + kRowTileH * kRowPitch);
-  const int f = blockIdx.y;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int x0 = tx * kRowTileW, y0 = ty * kRowTileH;
-  const int nrows = min(kRowTileH, h - y0), ncols = min(kRowTileW, w - x0);
-  const int span = ncols + 2 * radius;
-
-  stage_taps(tl, taps, radius);
-  for (int i = threadIdx.x; i < nrows * span; i += kThreads) {
-    const int tr = i / span, d = i - tr * span;
-    const int x = x0 - radius + d;
-    uint2 v = make_uint2(0u, 0u);
-    if (x >= 0 && x < w) {
-      const size_t pixel = ((size_t)f * h + (y0 + tr)) * w + x;
-      const uint32_t a = alpha[pixel];
-      if (a == 255u || a == 0u) {
-        const uint8_t* c = crops + pixel * 3;
-        const uint32_t e = 1u | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16) | ((uint32_t)c[2] << 24);
-        v = a == 255u ? make_uint2(e, 0u) : make_uint2(0u, e);
-      }
-    }
-    stage[tr * kRowPitch + d] = v;
-  }
-  __syncthreads();
-
-  for (int i = threadIdx.x; i < nrows * ncols; i += kThreads) {
-    const int tr = i / ncols, cx = i - tr * ncols;
-    const uint2* s = stage + tr * kRowPitch + cx;        // output x sums staged x .. x + 2 r
-    uint32_t sf[4] = {0u, 0u, 0u, 0u}, sb[4] = {0u, 0u, 0u, 0u};   // each <= 255 * 4096
-    for (int k = 0; k <= 2 * radius; ++k) {
-      const uint2 v = s[k];
-      const uint32_t t = tl[k];
-      sf[0] += t * (v.x & 255u);
-      sf[1] += t * ((v.x >> 8) & 255u);
-      sf[2] += t * ((v.x >> 16) & 255u);
-      sf[3] += t * (v.x >> 24);
-      sb[0] += t * (v.y & 255u);
-      sb[1] += t * ((v.y >> 8) & 255u);
-      sb[2] += t * ((v.y >> 16) & 255u);
-      sb[3] += t * (v.y >> 24);
-    }
-    uint4* o = sums + 2 * (((size_t)f * h + (y0 + tr)) * w + (x0 + cx));
-    o[0] = make_uint4(sf[0], sf[1], sf[2], sf[3]);
-    o[1] = make_uint4(sb[0], sb[1], sb[2], sb[3]);
-  }
+  rows_pass<2>(crops, alpha, h, w, tiles_x, taps, radius, sums, [](uint32_t a) { return a == 255u ? 0 : a == 0u ? 1 : -1; });
 }
-
-// F^ or B^ of one channel: the normalised sum, the crop's colour where the window saw no pixel of that side
-__device__ __forceinline__ uint32_t normalised(uint32_t n, uint32_t d, uint32_t c) { return d > 0u ? (n + (d >> 1)) / d : c; }
 
 // E of one channel, 0 < a < 255
 __device__ __forceinline__ uint32_t corrected(uint32_t c, uint32_t a, uint32_t fh, uint32_t bh) {
@@ -225,14 +115,14 @@ __device__ __forceinline__ uint32_t corrected(uint32_t c, uint32_t a, uint32_t f
 }
 
 constexpr size_t cols_lds_bytes(int radius) {
-  return (size_t)(kTileH + 2 * radius) * kColPitch * sizeof(uint4) + (2 * kMaxRadius + 1) * sizeof(uint32_t);
+  return (size_t)(kTileH + 2 * radius) * kColPitch * sizeof(uint4) + kTapBytes;
 }
 
 // Rgba: out is (f,h,w) dwords; else (f,h,w,3) bytes over `fill`.
 template <bool Rgba>
 __global__ void __launch_bounds__(kThreads) cutout_cols_kernel(const uint8_t* __restrict__ crops, const uint8_t* __restrict__ alpha,
                                                                const uint4* __restrict__ sums, int h, int w, int tiles_x,
-                                                               uint32_t fill, CutoutTaps taps, int radius, uint8_t* __restrict__ out) {
+                                                               uint32_t fill, Taps taps, int radius, uint8_t* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* col = reinterpret_cast<uint4*>(smem);                                   // (kTileH + 2 r) rows of kColPitch
   uint32_t* tl = reinterpret_cast<uint32_t*>(col + (kTileH + 2 * radius) * kColPitch);
@@ -258,33 +148,9 @@ __global__ void __launch_bounds__(kThreads) cutout_cols_kernel(const uint8_t* __
   uint32_t dn[4][8] = {};
   if (__syncthreads_or(soft)) {          // the same for every lane of the workgroup
     stage_taps(tl, taps, radius);
-    // sums of rows y0 - r .. y0 + nrows + r - 1, all kTileW columns: zero outside the image
-    for (int i = threadIdx.x; i < (nrows + 2 * radius) * 2 * kTileW; i += kThreads) {
-      const int tr = i / (2 * kTileW), q = i - tr * (2 * kTileW);
-      const int y = y0 - radius + tr, sx = x0 + (q >> 1);
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (y >= 0 && y < h && sx < w) v = sums[2 * (((size_t)f * h + y) * w + sx) + (q & 1)];
-      col[tr * kColPitch + q] = v;
-    }
+    stage_cols<2, kTileW, kColPitch>(col, sums, f, h, w, x0, y0, nrows, radius);
     __syncthreads();
-    if (soft) {
-      for (int k = 0; k <= 2 * radius; ++k) {
-        const uint32_t t = tl[k];
-        const uint4* p = col + (r + k) * kColPitch + 8 * g;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint4 vf = p[2 * j], vb = p[2 * j + 1];
-          dn[j][0] += t * vf.x;
-          dn[j][1] += t * vf.y;
-          dn[j][2] += t * vf.z;
-          dn[j][3] += t * vf.w;
-          dn[j][4] += t * vb.x;
-          dn[j][5] += t * vb.y;
-          dn[j][6] += t * vb.z;
-          dn[j][7] += t * vb.w;
-        }
-      }
-    }
+    if (soft) cols_taps<2, kColPitch>(col, tl, radius, r, g, dn);
   }
   if (!mine) return;
 
@@ -316,63 +182,24 @@ __global__ void __launch_bounds__(kThreads) cutout_cols_kernel(const uint8_t* __
   }
 }
 
-bool sizes_ok(int f, int h, int w) { return f >= 0 && f <= 65535 && h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide; }
-
 }  // namespace
 
-extern "C" int fcp_feather_alpha_u8(const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather, uint8_t* alpha,
-                                    fcp_stream_t stream) {
-  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "feather_alpha: bad sizes (f %d, h %d, w %d)", f, h, w);
-  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "feather_alpha: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h,
-              w);
-  FCP_REQUIRE(f <= 65535, "feather_alpha: at most 65535 crops per call (got %d)", f);
-  FCP_REQUIRE(feather == 0 || feather == 3 || feather == 5 || feather == 7, "feather_alpha: feather must be 0, 3, 5 or 7 (got %d)",
-              feather);
-  FCP_REQUIRE((class_bits >> kClasses) == 0, "feather_alpha: class_bits 0x%x names a class at or above %d", class_bits, kClasses);
-  if (f == 0) return 0;
-  FCP_REQUIRE(labels && alpha, "feather_alpha: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  switch (feather) {
-    case 0: launch_alpha<0>(labels, f, h, w, class_bits, alpha, s); break;
-    case 3: launch_alpha<1>(labels, f, h, w, class_bits, alpha, s); break;
-    case 5: launch_alpha<2>(labels, f, h, w, class_bits, alpha, s); break;
-    default: launch_alpha<3>(labels, f, h, w, class_bits, alpha, s); break;
-  }
-  FCP_LAUNCH_OK();
-  return 0;
-}
-
-extern "C" int64_t fcp_cutout_workspace_bytes(int f, int h, int w) {
-  if (!sizes_ok(f, h, w)) return -1;
-  return (int64_t)f * h * w * (int64_t)(2 * sizeof(uint4));
-}
+extern "C" int64_t fcp_cutout_workspace_bytes(int f, int h, int w) { return workspace_bytes(f, h, w, 2 * sizeof(uint4)); }
 
 extern "C" int fcp_cutout_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, int mode, int bg_r, int bg_g, int bg_b,
                              const uint16_t* taps, int radius, uint8_t* out, void* workspace, int64_t workspace_bytes,
                              fcp_stream_t stream) {
-  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "cutout: bad sizes (f %d, h %d, w %d)", f, h, w);
-  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "cutout: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h, w);
-  FCP_REQUIRE(f <= 65535, "cutout: at most 65535 crops per call (got %d)", f);
+  const char* who = "cutout";
+  FCP_CHECK(check_sizes(who, f, h, w));
   FCP_REQUIRE(mode == FCP_CUTOUT_RGBA || mode == FCP_CUTOUT_FILL, "cutout: mode must be %d (RGBA) or %d (fill) (got %d)",
               FCP_CUTOUT_RGBA, FCP_CUTOUT_FILL, mode);
   FCP_REQUIRE(radius == 0 || (radius >= kMinRadius && radius <= kMaxRadius), "cutout: radius must be 0 or %d..%d (got %d)",
               kMinRadius, kMaxRadius, radius);
   FCP_REQUIRE(mode == FCP_CUTOUT_RGBA || radius > 0,
               "cutout: the fill mode needs a radius: without an estimate it is fcp_matte_alpha_u8");
-  FCP_REQUIRE(bg_r >= 0 && bg_r <= 255 && bg_g >= 0 && bg_g <= 255 && bg_b >= 0 && bg_b <= 255,
-              "cutout: fill components must be 0..255 (got %d, %d, %d)", bg_r, bg_g, bg_b);
-  CutoutTaps t = {};
-  if (radius > 0) {
-    FCP_REQUIRE(taps != nullptr, "cutout: null taps");
-    // the 32-bit sums of the kernels hold because of this
-    uint32_t total = 0;
-    for (int k = 0; k <= radius; ++k) {
-      FCP_REQUIRE(taps[k] >= 1, "cutout: tap %d is 0: every tap must be at least 1", k);
-      t.t[k] = taps[k];
-      total += (k == 0 ? 1u : 2u) * taps[k];
-    }
-    FCP_REQUIRE(total == kTapSum, "cutout: the taps must sum to %u over the window (got %u)", kTapSum, total);
-  }
+  FCP_CHECK(check_fill(who, bg_r, bg_g, bg_b));
+  Taps t = {};
+  if (radius > 0) FCP_CHECK(load_taps(who, taps, radius, &t));
   if (f == 0) return 0;
   FCP_REQUIRE(crops && alpha && out, "cutout: null pointer");
   FCP_REQUIRE(mode != FCP_CUTOUT_RGBA || (reinterpret_cast<uintptr_t>(out) & 3) == 0, "cutout: an RGBA out must be 4-byte aligned");
@@ -387,18 +214,14 @@ extern "C" int fcp_cutout_u8(const uint8_t* crops, const uint8_t* alpha, int f, 
     FCP_LAUNCH_OK();
     return 0;
   }
-  const int64_t need = fcp_cutout_workspace_bytes(f, h, w);
-  FCP_REQUIRE(workspace != nullptr && workspace_bytes >= need, "cutout: the workspace needs %lld bytes (got %lld)", (long long)need,
-              (long long)workspace_bytes);
-  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "cutout: the workspace must be 16-byte aligned");
+  FCP_CHECK(check_workspace(who, workspace, workspace_bytes, fcp_cutout_workspace_bytes(f, h, w)));
   uint4* sums = static_cast<uint4*>(workspace);
   const int row_tiles_x = fcp_cdiv(w, kRowTileW), row_tiles_y = fcp_cdiv(h, kRowTileH);
-  hipLaunchKernelGGL(cutout_rows_kernel, dim3(row_tiles_x * row_tiles_y, f), dim3(kThreads),
-                     kRowTileH * kRowPitch * sizeof(uint2) + (2 * kMaxRadius + 1) * sizeof(uint32_t), s, crops, alpha, h, w,
-                     row_tiles_x, t, radius, sums);
+  hipLaunchKernelGGL(cutout_rows_kernel, dim3(row_tiles_x * row_tiles_y, f), dim3(kThreads), rows_lds_bytes<2>(), s, crops, alpha,
+                     h, w, row_tiles_x, t, radius, sums);
   FCP_LAUNCH_OK();
   const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
-  const uint32_t fill = (uint32_t)bg_r | ((uint32_t)bg_g << 8) | ((uint32_t)bg_b << 16);
+  const uint32_t fill = packed_fill(bg_r, bg_g, bg_b);
   if (mode == FCP_CUTOUT_RGBA) {
     hipLaunchKernelGGL((cutout_cols_kernel<true>), dim3(tiles_x * tiles_y, f), dim3(kThreads), cols_lds_bytes(radius), s, crops,
                        alpha, sums, h, w, tiles_x, fill, t, radius, out);

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "fcp_crop_bytes.h"
 
@@ -56,6 +57,17 @@ __device__ __forceinline__ uint32_t mask_of(uint32_t label, uint32_t bits) {
 __device__ __forceinline__ uint32_t over255(uint32_t c, uint32_t a, uint32_t b) {
   const uint32_t u = c * a + b * (255u - a) + 128u;
   return (u + (u >> 8)) >> 8;
+}
+
+// A checked feather (0, 3, 5 or 7) as Tile's R = feather / 2: calls fn(std::integral_constant<int, R>), on the host.
+template <class Fn>
+inline void with_feather(int feather, Fn&& fn) {
+  switch (feather) {
+    case 0: fn(std::integral_constant<int, 0>{}); break;
+    case 3: fn(std::integral_constant<int, 1>{}); break;
+    case 5: fn(std::integral_constant<int, 2>{}); break;
+    default: fn(std::integral_constant<int, 3>{}); break;
+  }
 }
 
 template <int R, int TileW, int TileH>

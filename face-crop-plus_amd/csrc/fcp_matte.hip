@@ -11,6 +11,7 @@
 // feather-0 instantiation once more, a group's four alpha bytes read from the plane where that one reads four labels.
 // Every output byte has one writer and depends on its own crop pixel and on labels only, so out may be the crops
 // themselves and the result is the same from run to run.
+// fcp_feather_alpha_u8 is the alpha plane of fcp_matte_u8 alone (feather_alpha_kernel): the same tile and LDS, no crop.
 //
 // The tile.  LDS per workgroup at r = 3: mask 38 rows x 72 B = 2736 B, H 38 rows x 128 B = 4864 B, 7600 B together: 21
 // workgroups fit the 160 KiB of a CU, so the limit is the 32 wave slots of a CU: 8 workgroups of 4 waves, reached because
@@ -25,12 +26,14 @@
 // of them.
 #include "fcp_common.h"
 #include "fcp_crop_bytes.h"
+#include "fcp_crop_checks.h"
 #include "fcp_feather.h"
 #include "fcp_hip.h"
 
 namespace {
 
 using namespace fcp_crop_bytes;
+using namespace fcp_crop_checks;
 using namespace fcp_feather;
 
 constexpr int kThreads = 256;
@@ -81,53 +84,91 @@ __global__ void __launch_bounds__(kThreads) matte_kernel(const uint8_t* crops, c
   }
 }
 
-template <int R, bool Plane = false>
+// matte_kernel without the composite: the alpha alone (fcp_feather_alpha_u8).  A kernel of its own: as a flag of
+// matte_kernel, or with the tile loop of both in one function, the compiler orders the composite's arithmetic differently
+// and the feather-0 instantiation needs two more registers.
+template <int R>
+__global__ void __launch_bounds__(kThreads) feather_alpha_kernel(const uint8_t* __restrict__ labels, int h, int w, int tiles_x,
+                                                                 uint32_t bits, uint8_t* __restrict__ alpha) {
+  using Feather = Tile<R, kTileW, kTileH>;
+  extern __shared__ uint2 lds[];         // R > 0: the feather's tile; R == 0: none
+  const int f = blockIdx.y;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int x0 = tx * kTileW, y0 = ty * kTileH;
+  const int nrows = min(kTileH, h - y0);
+  const int groups = (min(kTileW, w - x0) + 3) >> 2;
+
+  if constexpr (R > 0) {
+    Feather::stage(lds, labels + (size_t)f * h * w, h, w, x0, y0, nrows, groups, bits, kThreads);
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < nrows * groups; i += kThreads) {
+    const int r = i / groups, g = i - r * groups;
+    const int x = x0 + 4 * g;
+    const int npx = min(4, w - x);
+    const size_t pixel = ((size_t)f * h + (y0 + r)) * w + x;
+    uint32_t a[4];
+    Feather::alpha(lds, r, g, labels + pixel, npx, bits, a);
+    store_u8(alpha + pixel, npx, a);
+  }
+}
+
+// Composite false: feather_alpha_kernel, which takes labels, bits and alpha only.
+template <int R, bool Plane = false, bool Composite = true>
 void launch(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t bits, uint32_t fill, uint8_t* out,
             uint8_t* alpha, hipStream_t stream) {
   const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
   constexpr size_t lds = Tile<R, kTileW, kTileH>::kBytes;
-  hipLaunchKernelGGL((matte_kernel<R, Plane>), dim3(tiles_x * tiles_y, f), dim3(kThreads), lds, stream, crops, labels, h, w,
-                     tiles_x, bits, fill, out, alpha);
+  const dim3 grid(tiles_x * tiles_y, f);
+  if constexpr (Composite) {
+    hipLaunchKernelGGL((matte_kernel<R, Plane>), grid, dim3(kThreads), lds, stream, crops, labels, h, w, tiles_x, bits, fill, out,
+                       alpha);
+  } else {
+    hipLaunchKernelGGL(feather_alpha_kernel<R>, grid, dim3(kThreads), lds, stream, labels, h, w, tiles_x, bits, alpha);
+  }
 }
 
 }  // namespace
 
 extern "C" int fcp_matte_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather,
                             int bg_r, int bg_g, int bg_b, uint8_t* out, uint8_t* alpha, fcp_stream_t stream) {
-  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "matte: bad sizes (f %d, h %d, w %d)", f, h, w);
-  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "matte: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h, w);
-  FCP_REQUIRE(f <= 65535, "matte: at most 65535 crops per call (got %d)", f);
-  FCP_REQUIRE(feather == 0 || feather == 3 || feather == 5 || feather == 7, "matte: feather must be 0, 3, 5 or 7 (got %d)",
-              feather);
-  FCP_REQUIRE(bg_r >= 0 && bg_r <= 255 && bg_g >= 0 && bg_g <= 255 && bg_b >= 0 && bg_b <= 255,
-              "matte: fill components must be 0..255 (got %d, %d, %d)", bg_r, bg_g, bg_b);
-  FCP_REQUIRE((class_bits >> kClasses) == 0, "matte: class_bits 0x%x names a class at or above %d", class_bits, kClasses);
+  const char* who = "matte";
+  FCP_CHECK(check_sizes(who, f, h, w));
+  FCP_CHECK(check_feather(who, feather));
+  FCP_CHECK(check_fill(who, bg_r, bg_g, bg_b));
+  FCP_CHECK(check_class_bits(who, class_bits));
   if (f == 0) return 0;
-  FCP_REQUIRE(crops && labels && out, "matte: null pointer");
-  const uint32_t fill = (uint32_t)bg_r | ((uint32_t)bg_g << 8) | ((uint32_t)bg_b << 16);
-  hipStream_t s = (hipStream_t)stream;
-  switch (feather) {
-    case 0: launch<0>(crops, labels, f, h, w, class_bits, fill, out, alpha, s); break;
-    case 3: launch<1>(crops, labels, f, h, w, class_bits, fill, out, alpha, s); break;
-    case 5: launch<2>(crops, labels, f, h, w, class_bits, fill, out, alpha, s); break;
-    default: launch<3>(crops, labels, f, h, w, class_bits, fill, out, alpha, s); break;
-  }
+  FCP_REQUIRE(crops && labels && out, "%s: null pointer", who);
+  with_feather(feather, [&](auto r) {
+    launch<decltype(r)::value>(crops, labels, f, h, w, class_bits, packed_fill(bg_r, bg_g, bg_b), out, alpha, (hipStream_t)stream);
+  });
   FCP_LAUNCH_OK();
   return 0;
 }
 
 extern "C" int fcp_matte_alpha_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, int bg_r, int bg_g, int bg_b,
                                   uint8_t* out, fcp_stream_t stream) {
-  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "matte_alpha: bad sizes (f %d, h %d, w %d)", f, h, w);
-  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "matte_alpha: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h,
-              w);
-  FCP_REQUIRE(f <= 65535, "matte_alpha: at most 65535 crops per call (got %d)", f);
-  FCP_REQUIRE(bg_r >= 0 && bg_r <= 255 && bg_g >= 0 && bg_g <= 255 && bg_b >= 0 && bg_b <= 255,
-              "matte_alpha: fill components must be 0..255 (got %d, %d, %d)", bg_r, bg_g, bg_b);
+  const char* who = "matte_alpha";
+  FCP_CHECK(check_sizes(who, f, h, w));
+  FCP_CHECK(check_fill(who, bg_r, bg_g, bg_b));
   if (f == 0) return 0;
-  FCP_REQUIRE(crops && alpha && out, "matte_alpha: null pointer");
-  const uint32_t fill = (uint32_t)bg_r | ((uint32_t)bg_g << 8) | ((uint32_t)bg_b << 16);
-  launch<0, true>(crops, alpha, f, h, w, 0u, fill, out, nullptr, (hipStream_t)stream);
+  FCP_REQUIRE(crops && alpha && out, "%s: null pointer", who);
+  launch<0, true>(crops, alpha, f, h, w, 0u, packed_fill(bg_r, bg_g, bg_b), out, nullptr, (hipStream_t)stream);
+  FCP_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int fcp_feather_alpha_u8(const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather, uint8_t* alpha,
+                                    fcp_stream_t stream) {
+  const char* who = "feather_alpha";
+  FCP_CHECK(check_sizes(who, f, h, w));
+  FCP_CHECK(check_feather(who, feather));
+  FCP_CHECK(check_class_bits(who, class_bits));
+  if (f == 0) return 0;
+  FCP_REQUIRE(labels && alpha, "%s: null pointer", who);
+  with_feather(feather, [&](auto r) {
+    launch<decltype(r)::value, false, false>(nullptr, labels, f, h, w, class_bits, 0u, nullptr, alpha, (hipStream_t)stream);
+  });
   FCP_LAUNCH_OK();
   return 0;
 }

@@ -4,32 +4,22 @@
 //
 //   m, alpha  = the mask and the feathered alpha of fcp_feather.h (feather 0, 3, 5, 7): those of fcp_matte_u8
 //   b(y,x)    = 1 where m == 0, else 0                                                          from the HARD mask
-//   t[0..r]   : all >= 1, t[0] + 2 sum(t[1..r]) == 4096, 3 <= r <= 48; made on the host from sigma, data here
-//   D(y,x)    = sum_j sum_i t|j| t|i| b(y+j, x+i)                                               taps inside the image only
-//   N_ch(y,x) = sum_j sum_i t|j| t|i| b(y+j, x+i) c_ch(y+j, x+i)                                the same taps
-//   B_ch(y,x) = D > 0 ? (N_ch + D / 2) / D : c_ch(y,x)                                          integer division
+//   t, D, N, B: the mask-normalised Gaussian of fcp_masked_blur.h with the one side b; its 32-bit bounds are stated there
 //   out_ch    = (c_ch alpha + B_ch (255 - alpha) + 127) / 255                                   fcp_feather.h's over255
 //
-// Positions outside the image contribute to neither N nor D: the normalisation is the border rule.  Bounds, all in
-// unsigned 32 bits: a horizontal sum is at most 255 * 4096 < 2^20; N <= 255 * 4096^2 = 4 278 190 080 < 2^32 and
-// N + D / 2 <= 4 286 578 688 < 2^32, only just, which is why the entry point refuses taps that do not sum to 4096;
-// N <= 255 D, so B <= 255.  alpha < 255 needs a hard-background pixel within Chebyshev distance 3 inside the image
-// (reflect-101 revisits in-image pixels only), every tap is >= 1 and r >= 3, so D > 0 wherever B shows; the D == 0
-// branch only defines the bytes nobody sees.
+// alpha < 255 needs a hard-background pixel within Chebyshev distance 3 inside the image (reflect-101 revisits in-image
+// pixels only), every tap is >= 1 and r >= 3, so D > 0 wherever B shows; the D == 0 branch only defines the bytes nobody
+// sees.
 //
 // Two launches and a workspace of 16 bytes per pixel (the caller's: nothing is allocated here).
 //
-//   blur_rows_kernel, workgroups of 256 lanes over (4 rows x 256 columns, face).  A workgroup stages one dword per pixel
-//   of its rows and an r-pixel margin, (b, b c_r, b c_g, b c_b) as four bytes, zero for a subject pixel and for a
-//   position outside the image, so the border rule and the indicator cost nothing in the loop; then a lane per output
-//   pixel runs the 2 r + 1 taps over consecutive dwords (consecutive lanes, consecutive banks) and stores the four sums
-//   (H_b, H_r, H_g, H_b') as one 16-byte store.  LDS per workgroup: 4 x (256 + 96) x 4 B + 97 taps x 4 B = 6020 B (the
-//   tap table is mirrored to 2 r + 1 entries, so the loop has no |k|).  27 workgroups would fit the 160 KiB of a CU; the
-//   32 wave slots allow 8.
+//   blur_rows_kernel, workgroups of 256 lanes over (4 rows x 256 columns, face): fcp_masked_blur.h's rows_pass, one dword
+//   per staged pixel.  LDS per workgroup: 4 x (256 + 96) x 4 B + 97 taps x 4 B = 6020 B.  27 workgroups would fit the
+//   160 KiB of a CU; the 32 wave slots allow 8.
 //
 //   blur_cols_kernel, workgroups of 256 lanes over (64 rows x 16 columns, face), four pixels of a row per lane.  A
-//   workgroup stages the 16-byte sums of its columns for rows y0 - r .. y0 + 63 + r (zero outside the image), and the
-//   feather's tile (fcp_feather.h: Tile::stage); then a lane runs the 2 r + 1 taps down its four columns (four 16-byte
+//   workgroup stages the 16-byte sums of its columns for rows y0 - r .. y0 + 63 + r (fcp_masked_blur.h: stage_cols), and the
+//   feather's tile (fcp_feather.h: Tile::stage); then a lane runs the 2 r + 1 taps down its four columns (cols_taps: four 16-byte
 //   LDS reads per tap, 16 accumulators), divides, runs the feather's vertical pass, reads the 12 crop bytes of its
 //   group, composites and writes out (and alpha) once.  LDS per workgroup at r = 48 and feather 7:
 //   160 x 16 x 16 B = 40960 B of sums + 70 x 32 B + 70 x 24 B of feather + 388 B of taps = 45268 B: 3 workgroups per CU
@@ -50,86 +40,32 @@
 // and no dword is read that does not hold a byte of them.
 #include "fcp_common.h"
 #include "fcp_crop_bytes.h"
+#include "fcp_crop_checks.h"
 #include "fcp_feather.h"
 #include "fcp_hip.h"
+#include "fcp_masked_blur.h"
 
 namespace {
 
 using namespace fcp_crop_bytes;
+using namespace fcp_crop_checks;
 using namespace fcp_feather;
-
-constexpr int kThreads = 256;
-constexpr int kMinRadius = 3;
-constexpr int kMaxRadius = 48;
-constexpr uint32_t kTapSum = 4096;
-
-// rows pass
-constexpr int kRowTileW = 256;
-constexpr int kRowTileH = 4;
-constexpr int kRowPitch = kRowTileW + 2 * kMaxRadius;   // dwords of a staged row
+using namespace fcp_masked_blur;
 
 // columns pass
 constexpr int kTileW = 16;              // output pixels of a tile row: 4 groups of four
 constexpr int kTileH = 64;
 
-struct BlurTaps {
-  uint16_t t[kMaxRadius + 1];           // 49 x 16 bit in the kernel argument block
-};
-
-// the mirrored tap table, 2 r + 1 dwords: entry k is t|k - r|
-__device__ __forceinline__ void stage_taps(uint32_t* tl, const BlurTaps& taps, int radius) {
-  const int k = threadIdx.x;
-  if (k <= 2 * radius) tl[k] = taps.t[k < radius ? radius - k : k - radius];
-}
-
 __global__ void __launch_bounds__(kThreads) blur_rows_kernel(const uint8_t* __restrict__ crops, const uint8_t* __restrict__ labels,
-                                                             int h, int w, int tiles_x, uint32_t bits, BlurTaps taps, int radius,
+                                                             int h, int w, int tiles_x, uint32_t bits, Taps taps, int radius,
                                                              uint4* __restrict__ sums) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  uint32_t* stage = reinterpret_cast<uint32_t*>(smem);   // kRowTileH rows of kRowPitch dwords
-  uint32_t* tl = stage + kRowTileH * kRowPitch;
-  const int f = blockIdx.y;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int x0 = tx * kRowTileW, y0 = ty * kRowTileH;
-  const int nrows = min(kRowTileH, h - y0), ncols = min(kRowTileW, w - x0);
-  const int span = ncols + 2 * radius;
-
-  stage_taps(tl, taps, radius);
-  for (int i = threadIdx.x; i < nrows * span; i += kThreads) {
-    const int tr = i / span, d = i - tr * span;
-    const int x = x0 - radius + d;
-    uint32_t v = 0;
-    if (x >= 0 && x < w) {
-      const size_t pixel = ((size_t)f * h + (y0 + tr)) * w + x;
-      if (mask_of(labels[pixel], bits) == 0u) {
-        const uint8_t* c = crops + pixel * 3;
-        v = 1u | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16) | ((uint32_t)c[2] << 24);
-      }
-    }
-    stage[tr * kRowPitch + d] = v;
-  }
-  __syncthreads();
-
-  for (int i = threadIdx.x; i < nrows * ncols; i += kThreads) {
-    const int tr = i / ncols, cx = i - tr * ncols;
-    const uint32_t* s = stage + tr * kRowPitch + cx;   // output x sums staged x .. x + 2 r
-    uint32_t a0 = 0u, a1 = 0u, a2 = 0u, a3 = 0u;        // each <= 255 * 4096
-    for (int k = 0; k <= 2 * radius; ++k) {
-      const uint32_t v = s[k], t = tl[k];
-      a0 += t * (v & 255u);
-      a1 += t * ((v >> 8) & 255u);
-      a2 += t * ((v >> 16) & 255u);
-      a3 += t * (v >> 24);
-    }
-    sums[((size_t)f * h + (y0 + tr)) * w + (x0 + cx)] = make_uint4(a0, a1, a2, a3);
-  }
+  rows_pass<1>(crops, labels, h, w, tiles_x, taps, radius, sums, [bits](uint32_t l) { return mask_of(l, bits) == 0u ? 0 : -1; });
 }
 
 // Bytes of dynamic LDS of blur_cols_kernel<R>: the sums, the feather's tile, the taps.
 template <int R>
 constexpr size_t cols_lds_bytes(int radius) {
-  return (size_t)(kTileH + 2 * radius) * kTileW * sizeof(uint4) + Tile<R, kTileW, kTileH>::kBytes +
-         (2 * kMaxRadius + 1) * sizeof(uint32_t);
+  return (size_t)(kTileH + 2 * radius) * kTileW * sizeof(uint4) + Tile<R, kTileW, kTileH>::kBytes + kTapBytes;
 }
 
 // crops and out may be the same array: neither is __restrict__.  Plane (with R == 0, fcp_matte_blur_alpha_u8): labels is an
@@ -137,7 +73,7 @@ constexpr size_t cols_lds_bytes(int radius) {
 template <int R, bool Plane = false>
 __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crops, const uint8_t* __restrict__ labels,
                                                              const uint4* __restrict__ sums, int h, int w, int tiles_x,
-                                                             uint32_t bits, BlurTaps taps, int radius, uint8_t* out,
+                                                             uint32_t bits, Taps taps, int radius, uint8_t* out,
                                                              uint8_t* alpha) {
   static_assert(!Plane || R == 0, "a given alpha has no feather");
   using Feather = Tile<R, kTileW, kTileH>;
@@ -152,14 +88,7 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
   const int groups = (min(kTileW, w - x0) + 3) >> 2;
 
   stage_taps(tl, taps, radius);
-  // sums of rows y0 - r .. y0 + nrows + r - 1, all kTileW columns: zero outside the image
-  for (int i = threadIdx.x; i < (nrows + 2 * radius) * kTileW; i += kThreads) {
-    const int tr = i / kTileW, c = i - tr * kTileW;
-    const int y = y0 - radius + tr, x = x0 + c;
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (y >= 0 && y < h && x < w) v = sums[((size_t)f * h + y) * w + x];
-    col[i] = v;
-  }
+  stage_cols<1, kTileW, kTileW>(col, sums, f, h, w, x0, y0, nrows, radius);
   if constexpr (R > 0) Feather::stage(hsum, labels + (size_t)f * h * w, h, w, x0, y0, nrows, groups, bits, kThreads);
   __syncthreads();
 
@@ -169,20 +98,8 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
     const int npx = min(4, w - x);
     const size_t pixel = ((size_t)f * h + y) * w + x;
 
-    // D and N of the four pixels: N + D / 2 < 2^32
     uint32_t dn[4][4] = {};
-    for (int k = 0; k <= 2 * radius; ++k) {
-      const uint32_t t = tl[k];
-      const uint4* p = col + (r + k) * kTileW + 4 * g;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint4 v = p[j];
-        dn[j][0] += t * v.x;
-        dn[j][1] += t * v.y;
-        dn[j][2] += t * v.z;
-        dn[j][3] += t * v.w;
-      }
-    }
+    cols_taps<1, kTileW>(col, tl, radius, r, g, dn);
 
     uint32_t a[4];
     if constexpr (Plane) {
@@ -198,9 +115,7 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
 #pragma unroll
     for (int k = 0; k < 12; ++k) {            // byte k of the group: pixel k / 3, channel k % 3
       const uint32_t cv = (c[k >> 2] >> (8 * (k & 3))) & 255u;
-      const uint32_t dd = dn[k / 3][0];
-      const uint32_t bv = dd > 0u ? (dn[k / 3][1 + k % 3] + (dd >> 1)) / dd : cv;
-      o[k >> 2] |= over255(cv, a[k / 3], bv) << (8 * (k & 3));
+      o[k >> 2] |= over255(cv, a[k / 3], normalised(dn[k / 3][1 + k % 3], dn[k / 3][0], cv)) << (8 * (k & 3));
     }
     store_rgb(out + pixel * 3, npx, o);
   }
@@ -208,7 +123,7 @@ __global__ void __launch_bounds__(kThreads) blur_cols_kernel(const uint8_t* crop
 
 template <int R, bool Plane = false>
 void launch_cols(const uint8_t* crops, const uint8_t* labels, const uint4* sums, int f, int h, int w, uint32_t bits,
-                 const BlurTaps& taps, int radius, uint8_t* out, uint8_t* alpha, hipStream_t stream) {
+                 const Taps& taps, int radius, uint8_t* out, uint8_t* alpha, hipStream_t stream) {
   const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
   hipLaunchKernelGGL((blur_cols_kernel<R, Plane>), dim3(tiles_x * tiles_y, f), dim3(kThreads), cols_lds_bytes<R>(radius), stream,
                      crops, labels, sums, h, w, tiles_x, bits, taps, radius, out, alpha);
@@ -216,10 +131,7 @@ void launch_cols(const uint8_t* crops, const uint8_t* labels, const uint4* sums,
 
 }  // namespace
 
-extern "C" int64_t fcp_matte_blur_workspace_bytes(int f, int h, int w) {
-  if (f < 0 || f > 65535 || h < 1 || w < 1 || h > kMaxSide || w > kMaxSide) return -1;
-  return (int64_t)f * h * w * (int64_t)sizeof(uint4);
-}
+extern "C" int64_t fcp_matte_blur_workspace_bytes(int f, int h, int w) { return workspace_bytes(f, h, w, sizeof(uint4)); }
 
 namespace {
 
@@ -228,46 +140,28 @@ namespace {
 int matte_blur(const char* who, const uint8_t* crops, const uint8_t* labels, const uint8_t* alpha_in, bool given, int f, int h, int w,
                uint32_t class_bits, int feather, const uint16_t* taps, int radius, uint8_t* out, uint8_t* alpha, void* workspace,
                int64_t workspace_bytes, fcp_stream_t stream) {
-  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "%s: bad sizes (f %d, h %d, w %d)", who, f, h, w);
-  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "%s: crops of at most %d x %d px (got h %d, w %d)", who, kMaxSide, kMaxSide, h, w);
-  FCP_REQUIRE(f <= 65535, "%s: at most 65535 crops per call (got %d)", who, f);
-  FCP_REQUIRE(feather == 0 || feather == 3 || feather == 5 || feather == 7, "%s: feather must be 0, 3, 5 or 7 (got %d)", who,
-              feather);
-  FCP_REQUIRE((class_bits >> kClasses) == 0, "%s: class_bits 0x%x names a class at or above %d", who, class_bits, kClasses);
+  FCP_CHECK(check_sizes(who, f, h, w));
+  FCP_CHECK(check_feather(who, feather));
+  FCP_CHECK(check_class_bits(who, class_bits));
   FCP_REQUIRE(radius >= kMinRadius && radius <= kMaxRadius, "%s: radius must be %d..%d (got %d)", who, kMinRadius, kMaxRadius,
               radius);
-  FCP_REQUIRE(taps != nullptr, "%s: null taps", who);
-  // the 32-bit sums of the kernels hold because of this
-  BlurTaps t = {};
-  uint32_t total = 0;
-  for (int k = 0; k <= radius; ++k) {
-    FCP_REQUIRE(taps[k] >= 1, "%s: tap %d is 0: every tap must be at least 1", who, k);
-    t.t[k] = taps[k];
-    total += (k == 0 ? 1u : 2u) * taps[k];
-  }
-  FCP_REQUIRE(total == kTapSum, "%s: the taps must sum to %u over the window (got %u)", who, kTapSum, total);
+  Taps t = {};
+  FCP_CHECK(load_taps(who, taps, radius, &t));
   if (f == 0) return 0;
   FCP_REQUIRE(crops && labels && out && (!given || alpha_in), "%s: null pointer", who);
-  const int64_t need = fcp_matte_blur_workspace_bytes(f, h, w);
-  FCP_REQUIRE(workspace != nullptr && workspace_bytes >= need, "%s: the workspace needs %lld bytes (got %lld)", who,
-              (long long)need, (long long)workspace_bytes);
-  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+  FCP_CHECK(check_workspace(who, workspace, workspace_bytes, fcp_matte_blur_workspace_bytes(f, h, w)));
   hipStream_t s = (hipStream_t)stream;
   uint4* sums = static_cast<uint4*>(workspace);
   const int row_tiles_x = fcp_cdiv(w, kRowTileW), row_tiles_y = fcp_cdiv(h, kRowTileH);
-  hipLaunchKernelGGL(blur_rows_kernel, dim3(row_tiles_x * row_tiles_y, f), dim3(kThreads),
-                     (kRowTileH * kRowPitch + 2 * kMaxRadius + 1) * sizeof(uint32_t), s, crops, labels, h, w, row_tiles_x,
-                     class_bits, t, radius, sums);
+  hipLaunchKernelGGL(blur_rows_kernel, dim3(row_tiles_x * row_tiles_y, f), dim3(kThreads), rows_lds_bytes<1>(), s, crops, labels, h,
+                     w, row_tiles_x, class_bits, t, radius, sums);
   FCP_LAUNCH_OK();
   if (given) {
     launch_cols<0, true>(crops, alpha_in, sums, f, h, w, class_bits, t, radius, out, nullptr, s);
   } else {
-    switch (feather) {
-      case 0: launch_cols<0>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
-      case 3: launch_cols<1>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
-      case 5: launch_cols<2>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
-      default: launch_cols<3>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s); break;
-    }
+    with_feather(feather, [&](auto r) {
+      launch_cols<decltype(r)::value>(crops, labels, sums, f, h, w, class_bits, t, radius, out, alpha, s);
+    });
   }
   FCP_LAUNCH_OK();
   return 0;

@@ -54,11 +54,13 @@
 // The composite that goes with it is in fcp_matte.hip (fcp_matte_alpha_u8) and fcp_matte_blur.hip
 // (fcp_matte_blur_alpha_u8): the same kernels with the alpha read from a plane.
 #include "fcp_common.h"
+#include "fcp_crop_checks.h"
 #include "fcp_feather.h"
 #include "fcp_hip.h"
 
 namespace {
 
+using namespace fcp_crop_checks;
 using namespace fcp_feather;
 
 constexpr int kThreads = 256;
@@ -288,27 +290,19 @@ __global__ void __launch_bounds__(kThreads) refine_alpha_kernel(const uint8_t* _
 
 }  // namespace
 
-extern "C" int64_t fcp_matte_refine_workspace_bytes(int f, int h, int w) {
-  if (f < 0 || f > 65535 || h < 1 || w < 1 || h > kMaxSide || w > kMaxSide) return -1;
-  return (int64_t)f * h * w * (int64_t)sizeof(int2);
-}
+extern "C" int64_t fcp_matte_refine_workspace_bytes(int f, int h, int w) { return workspace_bytes(f, h, w, sizeof(int2)); }
 
 extern "C" int fcp_matte_refine_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int radius,
                                    int eps, uint8_t* alpha_out, void* workspace, int64_t workspace_bytes, fcp_stream_t stream) {
-  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "matte_refine: bad sizes (f %d, h %d, w %d)", f, h, w);
-  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "matte_refine: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h,
-              w);
-  FCP_REQUIRE(f <= 65535, "matte_refine: at most 65535 crops per call (got %d)", f);
+  const char* who = "matte_refine";
+  FCP_CHECK(check_sizes(who, f, h, w));
   FCP_REQUIRE(radius >= kMinRadius && radius <= kMaxRadius, "matte_refine: radius must be %d..%d (got %d)", kMinRadius, kMaxRadius,
               radius);
   FCP_REQUIRE(eps >= 1 && eps <= kMaxEps, "matte_refine: eps must be 1..%d (got %d)", kMaxEps, eps);
-  FCP_REQUIRE((class_bits >> kClasses) == 0, "matte_refine: class_bits 0x%x names a class at or above %d", class_bits, kClasses);
+  FCP_CHECK(check_class_bits(who, class_bits));
   if (f == 0) return 0;
   FCP_REQUIRE(crops && labels && alpha_out, "matte_refine: null pointer");
-  const int64_t need = fcp_matte_refine_workspace_bytes(f, h, w);
-  FCP_REQUIRE(workspace != nullptr && workspace_bytes >= need, "matte_refine: the workspace needs %lld bytes (got %lld)",
-              (long long)need, (long long)workspace_bytes);
-  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "matte_refine: the workspace must be 16-byte aligned");
+  FCP_CHECK(check_workspace(who, workspace, workspace_bytes, fcp_matte_refine_workspace_bytes(f, h, w)));
   hipStream_t s = (hipStream_t)stream;
   int2* ab = static_cast<int2*>(workspace);
   const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);

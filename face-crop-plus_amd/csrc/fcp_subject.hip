@@ -55,11 +55,13 @@
 // No loop waits for another lane or workgroup; every loop below names the integer that bounds it.  labels and out may
 // start at any byte (they are read and written as bytes); no byte outside out and the workspace is written.
 #include "fcp_common.h"
+#include "fcp_crop_checks.h"
 #include "fcp_feather.h"
 #include "fcp_hip.h"
 
 namespace {
 
+using namespace fcp_crop_checks;
 using namespace fcp_feather;
 
 constexpr int kThreads = 256;
@@ -344,26 +346,18 @@ int label_pass(const uint8_t* src, int f, int h, int w, uint32_t bits, int* L, i
 
 }  // namespace
 
-extern "C" int64_t fcp_subject_mask_workspace_bytes(int f, int h, int w) {
-  if (f < 0 || f > 65535 || h < 1 || w < 1 || h > kMaxSide || w > kMaxSide) return -1;
-  return (int64_t)f * h * w * kPlanes * (int64_t)sizeof(int);
-}
+extern "C" int64_t fcp_subject_mask_workspace_bytes(int f, int h, int w) { return workspace_bytes(f, h, w, kPlanes * sizeof(int)); }
 
 extern "C" int fcp_subject_mask_u8(const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int keep_largest, int max_hole,
                                    uint8_t* out, void* workspace, int64_t workspace_bytes, fcp_stream_t stream) {
-  FCP_REQUIRE(f >= 0 && h >= 1 && w >= 1, "subject_mask: bad sizes (f %d, h %d, w %d)", f, h, w);
-  FCP_REQUIRE(h <= kMaxSide && w <= kMaxSide, "subject_mask: crops of at most %d x %d px (got h %d, w %d)", kMaxSide, kMaxSide, h,
-              w);
-  FCP_REQUIRE(f <= 65535, "subject_mask: at most 65535 crops per call (got %d)", f);
-  FCP_REQUIRE((class_bits >> kClasses) == 0, "subject_mask: class_bits 0x%x names a class at or above %d", class_bits, kClasses);
+  const char* who = "subject_mask";
+  FCP_CHECK(check_sizes(who, f, h, w));
+  FCP_CHECK(check_class_bits(who, class_bits));
   FCP_REQUIRE(keep_largest == 0 || keep_largest == 1, "subject_mask: keep_largest must be 0 or 1 (got %d)", keep_largest);
   FCP_REQUIRE(max_hole >= 0 && max_hole <= kMaxHole, "subject_mask: max_hole must be 0..%d (got %d)", kMaxHole, max_hole);
   if (f == 0) return 0;
   FCP_REQUIRE(labels && out, "subject_mask: null pointer");
-  const int64_t need = fcp_subject_mask_workspace_bytes(f, h, w);
-  FCP_REQUIRE(workspace != nullptr && workspace_bytes >= need, "subject_mask: the workspace needs %lld bytes (got %lld)",
-              (long long)need, (long long)workspace_bytes);
-  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "subject_mask: the workspace must be 16-byte aligned");
+  FCP_CHECK(check_workspace(who, workspace, workspace_bytes, fcp_subject_mask_workspace_bytes(f, h, w)));
   hipStream_t s = (hipStream_t)stream;
   const size_t plane = (size_t)f * h * w;
   int* L = static_cast<int*>(workspace);

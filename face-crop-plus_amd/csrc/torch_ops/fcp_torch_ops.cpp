@@ -512,6 +512,40 @@ std::tuple<Tensor, Tensor> png_huffman_lengths(const Tensor& freq, bool with_cod
   return {lengths, codes};
 }
 
+// The shape checks the matte family shares: crops (f,h,w,3) and a plane (f,h,w) of its own, both uint8 on one device.
+static void crops_and_plane(const Tensor& crops, const Tensor& plane, const char* name, int64_t& f, int64_t& h, int64_t& w) {
+  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
+  f = crops.size(0), h = crops.size(1), w = crops.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
+  TORCH_CHECK(plane.get_device() == crops.get_device() && plane.dim() == 3 && plane.size(0) == f && plane.size(1) == h &&
+                  plane.size(2) == w, name, " must be (", f, ",", h, ",", w, ") uint8 on the device of the crops");
+}
+
+// The same for the ops that take label maps (f,h,w) uint8 alone.
+static void labels_plane(const Tensor& labels, int64_t class_bits, int64_t& f, int64_t& h, int64_t& w) {
+  TORCH_CHECK(labels.dim() == 3, "labels (f,h,w) uint8");
+  f = labels.size(0), h = labels.size(1), w = labels.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "labels (f,h,w): sizes past int");
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+}
+
+// taps = t[0..radius] of the op `name` as the 16-bit table of the C ABI; returns the radius (0 for the empty list that
+// `allow_empty` lets through).
+static int taps16(const char* name, at::IntArrayRef taps, bool allow_empty, uint16_t (&t16)[49]) {
+  const int64_t radius = (int64_t)taps.size() - 1;
+  TORCH_CHECK((allow_empty && taps.empty()) || (radius >= 3 && radius <= 48), name, ": taps must be ", allow_empty ? "empty or " : "",
+              "t[0..radius] with radius 3..48 (got ", taps.size(), " taps)");
+  for (int64_t k = 0; k <= radius; ++k) {
+    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, name, ": tap ", k, " past 16 bits");
+    t16[k] = (uint16_t)taps[k];
+  }
+  return taps.empty() ? 0 : (int)radius;
+}
+
+// The workspace of a call: `need` bytes (an fcp_*_workspace_bytes; negative for sizes the entry point refuses) from the
+// caching allocator, on the device of `like` (uint8).
+static Tensor workspace(int64_t need, const Tensor& like) { return at::empty({need < 0 ? 0 : need}, like.options()); }
+
 // Crops (f,h,w,3) uint8 over a uniform fill through the soft mask of their label maps (f,h,w) uint8: the composited
 // crops and, with `with_alpha`, the alpha (f,h,w) uint8 (else an empty tensor) (fcp_matte_u8).
 std::tuple<Tensor, Tensor> matte(const Tensor& crops, const Tensor& labels, int64_t class_bits, int64_t feather, int64_t bg_r,
@@ -519,11 +553,8 @@ std::tuple<Tensor, Tensor> matte(const Tensor& crops, const Tensor& labels, int6
   dev(crops, "crops", at::kByte);
   dev(labels, "labels", at::kByte);
   FCP_DEVICE_GUARD(crops);
-  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
-  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2);
-  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
-  TORCH_CHECK(labels.get_device() == crops.get_device() && labels.dim() == 3 && labels.size(0) == f && labels.size(1) == h &&
-                  labels.size(2) == w, "labels must be (", f, ",", h, ",", w, ") uint8 on the device of the crops");
+  int64_t f, h, w;
+  crops_and_plane(crops, labels, "labels", f, h, w);
   TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
   for (int64_t v : {feather, bg_r, bg_g, bg_b}) TORCH_CHECK(v >= INT_MIN && v <= INT_MAX, "feather / fill past int");
   Tensor out = at::empty_like(crops);
@@ -543,38 +574,20 @@ std::tuple<Tensor, Tensor> matte_blur(const Tensor& crops, const Tensor& labels,
   dev(crops, "crops", at::kByte);
   dev(labels, "labels", at::kByte);
   FCP_DEVICE_GUARD(crops);
-  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
-  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2);
-  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
-  TORCH_CHECK(labels.get_device() == crops.get_device() && labels.dim() == 3 && labels.size(0) == f && labels.size(1) == h &&
-                  labels.size(2) == w, "labels must be (", f, ",", h, ",", w, ") uint8 on the device of the crops");
+  int64_t f, h, w;
+  crops_and_plane(crops, labels, "labels", f, h, w);
   TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
   TORCH_CHECK(feather >= INT_MIN && feather <= INT_MAX, "feather past int");
-  const int64_t radius = (int64_t)taps.size() - 1;
-  TORCH_CHECK(radius >= 3 && radius <= 48, "matte_blur: taps must be t[0..radius] with radius 3..48 (got ", taps.size(), " taps)");
   uint16_t t16[49];
-  for (int64_t k = 0; k <= radius; ++k) {
-    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, "matte_blur: tap ", k, " past 16 bits");
-    t16[k] = (uint16_t)taps[k];
-  }
+  const int radius = taps16("matte_blur", taps, false, t16);
   Tensor out = at::empty_like(crops);
   Tensor alpha = with_alpha ? at::empty({f, h, w}, crops.options()) : at::empty({0}, crops.options());
-  const int64_t need = fcp_matte_blur_workspace_bytes((int)f, (int)h, (int)w);
-  Tensor work = at::empty({need < 0 ? 0 : need}, crops.options());
+  Tensor work = workspace(fcp_matte_blur_workspace_bytes((int)f, (int)h, (int)w), crops);
   ok(fcp_matte_blur_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits,
-                       (int)feather, t16, (int)radius, out.data_ptr<uint8_t>(), with_alpha ? alpha.data_ptr<uint8_t>() : nullptr,
+                       (int)feather, t16, radius, out.data_ptr<uint8_t>(), with_alpha ? alpha.data_ptr<uint8_t>() : nullptr,
                        work.data_ptr(), work.numel(), cur_stream()),
      "fcp::matte_blur");
   return {out, alpha};
-}
-
-// The shape checks the matte family shares: crops (f,h,w,3) and a plane (f,h,w) of its own, both uint8 on one device.
-static void crops_and_plane(const Tensor& crops, const Tensor& plane, const char* name, int64_t& f, int64_t& h, int64_t& w) {
-  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
-  f = crops.size(0), h = crops.size(1), w = crops.size(2);
-  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
-  TORCH_CHECK(plane.get_device() == crops.get_device() && plane.dim() == 3 && plane.size(0) == f && plane.size(1) == h &&
-                  plane.size(2) == w, name, " must be (", f, ",", h, ",", w, ") uint8 on the device of the crops");
 }
 
 // The guided-filter alpha (f,h,w) uint8 of crops (f,h,w,3) uint8 and their label maps (f,h,w) uint8
@@ -588,8 +601,7 @@ Tensor matte_refine(const Tensor& crops, const Tensor& labels, int64_t class_bit
   TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
   for (int64_t v : {radius, eps}) TORCH_CHECK(v >= INT_MIN && v <= INT_MAX, "radius / eps past int");
   Tensor alpha = at::empty({f, h, w}, crops.options());
-  const int64_t need = fcp_matte_refine_workspace_bytes((int)f, (int)h, (int)w);
-  Tensor work = at::empty({need < 0 ? 0 : need}, crops.options());
+  Tensor work = workspace(fcp_matte_refine_workspace_bytes((int)f, (int)h, (int)w), crops);
   ok(fcp_matte_refine_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits,
                          (int)radius, (int)eps, alpha.data_ptr<uint8_t>(), work.data_ptr(), work.numel(), cur_stream()),
      "fcp::matte_refine");
@@ -622,20 +634,13 @@ Tensor matte_blur_alpha(const Tensor& crops, const Tensor& labels, const Tensor&
   crops_and_plane(crops, labels, "labels", f, h, w);
   crops_and_plane(crops, alpha, "alpha", f, h, w);
   TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
-  const int64_t radius = (int64_t)taps.size() - 1;
-  TORCH_CHECK(radius >= 3 && radius <= 48, "matte_blur_alpha: taps must be t[0..radius] with radius 3..48 (got ", taps.size(),
-              " taps)");
   uint16_t t16[49];
-  for (int64_t k = 0; k <= radius; ++k) {
-    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, "matte_blur_alpha: tap ", k, " past 16 bits");
-    t16[k] = (uint16_t)taps[k];
-  }
+  const int radius = taps16("matte_blur_alpha", taps, false, t16);
   Tensor out = at::empty_like(crops);
-  const int64_t need = fcp_matte_blur_workspace_bytes((int)f, (int)h, (int)w);
-  Tensor work = at::empty({need < 0 ? 0 : need}, crops.options());
+  Tensor work = workspace(fcp_matte_blur_workspace_bytes((int)f, (int)h, (int)w), crops);
   ok(fcp_matte_blur_alpha_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), alpha.data_ptr<uint8_t>(), (int)f, (int)h,
-                             (int)w, (uint32_t)class_bits, t16, (int)radius, out.data_ptr<uint8_t>(), work.data_ptr(),
-                             work.numel(), cur_stream()),
+                             (int)w, (uint32_t)class_bits, t16, radius, out.data_ptr<uint8_t>(), work.data_ptr(), work.numel(),
+                             cur_stream()),
      "fcp::matte_blur_alpha");
   return out;
 }
@@ -644,10 +649,8 @@ Tensor matte_blur_alpha(const Tensor& crops, const Tensor& labels, const Tensor&
 Tensor feather_alpha(const Tensor& labels, int64_t class_bits, int64_t feather) {
   dev(labels, "labels", at::kByte);
   FCP_DEVICE_GUARD(labels);
-  TORCH_CHECK(labels.dim() == 3, "labels (f,h,w) uint8");
-  const int64_t f = labels.size(0), h = labels.size(1), w = labels.size(2);
-  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "labels (f,h,w): sizes past int");
-  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  int64_t f, h, w;
+  labels_plane(labels, class_bits, f, h, w);
   TORCH_CHECK(feather >= INT_MIN && feather <= INT_MAX, "feather past int");
   Tensor alpha = at::empty_like(labels);
   ok(fcp_feather_alpha_u8(labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits, (int)feather,
@@ -666,20 +669,12 @@ Tensor cutout(const Tensor& crops, const Tensor& alpha, int64_t mode, int64_t bg
   int64_t f, h, w;
   crops_and_plane(crops, alpha, "alpha", f, h, w);
   for (int64_t v : {mode, bg_r, bg_g, bg_b}) TORCH_CHECK(v >= INT_MIN && v <= INT_MAX, "mode / fill past int");
-  const int64_t radius = (int64_t)taps.size() - 1;
-  TORCH_CHECK(taps.empty() || (radius >= 3 && radius <= 48), "cutout: taps must be empty or t[0..radius] with radius 3..48 (got ",
-              taps.size(), " taps)");
   uint16_t t16[49] = {};
-  for (int64_t k = 0; k <= radius; ++k) {
-    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, "cutout: tap ", k, " past 16 bits");
-    t16[k] = (uint16_t)taps[k];
-  }
+  const int radius = taps16("cutout", taps, true, t16);
   Tensor out = at::empty({f, h, w, mode == FCP_CUTOUT_RGBA ? 4 : 3}, crops.options());
-  const int64_t need = taps.empty() ? 0 : fcp_cutout_workspace_bytes((int)f, (int)h, (int)w);
-  Tensor work = at::empty({need < 0 ? 0 : need}, crops.options());
+  Tensor work = workspace(taps.empty() ? 0 : fcp_cutout_workspace_bytes((int)f, (int)h, (int)w), crops);
   ok(fcp_cutout_u8(crops.data_ptr<uint8_t>(), alpha.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (int)mode, (int)bg_r, (int)bg_g,
-                   (int)bg_b, t16, taps.empty() ? 0 : (int)radius, out.data_ptr<uint8_t>(), work.data_ptr(), work.numel(),
-                   cur_stream()),
+                   (int)bg_b, t16, radius, out.data_ptr<uint8_t>(), work.data_ptr(), work.numel(), cur_stream()),
      "fcp::cutout");
   return out;
 }
@@ -690,14 +685,11 @@ Tensor cutout(const Tensor& crops, const Tensor& alpha, int64_t mode, int64_t bg
 Tensor subject_mask(const Tensor& labels, int64_t class_bits, bool keep_largest, int64_t max_hole) {
   dev(labels, "labels", at::kByte);
   FCP_DEVICE_GUARD(labels);
-  TORCH_CHECK(labels.dim() == 3, "labels (f,h,w) uint8");
-  const int64_t f = labels.size(0), h = labels.size(1), w = labels.size(2);
-  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "labels (f,h,w): sizes past int");
-  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  int64_t f, h, w;
+  labels_plane(labels, class_bits, f, h, w);
   TORCH_CHECK(max_hole >= INT_MIN && max_hole <= INT_MAX, "max_hole past int");
   Tensor out = at::empty_like(labels);
-  const int64_t need = fcp_subject_mask_workspace_bytes((int)f, (int)h, (int)w);
-  Tensor work = at::empty({need < 0 ? 0 : need}, labels.options());
+  Tensor work = workspace(fcp_subject_mask_workspace_bytes((int)f, (int)h, (int)w), labels);
   ok(fcp_subject_mask_u8(labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits, keep_largest ? 1 : 0,
                          (int)max_hole, out.data_ptr<uint8_t>(), work.data_ptr(), work.numel(), cur_stream()),
      "fcp::subject_mask");

@@ -114,25 +114,24 @@ def check_feather(feather) -> int:
     return int(feather)
 
 
-def check_blur(sigma):
-    """``background_blur`` of the Cropper -> None (off) or sigma in output pixels as a float: finite, 0.5..16."""
+def _check_sigma(option: str, sigma):
     if sigma is None:
         return None
     if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or \
             not np.isfinite(sigma) or not MIN_SIGMA <= sigma <= MAX_SIGMA:
-        raise ValueError(f"background_blur must be None or a finite sigma in [{MIN_SIGMA}, {MAX_SIGMA}] pixels, not {sigma!r}")
+        raise ValueError(f"{option} must be None or a finite sigma in [{MIN_SIGMA}, {MAX_SIGMA}] pixels, not {sigma!r}")
     return float(sigma)
+
+
+def check_blur(sigma):
+    """``background_blur`` of the Cropper -> None (off) or sigma in output pixels as a float: finite, 0.5..16."""
+    return _check_sigma("background_blur", sigma)
 
 
 def check_decontaminate(sigma):
     """``decontaminate`` of the Cropper -> None (off) or sigma in output pixels as a float: finite, 0.5..16, the range of
     ``background_blur`` (the taps are ``blur_taps``' too)."""
-    if sigma is None:
-        return None
-    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or \
-            not np.isfinite(sigma) or not MIN_SIGMA <= sigma <= MAX_SIGMA:
-        raise ValueError(f"decontaminate must be None or a finite sigma in [{MIN_SIGMA}, {MAX_SIGMA}] pixels, not {sigma!r}")
-    return float(sigma)
+    return _check_sigma("decontaminate", sigma)
 
 
 def check_refine(refine):
@@ -190,9 +189,25 @@ def blur_taps(sigma) -> list:
     return t
 
 
+def _check_crops(crops_dev, labels_dev=None):
+    """crops (F,H,W,3) u8, contiguous, and with them the label maps (F,H,W) u8."""
+    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
+    if labels_dev is not None:
+        assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and tuple(labels_dev.shape) == tuple(crops_dev.shape[:3])
+
+
 def _check_alpha(alpha, crops_dev):
     assert alpha.dtype == torch.uint8 and alpha.is_contiguous() and tuple(alpha.shape) == tuple(crops_dev.shape[:3])
     assert alpha.device == crops_dev.device
+
+
+def _check_taps(entry: str, taps, allow_empty: bool = False):
+    """The ctypes boundary's share of the taps check (the torch ops have their own): the count and 16 bits each."""
+    if allow_empty and not taps:
+        return
+    if not MIN_RADIUS + 1 <= len(taps) <= MAX_RADIUS + 1 or min(taps) < 0 or max(taps) > 65535:
+        raise RuntimeError(f"{entry}: taps must be {'empty or ' if allow_empty else ''}t[0..radius] with radius "
+                           f"{MIN_RADIUS}..{MAX_RADIUS}, each 16 bits (got {len(taps)} taps)")
 
 
 def refine_alpha(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, radius: int, eps: int) -> torch.Tensor:
@@ -200,8 +215,7 @@ def refine_alpha(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: 
     a guided filter of window radius ``radius`` (1..16) and regulariser ``eps`` (1..4096) with the gray of the crop as the
     guide, in integers.  Two launches and a workspace of 8 bytes per pixel that lives for the
     call; H, W <= 8192."""
-    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
-    assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and tuple(labels_dev.shape) == tuple(crops_dev.shape[:3])
+    _check_crops(crops_dev, labels_dev)
     if T.ENABLED:
         return T.load().matte_refine(crops_dev, labels_dev, int(class_bits), int(radius), int(eps))
     f, h, w, _ = crops_dev.shape
@@ -251,16 +265,14 @@ def cutout(crops_dev: torch.Tensor, alpha: torch.Tensor, fill=None, taps=None) -
     ``blur_taps``: its weights are the pixels whose alpha is exactly 255 (subject) and exactly 0 (background), and where
     the window holds neither kind the crop's colour stands.  One launch without taps; two and a workspace of 32 bytes per
     pixel that lives for the call with them; H, W <= 8192."""
-    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
+    _check_crops(crops_dev)
     _check_alpha(alpha, crops_dev)
     mode = CUTOUT_RGBA if fill is None else CUTOUT_FILL
     r, g, b = (0, 0, 0) if fill is None else (int(v) for v in fill)
     taps = [] if taps is None else [int(t) for t in taps]
     if T.ENABLED:
         return T.load().cutout(crops_dev, alpha, mode, r, g, b, taps)
-    if taps and (not MIN_RADIUS + 1 <= len(taps) <= MAX_RADIUS + 1 or min(taps) < 0 or max(taps) > 65535):
-        raise RuntimeError(f"fcp_cutout_u8: taps must be empty or t[0..radius] with radius {MIN_RADIUS}..{MAX_RADIUS}, each 16 "
-                           f"bits (got {len(taps)} taps)")
+    _check_taps("fcp_cutout_u8", taps, allow_empty=True)
     f, h, w, _ = crops_dev.shape
     out = torch.empty((f, h, w, 4 if fill is None else 3), dtype=torch.uint8, device=crops_dev.device)
     need = max(int(N.lib().fcp_cutout_workspace_bytes(f, h, w)), 0) if taps else 0
@@ -278,8 +290,7 @@ def matte_blur(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: in
     workspace of 16 bytes per pixel that lives for the call; H, W <= 8192.  With ``alpha`` (F,H,W) u8 (``refine_alpha``'s)
     the composite goes through that plane instead of the feathered mask: ``feather`` is not used, and the plane itself
     comes back where ``with_alpha`` asks for one."""
-    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
-    assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and tuple(labels_dev.shape) == tuple(crops_dev.shape[:3])
+    _check_crops(crops_dev, labels_dev)
     taps = [int(t) for t in taps]
     if alpha is not None:
         _check_alpha(alpha, crops_dev)
@@ -289,9 +300,7 @@ def matte_blur(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: in
     elif T.ENABLED:
         out, alpha = T.load().matte_blur(crops_dev, labels_dev, int(class_bits), int(feather), taps, bool(with_alpha))
         return out, (alpha if with_alpha else None)
-    if not MIN_RADIUS + 1 <= len(taps) <= MAX_RADIUS + 1 or min(taps) < 0 or max(taps) > 65535:
-        raise RuntimeError(f"fcp_matte_blur_u8: taps must be t[0..radius] with radius {MIN_RADIUS}..{MAX_RADIUS}, each 16 bits "
-                           f"(got {len(taps)} taps)")
+    _check_taps("fcp_matte_blur_u8", taps)
     f, h, w, _ = crops_dev.shape
     out = torch.empty_like(crops_dev)
     need = max(int(N.lib().fcp_matte_blur_workspace_bytes(f, h, w)), 0)
@@ -314,8 +323,7 @@ def matte(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, fe
     """crops (F,H,W,3) u8 and labels (F,H,W) u8, device -> (out (F,H,W,3) u8, alpha (F,H,W) u8 or None), device.  One
     launch; H, W <= 8192.  With ``alpha`` (F,H,W) u8 (``refine_alpha``'s) the composite goes through that plane: the
     labels, ``class_bits`` and ``feather`` are not used, and the plane itself comes back where ``with_alpha`` asks for one."""
-    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() == 4 and crops_dev.shape[3] == 3
-    assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and tuple(labels_dev.shape) == tuple(crops_dev.shape[:3])
+    _check_crops(crops_dev, labels_dev)
     r, g, b = (int(v) for v in fill)
     if alpha is not None:
         _check_alpha(alpha, crops_dev)

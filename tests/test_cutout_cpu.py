@@ -51,8 +51,10 @@ def test_reference_taps_are_the_package_s():
 
 
 def test_shape_list_crosses_the_kernel_s_tiles():
-    """The shapes of the GPU tests come from the tile constants of csrc/fcp_cutout.hip: more than one tile each way."""
-    src = open(os.path.join(ROOT, "face-crop-plus_amd", "csrc", "fcp_cutout.hip")).read()
+    """The shapes of the GPU tests come from the tile constants of csrc/fcp_cutout.hip and, for the rows pass it shares
+    with the background blur, of csrc/fcp_masked_blur.h: more than one tile each way."""
+    csrc = os.path.join(ROOT, "face-crop-plus_amd", "csrc")
+    src = open(os.path.join(csrc, "fcp_masked_blur.h")).read() + open(os.path.join(csrc, "fcp_cutout.hip")).read()
     const = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
     assert (R.ROW_W, R.ROW_H, R.COL_W, R.COL_H) == (const("kRowTileW"), const("kRowTileH"), const("kTileW"), const("kTileH"))
     assert any(w > R.ROW_W for _, w in R.SHAPES) and any(h > R.ROW_H for h, _ in R.SHAPES)

@@ -192,15 +192,18 @@ def test_refusals_carry_their_messages(device):
     need = lib.fcp_cutout_workspace_bytes(1, 8, 8)
     work = torch.empty((need + 16,), dtype=torch.uint8, device=device)
 
-    def call(mode=0, radius=len(taps) - 1, o=N.ptr(out), ws=N.ptr(work), wsb=need, a=N.ptr(alpha), f=1):
-        return lib.fcp_cutout_u8(N.ptr(crops), a, f, 8, 8, mode, 1, 2, 3, t16, radius, o, ws, wsb, N.stream_ptr())
+    def call(mode=0, radius=len(taps) - 1, o=N.ptr(out), ws=N.ptr(work), wsb=need, a=N.ptr(alpha), f=1, t=t16):
+        return lib.fcp_cutout_u8(N.ptr(crops), a, f, 8, 8, mode, 1, 2, 3, t, radius, o, ws, wsb, N.stream_ptr())
+    zero_tap, short_sum = (ctypes.c_uint16 * 4)(4090, 2, 0, 1), (ctypes.c_uint16 * 4)(4089, 1, 1, 1)   # sums 4096 and 4095
     for kw, word in ((dict(mode=3), b"mode"), (dict(radius=2), b"radius"), (dict(radius=49), b"radius"),
                      (dict(mode=1, radius=0), b"fcp_matte_alpha_u8"), (dict(radius=11), b"sum to 4096"),
                      (dict(wsb=need - 1), b"workspace"), (dict(ws=None), b"workspace"), (dict(ws=N.ptr(work, 4)), b"16-byte aligned"),
                      (dict(o=N.ptr(out, 1)), b"4-byte aligned"), (dict(a=None), b"null pointer"), (dict(o=None), b"null pointer"),
-                     (dict(f=65536), b"65535")):
+                     (dict(f=65536), b"65535"), (dict(radius=3, t=zero_tap), b"tap 2 is 0"),
+                     (dict(radius=3, t=short_sum), b"sum to 4096")):
         assert call(**kw) < 0, kw
         assert word in lib.fcp_last_error() and b"cutout" in lib.fcp_last_error(), (kw, lib.fcp_last_error())
+        assert lib.fcp_last_error().startswith(b"cutout:"), lib.fcp_last_error()
     torch.cuda.synchronize()
     assert (out.cpu() == 7).all()                                    # nothing was launched
     assert call() == 0 and call(radius=0, ws=None, wsb=0) == 0       # radius 0 reads no workspace

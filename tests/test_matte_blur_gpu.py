@@ -14,7 +14,7 @@ from oracle import align_ref as A
 
 pytestmark = pytest.mark.gpu
 
-ROW_W, ROW_H = 256, 4                        # kRowTileW, kRowTileH of csrc/fcp_matte_blur.hip
+ROW_W, ROW_H = 256, 4                        # kRowTileW, kRowTileH of csrc/fcp_masked_blur.h
 TILE_W, TILE_H = 16, 64                      # kTileW, kTileH
 SMALL = [(1, 1), (1, 2), (2, 1), (3, 3), (5, 4), (7, 7), (33, 65), (96, 80),
          (TILE_H - 1, TILE_W - 1), (TILE_H, TILE_W), (TILE_H + 1, TILE_W + 1),
@@ -236,6 +236,27 @@ def test_boundaries_give_identical_tensors(device, monkeypatch):
         ops.matte_blur(cd, ld[:, :-1].contiguous(), ONE_17, 5, taps, True)
     with pytest.raises(RuntimeError):
         ops.matte_blur(cd.float(), ld, ONE_17, 5, taps, True)
+    # the C entry points themselves at 8 x 8: one tap of 0 in a window that still sums to 4096, and a window that sums to
+    # 4095, are refused under the entry point's name before anything is launched
+    import ctypes
+    from face_crop_plus_amd import _native as N
+    lib = N.lib()
+    c8 = torch.zeros((1, 8, 8, 3), dtype=torch.uint8, device=device)
+    l8 = torch.zeros((1, 8, 8), dtype=torch.uint8, device=device)
+    a8 = torch.full((1, 8, 8), 128, dtype=torch.uint8, device=device)
+    o8 = torch.full((1, 8, 8, 3), 7, dtype=torch.uint8, device=device)
+    need = lib.fcp_matte_blur_workspace_bytes(1, 8, 8)
+    work = torch.empty((need,), dtype=torch.uint8, device=device)
+    for bad, word in (([4090, 2, 0, 1], b"tap 2 is 0"), ([4089, 1, 1, 1], b"sum to 4096")):
+        t16 = (ctypes.c_uint16 * 4)(*bad)
+        assert lib.fcp_matte_blur_u8(N.ptr(c8), N.ptr(l8), 1, 8, 8, ONE_17, 5, t16, 3, N.ptr(o8), None, N.ptr(work), need,
+                                     N.stream_ptr()) < 0, bad
+        assert lib.fcp_last_error().startswith(b"matte_blur:") and word in lib.fcp_last_error(), (bad, lib.fcp_last_error())
+        assert lib.fcp_matte_blur_alpha_u8(N.ptr(c8), N.ptr(l8), N.ptr(a8), 1, 8, 8, ONE_17, t16, 3, N.ptr(o8), N.ptr(work), need,
+                                           N.stream_ptr()) < 0, bad
+        assert lib.fcp_last_error().startswith(b"matte_blur_alpha:") and word in lib.fcp_last_error(), (bad, lib.fcp_last_error())
+    torch.cuda.synchronize()
+    assert (o8.cpu() == 7).all()                                     # nothing was launched
 
 
 def test_cropper_matte_equals_reference(device):
