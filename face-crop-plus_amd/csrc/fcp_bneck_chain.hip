@@ -41,8 +41,6 @@ using namespace fcp_conv;
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int FCP_CHAIN_STORE_AUX = 2;   // cache policy of the `out` stores of the chunk loop: nt (0 default / 16 sc1 measured equal)
 
 struct ChainK {
@@ -154,6 +152,8 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* lds = reinterpret_cast<char*>(smem);
 
+  // (xcd_tile_order spelt out: through the helper the sum's two scalar instructions come out in other registers, and this
+  //  file's kernels are to stay instruction-identical: profiles/conv_walk.md)
   const int nb = gridDim.x;
   const int bid = blockIdx.x;
   const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;

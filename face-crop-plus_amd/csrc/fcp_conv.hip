@@ -28,12 +28,6 @@ namespace {
 constexpr int LDK = 32;  // floats per LDS row (XOR-swizzled 16-byte chunks, no padding)
 
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 0));
-}
-
 // BUF: operands are fetched with raw buffer loads (32-bit byte offsets from a
 // wave-uniform descriptor; an offset of 0xFFFFFFFF is out of range and returns
 // zeros, which is exactly the conv's zero padding) — branch-free, so the
@@ -53,13 +47,7 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
   float* As = smem;
   float* Bs = smem + 2 * BM * LDK;
 
-  // XCD-aware tile order: hardware round-robins consecutive workgroup ids over
-  // the 8 XCDs; give each XCD a contiguous run of logical tiles so the N-tiles
-  // of one pixel block and neighbouring pixel blocks (3x3 halos) share an L2.
-  const int nb = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q = nb >> 3, r = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int logical = xcd_tile_order(gridDim.x, blockIdx.x);
   const int tile_n = logical % p.grid_n;
   const int tile_m = logical / p.grid_n;
 
@@ -70,29 +58,16 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
   const int chunk = tid & 7;
   const int lrow = tid >> 3;  // 0..31
 
-  // per-thread im2col row bookkeeping
-  long nbase[A_LD];        // flat path only
-  unsigned pbase[A_LD];    // buffer path: first pixel of the row's image (32-bit)
-  int hi0[A_LD], wi0[A_LD];
+  // per-thread im2col row bookkeeping: one 16-byte piece per row (chunk `chunk` of the slice's 32 channels; CIN4: pixel
+  // `chunk` of the tap row)
+  long nbase[A_LD];        // flat path only: first pixel of the row's image, 64-bit
+  RowPiece pc[A_LD];
   const int hw = p.out_h * p.out_w;
 #pragma unroll
   for (int i = 0; i < A_LD; ++i) {
-    const int m = tile_m * BM + lrow + 32 * i;
-    if (m < p.M) {
-      const int ni = m / hw;
-      const int rem = m - ni * hw;
-      const int ho = rem / p.out_w;
-      const int wo = rem - ho * p.out_w;
-      nbase[i] = (long)ni * p.ph * p.pw;
-      pbase[i] = (unsigned)(ni * p.ph * p.pw);
-      hi0[i] = ho * p.stride - p.pad_h;
-      wi0[i] = wo * p.stride - p.pad;
-    } else {
-      nbase[i] = 0;
-      pbase[i] = 0;
-      hi0[i] = -(1 << 28);
-      wi0[i] = 0;
-    }
+    const ConvRow r = conv_row(p, tile_m * BM + lrow + 32 * i, p.M, hw, 0u);
+    nbase[i] = (long)r.ni * p.ph * p.pw;
+    pc[i] = make_row_piece<CIN4>(p, r, chunk, (unsigned)(chunk * 4));
   }
   const float* wbase = p.w + (long)(tile_n * BN + lrow) * p.wrow + chunk * 4;
 
@@ -106,29 +81,6 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
     for (int i = 0; i < B_LD; ++i)
       woff[i] = (unsigned)(((tile_n * BN + lrow + 32 * i) * p.wrow + chunk * 4) * 4);
   }
-  TapPiece tp[A_LD];
-  if (BUF) {
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i)
-      tp[i] = make_tap_piece<CIN4>(p, pbase[i], hi0[i], wi0[i] + (CIN4 ? chunk : 0), CIN4 ? 0u : (unsigned)(chunk * 4));
-  }
-  auto set_tap = [&](int tap, int kh_i, int kw_i) {
-    if (p.in_up2) {   // nearest-x2 operand fetch: physical offset is not linear in the tap
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        int hi = hi0[i] + kh_i;
-        int wi = wi0[i] + (CIN4 ? chunk : kw_i);
-        const bool ok = (unsigned)hi < (unsigned)p.in_h && (unsigned)wi < (unsigned)p.in_w;
-        hi >>= 1; wi >>= 1;
-        const unsigned pix = pbase[i] + (unsigned)(hi * p.pw + wi);
-        rowoff[i] = ok ? (pix * (unsigned)p.in_ld + (CIN4 ? 0u : (unsigned)(chunk * 4))) * 4u : 0xFFFFFFFFu;
-      }
-    } else {
-      const unsigned tapoff = (unsigned)((kh_i * p.pw + kw_i) * p.in_ld) * 4u;   // wave-uniform
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) rowoff[i] = ((tp[i].mask >> tap) & 1u) ? tp[i].base + tapoff : 0xFFFFFFFFu;
-    }
-  };
 
   // two register sets: the fetch of slice k+2 is in flight while slice k is multiplied and
   // slice k+1 (fetched one full iteration earlier) is written to LDS — a prefetch distance of
@@ -147,8 +99,8 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
     } else {
 #pragma unroll
       for (int i = 0; i < A_LD; ++i) {
-        int hi = hi0[i] + kh_i;
-        int wi = wi0[i] + (CIN4 ? chunk : kw_i);
+        int hi = pc[i].hi0 + kh_i;
+        int wi = pc[i].wi0 + (CIN4 ? chunk : kw_i);
         const bool ok = (unsigned)hi < (unsigned)p.in_h && (unsigned)wi < (unsigned)p.in_w;
         if (p.in_up2) { hi >>= 1; wi >>= 1; }
         const long pix = nbase[i] + (long)hi * p.pw + wi;
@@ -174,23 +126,12 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  clear_acc(acc);
 
-  int tap = 0, kh_i = 0, kw_i = 0, c0 = 0;
-  auto advance = [&]() {      // next slice: taps fastest, then the 32-channel slice
-    ++tap;
-    if (CIN4) {
-      ++kh_i;
-    } else if (++kw_i >= p.kw) {
-      kw_i = 0;
-      if (++kh_i >= p.kh) { kh_i = 0; tap = 0; c0 += BK; }
-    }
-    if (BUF) set_tap(tap, kh_i, kw_i);
+  TapWalk tw;
+  auto advance = [&]() {      // next slice; the flat path works its addresses out per load (load_slice)
+    if (BUF) next_tap<CIN4, true>(p, tw, pc, rowoff);
+    else tw.advance<CIN4>(p);
   };
 
   const int aoff = (wm * WTM + (lane & 31)) * LDK;
@@ -225,19 +166,19 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
                   const f32x4 (&rb_st)[B_LD]) {
     if (kt + 2 < p.ktiles) {
       advance();
-      load_slice(ra_ld, rb_ld, kt + 2, kh_i, kw_i, c0);
+      load_slice(ra_ld, rb_ld, kt + 2, tw.kh_i, tw.kw_i, tw.c0);
     }
     compute(kt & 1);
     if (kt + 1 < p.ktiles) store_slice(ra_st, rb_st, (kt + 1) & 1);
     __syncthreads();
   };
 
-  if (BUF) set_tap(0, 0, 0);
-  load_slice(ra0, rb0, 0, kh_i, kw_i, c0);
+  if (BUF) set_tap<CIN4, true>(p, tw, pc, rowoff);
+  load_slice(ra0, rb0, 0, tw.kh_i, tw.kw_i, tw.c0);
   store_slice(ra0, rb0, 0);
   if (p.ktiles > 1) {
     advance();
-    load_slice(ra1, rb1, 1, kh_i, kw_i, c0);
+    load_slice(ra1, rb1, 1, tw.kh_i, tw.kw_i, tw.c0);
   }
   __syncthreads();
   for (int kt = 0; kt < p.ktiles; kt += 2) {

@@ -1,5 +1,5 @@
 // Shared pieces of the convolution kernels (fp32-exact and fp16x3-split variants):
-// kernel parameter block and the fused epilogue.
+// kernel parameter block, the im2col walk and the fused epilogue.
 #pragma once
 #include <type_traits>
 #include "fcp_common.h"
@@ -80,6 +80,175 @@ __device__ __forceinline__ TapPiece make_tap_piece(const ConvK& p, unsigned pbas
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The im2col walk of the generic implicit-GEMM kernels (conv_igemm_f32, _f16x3, _f16x3_dma, _f16x3_big), stated once: which
+// tile a workgroup owns, where an output row's window starts, which tap and channel slice a K slice is, and the operand
+// offset of a 16-byte piece at that tap.  How a slice reaches LDS, the pipeline and the MFMAs are the kernels' own.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// XCD-aware tile order: hardware round-robins consecutive workgroup ids over the 8 XCDs; give each XCD a contiguous run of
+// logical tiles so the N-tiles of one pixel block and neighbouring pixel blocks (3x3 halos) share an L2.
+// bid of nb workgroups -> logical tile.
+__device__ __forceinline__ int xcd_tile_order(int nb, int bid) {
+  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
+// Output pixel m -> (image, row, column); hw = out_h * out_w.  (M: int in the walk, long in the epilogue's res1_pixel.)
+template <typename M>
+__device__ __forceinline__ void conv_out_pixel(const ConvK& p, M m, int hw, int& ni, int& ho, int& wo) {
+  ni = (int)(m / hw);
+  const int rem = (int)(m - (M)ni * hw);
+  ho = rem / p.out_w;
+  wo = rem - ho * p.out_w;
+}
+
+// One output row (GEMM row m) of a tile whose rows end at m_end, decoded once.
+struct ConvRow {
+  int ni;           // image of the row: the fp32 kernel's flat path forms its 64-bit pixel index from it
+  unsigned pbase;   // first pixel of that image (32-bit: the buffer paths)
+  int hi0, wi0;     // input coordinates of tap (0, 0); a row at or past m_end has hi0 = -(1 << 28): every tap is padding
+  unsigned base2;   // second source (p.in2 set): byte offset of the row's pixel there + chan_off2 floats, else 0xFFFFFFFF
+};
+__device__ __forceinline__ ConvRow conv_row(const ConvK& p, int m, int m_end, int hw, unsigned chan_off2) {
+  ConvRow r = {0, 0u, -(1 << 28), 0, 0xFFFFFFFFu};
+  if (m < m_end) {
+    int ho, wo;
+    conv_out_pixel(p, m, hw, r.ni, ho, wo);
+    r.pbase = (unsigned)(r.ni * p.ph * p.pw);
+    r.hi0 = ho * p.stride - p.pad_h;
+    r.wi0 = wo * p.stride - p.pad;
+    if (p.in2 != nullptr)
+      r.base2 = (((unsigned)(r.ni * p.ph2 + ho * p.stride2) * (unsigned)p.pw2 + (unsigned)(wo * p.stride2)) * (unsigned)p.in2_ld + chan_off2) * 4u;
+  }
+  return r;
+}
+
+// One 16-byte operand piece of a row: channels chan_off .. + 3 of the tap's pixel, or (CIN4: 3 channels in an NHWC4 buffer,
+// a K slice = one filter row of 8 pixels) pixel `col` of the tap row.  A kernel holds as many per row as its staging needs.
+struct RowPiece {
+  unsigned pbase;
+  int hi0, wi0;       // the row's
+  int col;            // CIN4: the piece's pixel in the tap row, else 0
+  unsigned chan_off;  // 0 under CIN4
+  TapPiece tp;
+};
+template <bool CIN4>
+__device__ __forceinline__ RowPiece make_row_piece(const ConvK& p, const ConvRow& r, int col, unsigned chan_off) {
+  RowPiece c = {r.pbase, r.hi0, r.wi0, CIN4 ? col : 0, CIN4 ? 0u : chan_off, {0u, 0u}};
+  c.tp = make_tap_piece<CIN4>(p, c.pbase, c.hi0, c.wi0 + c.col, c.chan_off);
+  return c;
+}
+
+// The K slice a kernel is at: taps fastest, then the 32-channel slice (the K order above).
+struct TapWalk {
+  int tap = 0, kh_i = 0, kw_i = 0, c0 = 0;
+  template <bool CIN4>
+  __device__ __forceinline__ void advance(const ConvK& p) {
+    ++tap;
+    if (CIN4) {
+      ++kh_i;
+    } else if (++kw_i >= p.kw) {
+      kw_i = 0;
+      if (++kh_i >= p.kh) { kh_i = 0; tap = 0; c0 += BK; }
+    }
+  }
+};
+
+// rowoff[i] = byte offset of piece i at channel 0 of the walk's tap, 0xFFFFFFFF = zero padding.  UP2: the kernel has the
+// nearest-x2 operand fetch (p.in_up2), whose physical offset is not linear in the tap and is recomputed per tap.
+template <bool CIN4, bool UP2, int NP>
+__device__ __forceinline__ void set_tap(const ConvK& p, const TapWalk& t, const RowPiece (&pc)[NP], unsigned (&rowoff)[NP]) {
+  if (UP2 && p.in_up2) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      int hi = pc[i].hi0 + t.kh_i;
+      int wi = pc[i].wi0 + (CIN4 ? pc[i].col : t.kw_i);
+      const bool ok = (unsigned)hi < (unsigned)p.in_h && (unsigned)wi < (unsigned)p.in_w;
+      hi >>= 1; wi >>= 1;
+      const unsigned pix = pc[i].pbase + (unsigned)(hi * p.pw + wi);
+      rowoff[i] = ok ? (pix * (unsigned)p.in_ld + pc[i].chan_off) * 4u : 0xFFFFFFFFu;
+    }
+  } else {
+    const unsigned tapoff = (unsigned)((t.kh_i * p.pw + t.kw_i) * p.in_ld) * 4u;   // wave-uniform
+#pragma unroll
+    for (int i = 0; i < NP; ++i) rowoff[i] = ((pc[i].tp.mask >> t.tap) & 1u) ? pc[i].tp.base + tapoff : 0xFFFFFFFFu;
+  }
+}
+template <bool CIN4, bool UP2, int NP>
+__device__ __forceinline__ void next_tap(const ConvK& p, TapWalk& t, const RowPiece (&pc)[NP], unsigned (&rowoff)[NP]) {
+  t.advance<CIN4>(p);
+  set_tap<CIN4, UP2>(p, t, pc, rowoff);
+}
+
+__device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 0));
+}
+__device__ __forceinline__ u32x4_t buf_load16u(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
+  return __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 0));
+}
+
+// One K slice of the LDS-DMA kernels: A_LD + B_LD DMA instructions per wave, each 64 lanes x 16 B = LDS rows
+// 8 * wave + STEP * i .. + 7 of the pixel tile at `a` and of the filter tile at `b` (STEP = rows one instruction set covers:
+// a quarter of the threads' count).  Channels >= csplit come from the second source (wave-uniform choice).
+template <int STEP, int A_LD, int B_LD>
+__device__ __forceinline__ void dma_slice(const ConvK& p, __amdgpu_buffer_rsrc_t rs_in, __amdgpu_buffer_rsrc_t rs_in2, __amdgpu_buffer_rsrc_t rs_w,
+                                          char* a, char* b, const unsigned (&rowoff)[A_LD], const unsigned (&base2)[A_LD],
+                                          const unsigned (&woff)[B_LD], int c0, int kt) {
+  constexpr int ROWB = 128;
+  if (c0 >= p.csplit) {
+#pragma unroll
+    for (int i = 0; i < A_LD; ++i) {
+      const unsigned ro = base2[i];
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in2, (__attribute__((address_space(3))) void*)(a + STEP * i * ROWB), 16,
+                                               (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)((c0 - p.csplit) * 4)), 0, 0, FCP_AUX_A);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < A_LD; ++i) {
+      const unsigned ro = rowoff[i];
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (__attribute__((address_space(3))) void*)(a + STEP * i * ROWB), 16,
+                                               (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)(c0 * 4)), 0, 0, FCP_AUX_A);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < B_LD; ++i)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(b + STEP * i * ROWB), 16,
+                                             (int)(woff[i] + (unsigned)(kt * BK * 4)), 0, 0, FCP_AUX_B);
+}
+
+// Fragment offsets inside a swizzled 128-byte fp16x3 LDS row [hi k0..31 | lo k0..31] (chunk swizzle ((row >> 1) & 7) ^
+// ((row & 1) << 2), row = lane & 31): the hi / lo chunk of k-half s that lane `lane` feeds to v_mfma_f32_32x32x16_f16.
+__device__ __forceinline__ void frag_offsets(int lane, int (&offH)[2], int (&offL)[2]) {
+  const int rsw = (((lane & 31) >> 1) & 7) ^ ((lane & 1) << 2);
+  const int half = lane >> 5;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    offH[s] = ((2 * s + half) ^ rsw) << 4;
+    offL[s] = ((4 + 2 * s + half) ^ rsw) << 4;
+  }
+}
+
+// ds_read_b128 with an immediate offset, as inline asm: the compiler's waitcnt pass would otherwise drain the pending LDS-DMA
+// (vmcnt(0)) in front of every LDS read.
+template <int IMM>
+__device__ __forceinline__ f16x8 lds_read128i(unsigned addr) {
+  f16x8 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(IMM));
+  return v;
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void clear_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
 
 // Mixed-precision FMA (v_fma_mix_f32: every source is an f32 register or one binary16 half of a register, one rounding):
 //   fcp_mix_sum(h, l, HI)  = float(h.half) + float(l.half)      — exactly what v_cvt_f32_f16 x2 + v_add_f32 give (the conversions
@@ -230,10 +399,8 @@ __device__ __forceinline__ float conv_value_relu(float acc, float ws, float b) {
 // Pixel of a resized res1 that output pixel m = (ni, ho, wo) adds: nearest neighbour, floor(o * in / out) clamped to the map
 // (hw = out_h * out_w).
 __device__ __forceinline__ long res1_pixel(const ConvK& p, long m, int hw) {
-  const int ni = (int)(m / hw);
-  const int rem = (int)(m - (long)ni * hw);
-  const int ho = rem / p.out_w;
-  const int wo = rem - ho * p.out_w;
+  int ni, ho, wo;
+  conv_out_pixel(p, m, hw, ni, ho, wo);
   int sh = (int)floorf(ho * p.res1_sh);
   int sw = (int)floorf(wo * p.res1_sw);
   sh = sh < p.res1_h - 1 ? sh : p.res1_h - 1;

@@ -7,8 +7,10 @@
 // replace eight fp32 MFMAs (2 k-values each): 5.3x the matrix throughput of
 // v_mfma_f32_32x32x2_f32 at ~2^-20 per-product error, i.e. fp32-roundoff class.  Filters
 // are split offline (per-output-channel power-of-two pre-scaling keeps their lo parts out
-// of the fp16 subnormal range; the scale is undone exactly in the epilogue); activations
-// stay fp32 in HBM and are split on the fly while being staged into LDS.
+// of the fp16 subnormal range; the scale is undone exactly in the epilogue).  This kernel
+// takes fp32 activations (CIN4: the 3-channel stems' NHWC4 images) and splits them on the fly
+// while staging them into LDS; split32 activations go to the LDS-DMA kernels
+// (fcp_conv_f16x3_dma.hip, _big.hip, _halo.hip), never here.
 //
 // Geometry is the fp32 kernel's: 128 x BN tile per 256-thread workgroup, K walked in
 // slices of 32 (one filter tap x 32 channels), raw buffer loads (out-of-range offset ==
@@ -26,22 +28,10 @@ using namespace fcp_conv;
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef u32x4_t u32x4;
 
-__device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 0));
-}
-__device__ __forceinline__ u32x4 buf_load16u(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
-  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 0));
-}
-
-// ASPLIT: the activation tensor is already in split32 format (hi/lo binary16 planes per 32 channels):
-// a K slice of a pixel is then byte-for-byte the LDS row image and is staged as a plain copy, exactly
-// like the filter; otherwise (fp32 input) it is split on the fly.
-template <int BN, bool CIN4, bool ASPLIT>
+template <int BN, bool CIN4>
 __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) conv_igemm_f16x3(const ConvK p) {
-  static_assert(!(CIN4 && ASPLIT), "the 3-channel stems always read fp32");
   constexpr int WAVES_N = (BN == 32) ? 1 : 2;
   constexpr int WAVES_M = 4 / WAVES_N;
   constexpr int WTM = BM / WAVES_M;
@@ -54,10 +44,7 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
   char* As = reinterpret_cast<char*>(smem);
   char* Bs = As + 2 * BM * ROWB;
 
-  const int nb = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_tile_order(gridDim.x, blockIdx.x);
   const int tile_n = logical % p.grid_n;
   const int tile_m = logical / p.grid_n;
 
@@ -76,20 +63,8 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
   const int hw = p.out_h * p.out_w;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int m = tile_m * BM + arow + 64 * i;
-    if (m < p.M) {
-      const int ni = m / hw;
-      const int rem = m - ni * hw;
-      const int ho = rem / p.out_w;
-      const int wo = rem - ho * p.out_w;
-      pbase[i] = (unsigned)(ni * p.ph * p.pw);
-      hi0[i] = ho * p.stride - p.pad_h;
-      wi0[i] = wo * p.stride - p.pad;
-    } else {
-      pbase[i] = 0;
-      hi0[i] = -(1 << 28);
-      wi0[i] = 0;
-    }
+    const ConvRow r = conv_row(p, tile_m * BM + arow + 64 * i, p.M, hw, 0u);
+    pbase[i] = r.pbase; hi0[i] = r.hi0; wi0[i] = r.wi0;
   }
   __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
   __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
@@ -97,9 +72,10 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
 #pragma unroll
   for (int i = 0; i < B_LD; ++i) woff[i] = (unsigned)(((tile_n * BN + brow + 32 * i) * p.wrow + bc * 4) * 4);
 
-  // this thread's four 16-byte activation pieces: (row i, half h).  fp32 input: channels 8ag+4h..+3 of the
-  // slice; split32 input: chunk ag of the hi plane (h = 0) / of the lo plane (h = 1), in 4-byte units
-  auto achan = [&](int h) -> unsigned { return ASPLIT ? (unsigned)(h * 16 + ag * 4) : (unsigned)(ag * 8 + h * 4); };
+  // this thread's four 16-byte activation pieces: (row i, half h) = channels 8ag+4h..+3 of the slice (CIN4: pixel
+  // 2ag+h of the tap row).  (RowPiece / set_tap spelt out for the 2 x 2 shape: as RowPiece pc[4] through the shared set_tap
+  // the 128-wide kernel measured 0.3-0.7 % slower in ten of eleven alternating pairs, profiles/conv_walk.md)
+  auto achan = [&](int h) -> unsigned { return (unsigned)(ag * 8 + h * 4); };
   TapPiece tp[2][2];
   unsigned rowoff[2][2];   // byte offset at channel 0 of the current tap, 0xFFFFFFFF = zero padding
 #pragma unroll
@@ -153,8 +129,7 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       u32x4 hi, lo;
-      if (ASPLIT) { hi = __builtin_bit_cast(u32x4, ra[2 * i]); lo = __builtin_bit_cast(u32x4, ra[2 * i + 1]); }
-      else split8(ra[2 * i], ra[2 * i + 1], hi, lo);
+      split8(ra[2 * i], ra[2 * i + 1], hi, lo);
       *reinterpret_cast<u32x4*>(a + 64 * i * ROWB + ((ag ^ asw) << 4)) = hi;
       *reinterpret_cast<u32x4*>(a + 64 * i * ROWB + (((4 + ag) ^ asw) << 4)) = lo;
     }
@@ -164,35 +139,18 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  clear_acc(acc);
 
-  int tap = 0, kh_i = 0, kw_i = 0, c0 = 0;
-  auto advance = [&]() {      // next slice: taps fastest, then the 32-channel slice
-    ++tap;
-    if (CIN4) {
-      ++kh_i;
-    } else if (++kw_i >= p.kw) {
-      kw_i = 0;
-      if (++kh_i >= p.kh) { kh_i = 0; tap = 0; c0 += BK; }
-    }
-    set_tap(tap, kh_i, kw_i);
+  TapWalk tw;
+  auto advance = [&]() {
+    tw.advance<CIN4>(p);
+    set_tap(tw.tap, tw.kh_i, tw.kw_i);
   };
 
   const int aoff = (wm * WTM + (lane & 31)) * ROWB;
   const int boff = (wn * WTN + (lane & 31)) * ROWB;
-  const int rsw = (((lane & 31) >> 1) & 7) ^ ((lane & 1) << 2);
-  const int half = lane >> 5;
   int offH[2], offL[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    offH[s] = ((2 * s + half) ^ rsw) << 4;
-    offL[s] = ((4 + 2 * s + half) ^ rsw) << 4;
-  }
+  frag_offsets(lane, offH, offL);
 
   // ---- one pipeline step, hand-interleaved -------------------------------------------------
   // The wave's instruction stream is in order, so matrix work and the split (VALU) + LDS store of
@@ -208,7 +166,7 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
                   const u32x4 (&rb_st)[B_LD]) {
     if (kt + 2 < p.ktiles) {
       advance();
-      load_slice(ra_ld, rb_ld, kt + 2, c0);
+      load_slice(ra_ld, rb_ld, kt + 2, tw.c0);
     }
     const int buf = kt & 1, nbuf = buf ^ 1;
     const char* Ab = As + buf * BM * ROWB + aoff;
@@ -239,15 +197,10 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
       if (pc == 16 || pc == 33) {          // activation rows: hi and lo chunks
         const int row = pc == 16 ? 0 : 1;
         u32x4 hi, lo;
-        if (ASPLIT) {
-          hi = __builtin_bit_cast(u32x4, ra_st[2 * row]);
-          lo = __builtin_bit_cast(u32x4, ra_st[2 * row + 1]);
-        } else {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            hi[q] = __builtin_bit_cast(unsigned, h2[row * 4 + q]);
-            lo[q] = __builtin_bit_cast(unsigned, l2[row * 4 + q]);
-          }
+        for (int q = 0; q < 4; ++q) {
+          hi[q] = __builtin_bit_cast(unsigned, h2[row * 4 + q]);
+          lo[q] = __builtin_bit_cast(unsigned, l2[row * 4 + q]);
         }
         *reinterpret_cast<u32x4*>(a_st + 64 * row * ROWB + ((ag ^ asw) << 4)) = hi;
         *reinterpret_cast<u32x4*>(a_st + 64 * row * ROWB + (((4 + ag) ^ asw) << 4)) = lo;
@@ -258,7 +211,6 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
         for (int i = 0; i < B_LD; ++i) *reinterpret_cast<u32x4*>(b_st + 32 * i * ROWB) = rb_st[i];
         return;
       }
-      if (ASPLIT) return;                              // nothing to convert: the copy is the store above
       const int g = pc < 16 ? pc : pc - 1;             // 0..31 over the four 8-piece groups
       const int pr = (g >> 3) * 2 + (g & 1);           // pair index 0..7
       const int stage = (g & 7) >> 1;
@@ -288,11 +240,11 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
   };
 
   set_tap(0, 0, 0);
-  load_slice(ra0, rb0, 0, c0);
+  load_slice(ra0, rb0, 0, tw.c0);
   store_slice(ra0, rb0, 0);
   if (p.ktiles > 1) {
     advance();
-    load_slice(ra1, rb1, 1, c0);
+    load_slice(ra1, rb1, 1, tw.c0);
   }
   __syncthreads();
   for (int kt = 0; kt < p.ktiles; kt += 2) {
@@ -306,11 +258,11 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : (BN == 64 ? 3 : 4))) con
     conv_epilogue<BN, TM, TN, WTM, WTN>(p, acc, smem, tile_m, tile_n, tid, lane, wm, wn, hw);
 }
 
-template <int BN, bool CIN4, bool ASPLIT>
+template <int BN, bool CIN4>
 int launch(const ConvK& k, hipStream_t s) {
   const size_t lds = (size_t)2 * (BM + BN) * 128;
-  FCP_LDS_OPT_IN((&conv_igemm_f16x3<BN, CIN4, ASPLIT>), lds);
-  hipLaunchKernelGGL((conv_igemm_f16x3<BN, CIN4, ASPLIT>), dim3(k.grid_m * k.grid_n), dim3(256), lds, s, k);
+  FCP_LDS_OPT_IN((&conv_igemm_f16x3<BN, CIN4>), lds);
+  hipLaunchKernelGGL((conv_igemm_f16x3<BN, CIN4>), dim3(k.grid_m * k.grid_n), dim3(256), lds, s, k);
   FCP_LAUNCH_OK();
   return 0;
 }
@@ -319,25 +271,11 @@ int launch(const ConvK& k, hipStream_t s) {
 
 namespace fcp_conv {
 
-int launch_f16x3(const ConvK& k, int tile_n, bool cin4, hipStream_t s) {
-  if (cin4) {
-    switch (tile_n) {
-      case 32: return launch<32, true, false>(k, s);
-      case 64: return launch<64, true, false>(k, s);
-      default: return launch<128, true, false>(k, s);
-    }
-  }
-  if (k.in_fmt == 1) {
-    switch (tile_n) {
-      case 32: return launch<32, false, true>(k, s);
-      case 64: return launch<64, false, true>(k, s);
-      default: return launch<128, false, true>(k, s);
-    }
-  }
+int launch_f16x3(const ConvK& k, int tile_n, bool cin4, hipStream_t s) {   // k.in_fmt == 0: the entry point sends split32 inputs elsewhere
   switch (tile_n) {
-    case 32: return launch<32, false, false>(k, s);
-    case 64: return launch<64, false, false>(k, s);
-    default: return launch<128, false, false>(k, s);
+    case 32: return cin4 ? launch<32, true>(k, s) : launch<32, false>(k, s);
+    case 64: return cin4 ? launch<64, true>(k, s) : launch<64, false>(k, s);
+    default: return cin4 ? launch<128, true>(k, s) : launch<128, false>(k, s);
   }
 }
 

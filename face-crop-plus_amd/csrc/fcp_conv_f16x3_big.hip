@@ -25,19 +25,10 @@ using namespace fcp_conv;
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BMB = 256;          // rows per workgroup tile
 constexpr int NT = 512;           // threads per workgroup
 constexpr int ROWB = 128;         // bytes per LDS row (32 hi + 32 lo binary16)
 constexpr int STAGE = 1 << 16;    // stage stride (power of two: the stage toggles by XOR)
-
-template <int IMM>
-__device__ __forceinline__ f16x8 lds_read128(unsigned addr) {
-  f16x8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(IMM));
-  return v;
-}
 
 template <int BN>
 __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
@@ -66,8 +57,7 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
     const int rbase = (bid / p.round_size) * p.round_size;
     const int nr = nb - rbase < p.round_size ? nb - rbase : p.round_size;
     const int bi = bid - rbase;
-    const int q8 = nr >> 3, r8 = nr & 7, xcd = bi & 7;
-    const int logical = rbase + (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bi >> 3);
+    const int logical = rbase + xcd_tile_order(nr, bi);
     tile_n = logical % p.grid_n;
     const int tile_m = logical / p.grid_n;
     m_start = tile_m < p.mfull ? tile_m * BMB : p.mfull * BMB + (tile_m - p.mfull) * p.tail_rows;
@@ -84,30 +74,30 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
   const int csrc = (tid & 7) ^ (((lrow >> 1) & 7) ^ ((lrow & 1) << 2));
 
   const int hw = p.out_h * p.out_w;
-  TapPiece tp[A_LD];
+  RowPiece pc[A_LD];
   unsigned base2[A_LD];   // second source of a 1x1 conv (channels >= csplit), or unused
-  unsigned woff[B_LD];
+  unsigned rowoff[A_LD], woff[B_LD];
   auto setup_tile = [&]() {                                      // operand addresses of the tile (tile_n, m_start, m_end)
+    // (conv_row / make_row_piece spelt out: through the helpers' structs each of the three kernels spills one more SGPR,
+    //  profiles/conv_walk.md; without in_up2 only the piece's tp is ever read)
 #pragma unroll
-  for (int i = 0; i < A_LD; ++i) {
-    const int m = m_start + lrow + 64 * i;
-    unsigned pbase = 0;
-    int hi0 = -(1 << 28), wi0 = 0;
-    base2[i] = 0xFFFFFFFFu;
-    if (m < m_end) {
-      const int ni = m / hw;
-      const int rem = m - ni * hw;
-      const int ho = rem / p.out_w;
-      const int wo = rem - ho * p.out_w;
-      pbase = (unsigned)(ni * p.ph * p.pw);
-      hi0 = ho * p.stride - p.pad_h;
-      wi0 = wo * p.stride - p.pad;
-      if (p.in2 != nullptr)
-        base2[i] = (((unsigned)(ni * p.ph2 + ho * p.stride2) * (unsigned)p.pw2 + (unsigned)(wo * p.stride2)) * (unsigned)p.in2_ld +
-                    (unsigned)(csrc * 4)) * 4u;
+    for (int i = 0; i < A_LD; ++i) {
+      const int m = m_start + lrow + 64 * i;
+      unsigned pbase = 0;
+      int hi0 = -(1 << 28), wi0 = 0;
+      base2[i] = 0xFFFFFFFFu;
+      if (m < m_end) {
+        int ni, ho, wo;
+        conv_out_pixel(p, m, hw, ni, ho, wo);
+        pbase = (unsigned)(ni * p.ph * p.pw);
+        hi0 = ho * p.stride - p.pad_h;
+        wi0 = wo * p.stride - p.pad;
+        if (p.in2 != nullptr)
+          base2[i] = (((unsigned)(ni * p.ph2 + ho * p.stride2) * (unsigned)p.pw2 + (unsigned)(wo * p.stride2)) * (unsigned)p.in2_ld +
+                      (unsigned)(csrc * 4)) * 4u;
+      }
+      pc[i].tp = make_tap_piece<false>(p, pbase, hi0, wi0, (unsigned)(csrc * 4));
     }
-    tp[i] = make_tap_piece<false>(p, pbase, hi0, wi0, (unsigned)(csrc * 4));
-  }
 #pragma unroll
     for (int i = 0; i < B_LD; ++i) woff[i] = (unsigned)(((tile_n * BN + lrow + 64 * i) * p.wrow + csrc * 4) * 4);
   };
@@ -115,70 +105,36 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
   __amdgpu_buffer_rsrc_t rs_in2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in2 ? p.in2 : p.in), 0, p.in2_bytes, 0x00020000);
   __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
   __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
-  unsigned rowoff[A_LD];
-  auto set_tap = [&](int tap, int kh_i, int kw_i) {
-    const unsigned tapoff = (unsigned)((kh_i * p.pw + kw_i) * p.in_ld) * 4u;
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) rowoff[i] = ((tp[i].mask >> tap) & 1u) ? tp[i].base + tapoff : 0xFFFFFFFFu;
-  };
-  int tap = 0, kh_i = 0, kw_i = 0, c0 = 0;
-  auto advance = [&]() {
-    ++tap;
-    if (++kw_i >= p.kw) {
-      kw_i = 0;
-      if (++kh_i >= p.kh) { kh_i = 0; tap = 0; c0 += BK; }
-    }
-    set_tap(tap, kh_i, kw_i);
-  };
-  // one slice: A_LD + B_LD DMA instructions per wave, each 64 lanes x 16 B = rows 8*wave + 64*i .. +7
-  auto dma_slice = [&](int kt, int stage) {
+  TapWalk tw;
+  auto advance = [&]() { next_tap<false, false>(p, tw, pc, rowoff); };   // (no in_up2 form: the entry point keeps it off this kernel)
+  auto dma = [&](int kt, int stage) {    // slice kt (the walk is at it) -> LDS stage
     char* a = lds + stage * STAGE + wave_u * 8 * ROWB;
-    char* b = a + BMB * ROWB;
-    if (c0 >= p.csplit) {                  // wave-uniform: this slice comes from the second source
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        const unsigned ro = base2[i];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in2, (__attribute__((address_space(3))) void*)(a + 64 * i * ROWB), 16,
-                                                 (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)((c0 - p.csplit) * 4)), 0, 0, FCP_AUX_A);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        const unsigned ro = rowoff[i];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (__attribute__((address_space(3))) void*)(a + 64 * i * ROWB), 16,
-                                                 (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)(c0 * 4)), 0, 0, FCP_AUX_A);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(b + 64 * i * ROWB), 16,
-                                               (int)(woff[i] + (unsigned)(kt * BK * 4)), 0, 0, FCP_AUX_B);
+    dma_slice<64>(p, rs_in, rs_in2, rs_w, a, a + BMB * ROWB, rowoff, base2, woff, tw.c0, kt);
   };
 
   f32x16 acc[TM][TN];
 
   // fragment addresses (stage 0); the stage toggles by XOR with STAGE
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds;
-  const int rsw = (((lane & 31) >> 1) & 7) ^ ((lane & 1) << 2);
-  const int half = lane >> 5;
+  int offH[2], offL[2];
+  frag_offsets(lane, offH, offL);
   const unsigned arow = lds0 + (unsigned)((wm * WTM + (lane & 31)) * ROWB);
   const unsigned brow = lds0 + (unsigned)((BMB + wn * WTN + (lane & 31)) * ROWB);
   unsigned aH[2], aL[2], bH[2], bL[2];   // [k-half]
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const unsigned oh = (unsigned)(((2 * s + half) ^ rsw) << 4), ol = (unsigned)(((4 + 2 * s + half) ^ rsw) << 4);
-    aH[s] = arow + oh; aL[s] = arow + ol;
-    bH[s] = brow + oh; bL[s] = brow + ol;
+    aH[s] = arow + (unsigned)offH[s]; aL[s] = arow + (unsigned)offL[s];
+    bH[s] = brow + (unsigned)offH[s]; bL[s] = brow + (unsigned)offL[s];
   }
 
   // a tile's first two slices in flight (stages 0 and 1 are free: called at kernel start and after a tile's last barrier)
   auto prefetch_tile = [&]() {
-    tap = 0; kh_i = 0; kw_i = 0; c0 = 0;
-    set_tap(0, 0, 0);
-    dma_slice(0, 0);
+    tw = TapWalk();
+    set_tap<false, false>(p, tw, pc, rowoff);
+    dma(0, 0);
     if (p.ktiles > 1) {
       advance();
-      dma_slice(1, 1);
+      dma(1, 1);
     }
   };
   prefetch_tile();
@@ -194,13 +150,13 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
     constexpr int set = decltype(set_c)::value;
     fcp_static_for<0, TMA>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
-      fah[set][i] = lds_read128<i * 32 * ROWB>(aH[set] ^ stage_xor);
-      fal[set][i] = lds_read128<i * 32 * ROWB>(aL[set] ^ stage_xor);
+      fah[set][i] = lds_read128i<i * 32 * ROWB>(aH[set] ^ stage_xor);
+      fal[set][i] = lds_read128i<i * 32 * ROWB>(aL[set] ^ stage_xor);
     });
     fcp_static_for<0, TN>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      fbh[set][j] = lds_read128<j * 32 * ROWB>(bH[set] ^ stage_xor);
-      fbl[set][j] = lds_read128<j * 32 * ROWB>(bL[set] ^ stage_xor);
+      fbh[set][j] = lds_read128i<j * 32 * ROWB>(bH[set] ^ stage_xor);
+      fbl[set][j] = lds_read128i<j * 32 * ROWB>(bL[set] ^ stage_xor);
     });
   };
   constexpr std::integral_constant<int, 0> SET0{};
@@ -229,12 +185,12 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
         ) {
           if constexpr (r < 2 * TMA) {
             constexpr int ii = r / 2;
-            if constexpr (r % 2 == 0) fah[ls][ii] = lds_read128<ii * 32 * ROWB>(aH[ls] ^ stage_xor);
-            else fal[ls][ii] = lds_read128<ii * 32 * ROWB>(aL[ls] ^ stage_xor);
+            if constexpr (r % 2 == 0) fah[ls][ii] = lds_read128i<ii * 32 * ROWB>(aH[ls] ^ stage_xor);
+            else fal[ls][ii] = lds_read128i<ii * 32 * ROWB>(aL[ls] ^ stage_xor);
           } else {
             constexpr int jj = (r - 2 * TMA) / 2;
-            if constexpr (r % 2 == 0) fbh[ls][jj] = lds_read128<jj * 32 * ROWB>(bH[ls] ^ stage_xor);
-            else fbl[ls][jj] = lds_read128<jj * 32 * ROWB>(bL[ls] ^ stage_xor);
+            if constexpr (r % 2 == 0) fbh[ls][jj] = lds_read128i<jj * 32 * ROWB>(bH[ls] ^ stage_xor);
+            else fbl[ls][jj] = lds_read128i<jj * 32 * ROWB>(bL[ls] ^ stage_xor);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -266,14 +222,14 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
     const bool dma_first = wave_u >= 4;
     if (dma_first && kt + 2 < p.ktiles) {
       advance();
-      dma_slice(kt + 2, kt & 1);
+      dma(kt + 2, kt & 1);
     }
     __builtin_amdgcn_sched_barrier(0);
     mfmas_reads(SET1, SET0, sx ^ (unsigned)STAGE);
     __builtin_amdgcn_sched_barrier(0);
     if (!dma_first && kt + 2 < p.ktiles) {
       advance();
-      dma_slice(kt + 2, kt & 1);
+      dma(kt + 2, kt & 1);
     }
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -288,12 +244,7 @@ __global__ void __launch_bounds__(NT, 1) conv_igemm_f16x3_big(const ConvK p) {
   __builtin_amdgcn_sched_barrier(0);
   tm_act = (m_end - m_start - wm * WTM + 31) >> 5;
   tm_act = __builtin_amdgcn_readfirstlane(tm_act < 0 ? 0 : (tm_act > TM ? TM : tm_act));
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  clear_acc(acc);
   fcp_static_for<0, TM + 1>([&](auto tc) {
     if (tm_act == decltype(tc)::value) main_loop(tc);
   });

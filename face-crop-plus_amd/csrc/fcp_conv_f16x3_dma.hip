@@ -17,8 +17,6 @@ using namespace fcp_conv;
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int NST = 2;   // LDS stages (three were measured slower: they cost an occupancy step)
 
 // EP8: the output or a residual is split32 (cout % 8 == 0): the tile is accumulated transposed (filters x pixels — same bits) and
@@ -38,10 +36,7 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : 3)) conv_igemm_f16x3_dma
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* lds = reinterpret_cast<char*>(smem);
 
-  const int nb = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_tile_order(gridDim.x, blockIdx.x);
   const int tile_n = logical % p.grid_n;
   const int tile_m = logical / p.grid_n;
 
@@ -53,123 +48,37 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : 3)) conv_igemm_f16x3_dma
   const int lrow = tid >> 3;                                     // 0..31 (+32 i)
   const int csrc = (tid & 7) ^ (((lrow >> 1) & 7) ^ ((lrow & 1) << 2));   // source chunk of LDS position tid & 7
 
-  unsigned pbase[A_LD];
-  int hi0[A_LD], wi0[A_LD];
   const int hw = p.out_h * p.out_w;
-#pragma unroll
-  for (int i = 0; i < A_LD; ++i) {
-    const int m = tile_m * BM + lrow + 32 * i;
-    if (m < p.M) {
-      const int ni = m / hw;
-      const int rem = m - ni * hw;
-      const int ho = rem / p.out_w;
-      const int wo = rem - ho * p.out_w;
-      pbase[i] = (unsigned)(ni * p.ph * p.pw);
-      hi0[i] = ho * p.stride - p.pad_h;
-      wi0[i] = wo * p.stride - p.pad;
-    } else {
-      pbase[i] = 0;
-      hi0[i] = -(1 << 28);
-      wi0[i] = 0;
-    }
-  }
   __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
   __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
   // optional second source (1x1 convs): channels >= csplit come from in2 sampled at stride2
   __amdgpu_buffer_rsrc_t rs_in2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in2 ? p.in2 : p.in), 0, p.in2_bytes, 0x00020000);
-  unsigned base2[A_LD];
+  RowPiece pc[A_LD];
+  unsigned base2[A_LD], rowoff[A_LD], woff[B_LD];
 #pragma unroll
   for (int i = 0; i < A_LD; ++i) {
-    const int m = tile_m * BM + lrow + 32 * i;
-    base2[i] = 0xFFFFFFFFu;
-    if (p.in2 != nullptr && m < p.M) {
-      const int ni = m / hw;
-      const int rem = m - ni * hw;
-      const int ho = rem / p.out_w;
-      const int wo = rem - ho * p.out_w;
-      base2[i] = (((unsigned)(ni * p.ph2 + ho * p.stride2) * (unsigned)p.pw2 + (unsigned)(wo * p.stride2)) * (unsigned)p.in2_ld +
-                  (unsigned)(csrc * 4)) * 4u;
-    }
+    const ConvRow r = conv_row(p, tile_m * BM + lrow + 32 * i, p.M, hw, (unsigned)(csrc * 4));
+    pc[i] = make_row_piece<false>(p, r, 0, (unsigned)(csrc * 4));
+    base2[i] = r.base2;
   }
-  unsigned woff[B_LD];
 #pragma unroll
   for (int i = 0; i < B_LD; ++i) woff[i] = (unsigned)(((tile_n * BN + lrow + 32 * i) * p.wrow + csrc * 4) * 4);
-  TapPiece tp[A_LD];
-  unsigned rowoff[A_LD];
-#pragma unroll
-  for (int i = 0; i < A_LD; ++i) tp[i] = make_tap_piece<false>(p, pbase[i], hi0[i], wi0[i], (unsigned)(csrc * 4));
-  auto set_tap = [&](int tap, int kh_i, int kw_i) {
-    if (p.in_up2) {
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        int hi = hi0[i] + kh_i;
-        int wi = wi0[i] + kw_i;
-        const bool ok = (unsigned)hi < (unsigned)p.in_h && (unsigned)wi < (unsigned)p.in_w;
-        hi >>= 1; wi >>= 1;
-        const unsigned pix = pbase[i] + (unsigned)(hi * p.pw + wi);
-        rowoff[i] = ok ? (pix * (unsigned)p.in_ld + (unsigned)(csrc * 4)) * 4u : 0xFFFFFFFFu;
-      }
-    } else {
-      const unsigned tapoff = (unsigned)((kh_i * p.pw + kw_i) * p.in_ld) * 4u;
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) rowoff[i] = ((tp[i].mask >> tap) & 1u) ? tp[i].base + tapoff : 0xFFFFFFFFu;
-    }
-  };
-  int tap = 0, kh_i = 0, kw_i = 0, c0 = 0;
-  auto advance = [&]() {
-    ++tap;
-    if (++kw_i >= p.kw) {
-      kw_i = 0;
-      if (++kh_i >= p.kh) { kh_i = 0; tap = 0; c0 += BK; }
-    }
-    set_tap(tap, kh_i, kw_i);
-  };
-  // one slice: A_LD + B_LD DMA instructions per wave, each 64 lanes x 16 B = rows 8*wave + 32*i .. +7
-  auto dma_slice = [&](int kt, int stage) {
+  TapWalk tw;
+  auto dma = [&](int kt, int stage) {    // slice kt (the walk is at it) -> LDS stage
     char* a = lds + stage * STAGE + wave_u * 8 * ROWB;
-    char* b = a + BM * ROWB;
-    if (c0 >= p.csplit) {                  // wave-uniform: this slice comes from the second source
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        const unsigned ro = base2[i];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in2, (__attribute__((address_space(3))) void*)(a + 32 * i * ROWB), 16,
-                                                 (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)((c0 - p.csplit) * 4)), 0, 0, FCP_AUX_A);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        const unsigned ro = rowoff[i];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (__attribute__((address_space(3))) void*)(a + 32 * i * ROWB), 16,
-                                                 (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)(c0 * 4)), 0, 0, FCP_AUX_A);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(b + 32 * i * ROWB), 16,
-                                               (int)(woff[i] + (unsigned)(kt * BK * 4)), 0, 0, FCP_AUX_B);
+    dma_slice<32>(p, rs_in, rs_in2, rs_w, a, a + BM * ROWB, rowoff, base2, woff, tw.c0, kt);
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  clear_acc(acc);
 
   const int aoff = (wm * WTM + (lane & 31)) * ROWB;
   const int boff = BM * ROWB + (wn * WTN + (lane & 31)) * ROWB;
-  const int rsw = (((lane & 31) >> 1) & 7) ^ ((lane & 1) << 2);
-  const int half = lane >> 5;
   int offH[2], offL[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    offH[s] = ((2 * s + half) ^ rsw) << 4;
-    offL[s] = ((4 + 2 * s + half) ^ rsw) << 4;
-  }
+  frag_offsets(lane, offH, offL);
 
-  set_tap(0, 0, 0);
-  dma_slice(0, 0);
+  set_tap<false, true>(p, tw, pc, rowoff);
+  dma(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
@@ -197,10 +106,10 @@ __global__ void __launch_bounds__(256, (BN == 128 ? 2 : 3)) conv_igemm_f16x3_dma
     const int ahead = kt + NST - 1;
     const bool issue = ahead < p.ktiles;
     if (issue) {
-      advance();
+      next_tap<false, true>(p, tw, pc, rowoff);
       int st = stage + NST - 1;
       if (st >= NST) st -= NST;
-      dma_slice(ahead, st);
+      dma(ahead, st);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll

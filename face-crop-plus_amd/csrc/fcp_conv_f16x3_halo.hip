@@ -39,8 +39,6 @@ using namespace fcp_conv;
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int TH = 8, TW = 32;            // output patch
 constexpr int HW_ = TW + 2;               // halo patch width (34); height TH + 2 = 10
 constexpr int HROWS = 344;                // 340 halo rows padded to a multiple of 8
@@ -51,12 +49,6 @@ constexpr int B_OFF = 2 * A_BYTES;        // filter buffers follow the two halo 
 constexpr int LDS_TOTAL = 2 * A_BYTES + 2 * B_BYTES;   // 161792
 constexpr int A_LD = 11;                  // halo DMA instructions per thread: 2752 16-byte pieces / 256 (last: waves 0..2)
 
-template <int IMM>
-__device__ __forceinline__ f16x8 lds_read128i(unsigned addr) {
-  f16x8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(IMM));
-  return v;
-}
 __device__ __forceinline__ int swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
 // epilogue LDS accesses, also inline asm: the next tile's first DMA is in flight while the fp32 tile is staged
 __device__ __forceinline__ void lds_write32(unsigned addr, float v) { asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }

@@ -1,11 +1,16 @@
 """The cases of tests/test_conv_epilogue_bits_gpu.py and of its fixture generator (tests/golden/make_golden_conv_epilogue.py):
 one list, and the one function that runs a case.
 
-A case is a launch set that ends in every form of the fused conv epilogue (acc * wscale + bias, residual before / after the
-activation, leaky slope, alpha, second residual): the three generic epilogues behind every generic kernel, the halo-tile kernels,
-the bottleneck-chain forms and the fused stem + pool + conv1.  Inputs, filters, bias and residuals come from
-``numpy.random.default_rng(seed)`` (mean zero; the seed is the CRC of the case id); tiles are explicit, so the autotuner plays
-no part.  ``run_case`` returns, per tile choice, the raw bytes of every output buffer as int32 tensors.
+The epilogue cases are launch sets that end in every form of the fused conv epilogue (acc * wscale + bias, residual before /
+after the activation, leaky slope, alpha, second residual): the three generic epilogues behind every generic kernel, the halo-tile
+kernels, the bottleneck-chain forms and the fused stem + pool + conv1.  The walk cases (``_walk_rows``) hold the epilogue at one
+setting and vary what the front half of the generic kernels keeps books on (fcp_conv_common.h: xcd_tile_order, conv_row,
+TapWalk, set_tap, dma_slice): stride, 25 taps, one / two / three K slices, an image boundary inside a ragged M tile, the
+nearest-x2 fetch, the 3-channel NHWC4 mode, row bands, a second source, and flat 64-bit addressing.
+
+Inputs, filters, bias and residuals come from ``numpy.random.default_rng(seed)`` (mean zero; the seed is the CRC of the case
+id); tiles are explicit, so the autotuner plays no part.  ``run_case`` returns, per tile choice, the raw bytes of every output
+buffer as int32 tensors.
 """
 import zlib
 
@@ -23,10 +28,47 @@ NO_RESIZE = ("a_relu", "b_relu_res1pre", "d_leaky_alpha_res1post_res2", "e_nobia
 NO_RES = ("a_relu", "e_nobias_id")                                                         # halo wide above 64 filters: no residual inputs
 
 T128 = [(128, 32), (128, 64), (128, 128)]
+WALK = ("a_relu",)                                                                         # the walk rows: one epilogue setting
+
+
+def _walk_rows():
+    """Rows about the im2col walk, at the smallest shapes at which its bookkeeping can go wrong.  Keys beyond those of the
+    epilogue rows: stride, pad (default k // 2), in_up2 (h, w are the PHYSICAL size), band, x2 = (channels, h, w, stride) of a
+    second source, flat, cin4 (cin 3 in an NHWC4 buffer)."""
+    f32 = dict(precision="f32", in_fmt=0, out_fmt=0, cout=40, tiles=T128, settings=WALK)             # conv_igemm_f32
+    f16 = dict(precision="f16x3", in_fmt=0, out_fmt=0, cout=40, tiles=T128, settings=WALK)           # conv_igemm_f16x3 (fp32 input)
+    dma = dict(precision="f16x3", in_fmt=1, out_fmt=1, cout=64, tiles=T128, settings=WALK)           # conv_igemm_f16x3_dma
+    big = dict(precision="f16x3", in_fmt=1, out_fmt=1, cout=128, settings=WALK,                       # conv_igemm_f16x3_big
+               tiles=[(128, 128), (256, 128), (256, 128, "bal")])
+    rows = []
+    # stride 2, 9 x 11 -> 5 x 6: two channel slices x nine taps, and both images inside one M tile
+    s2 = dict(cin=64, k=3, stride=2, n=2, h=9, w=11)
+    rows += [("walk_s2_f32", dict(f32, **s2)), ("walk_s2_f16x3", dict(f16, **s2)), ("walk_s2_dma_out0", dict(dma, out_fmt=0, **s2)),
+             ("walk_s2_dma_out1", dict(dma, **s2)), ("walk_s2_big", dict(big, **s2))]
+    for name, kern in (("f32", f32), ("f16x3", f16), ("dma", dma)):
+        rows.append((f"walk_k5_{name}", dict(kern, cin=32, k=5, n=1, h=9, w=11)))                      # 25 taps: mask bits above 9
+        for cin in (32, 64, 96):                                      # ktiles 1 (prologue only), 2, 3 (odd: the pair's second step is skipped)
+            rows.append((f"walk_k1_cin{cin}_{name}", dict(kern, cin=cin, k=1, n=1, h=9, w=11)))
+        rows.append((f"walk_up2_{name}", dict(kern, cin=64, k=3, n=2, h=5, w=6, in_up2=True)))        # physical 5 x 6 read as 10 x 12
+    # M = 198: one whole and one ragged 128-row tile with the image change inside the first; one ragged 256-row tile
+    rows.append(("walk_ragged_k3", dict(big, cin=64, k=3, n=2, h=9, w=11, tiles=T128 + big["tiles"][1:])))
+    for name, kern in (("f32", f32), ("f16x3", f16)):                 # 3 channels in an NHWC4 buffer; 7 x 7: ktiles 7, kw near its limit of 8
+        rows.append((f"walk_cin4_k3_{name}", dict(kern, cin=3, cin4=True, k=3, n=2, h=9, w=11)))
+        rows.append((f"walk_cin4_k7s2_{name}", dict(kern, cin=3, cin4=True, k=7, stride=2, n=2, h=9, w=11)))
+    for band in ((1, 0), (0, 1), (1, 1)):                             # 9 input rows -> 8, 8, 7 output rows
+        for name, kern in (("f32", f32), ("f16x3", f16), ("dma", dma), ("big", big)):
+            rows.append((f"walk_band{band[0]}{band[1]}_{name}", dict(kern, cin=64, k=3, n=2, h=9, w=11, band=band)))
+    # second source of a 1x1 conv: 64 channels of x, then 32 channels of x2 sampled at stride 2
+    rows.append(("walk_two_source", dict(big, cin=96, k=1, n=2, h=5, w=6, x2=(32, 9, 11, 2), tiles=T128 + big["tiles"][1:])))
+    flat = dict(f32, flat=True)                                       # the fp32 kernel's 64-bit flat addressing
+    rows += [("walk_s2_f32_flat", dict(flat, **s2)), ("walk_up2_f32_flat", dict(flat, cin=64, k=3, n=2, h=5, w=6, in_up2=True)),
+             ("walk_cin4_k3_f32_flat", dict(flat, cin=3, cin4=True, k=3, n=2, h=9, w=11)),
+             ("walk_cin4_k7s2_f32_flat", dict(flat, cin=3, cin4=True, k=7, stride=2, n=2, h=9, w=11))]
+    return rows
 
 
 def _generic_rows():
-    """(row id, dict(precision, in_fmt, out_fmt, cin, cout, k, n, h, w, tiles, settings[, out_c0, balance]))"""
+    """(row id, dict(precision, in_fmt, out_fmt, cin, cout, k, n, h, w, tiles, settings[, out_c0, balance])), then the walk rows"""
     rows = []
     for cout in (19, 40):                                             # conv_igemm_f32 -> conv_epilogue (19: scalar tail)
         for k in (3, 1):
@@ -54,7 +96,7 @@ def _generic_rows():
         for cout in (72, 128):                                        # halo wide (1, 128): no residual inputs
             rows.append((f"halowide128_c{cout}_{h}x{w}", dict(precision="f16x3", in_fmt=1, out_fmt=int(cout % 32 == 0), cin=128, cout=cout, k=3, n=2, h=h, w=w,
                                                               tiles=[(128, 64), (128, 128), (1, 128)], settings=NO_RES)))
-    return rows
+    return rows + _walk_rows()
 
 
 def cases():
@@ -96,28 +138,34 @@ def _conv(E, torch, device, case_id, s):
     rng = _rng(case_id)
     st = SETTINGS[s["setting"]]
     n, h, w, cin, cout, k = s["n"], s["h"], s["w"], s["cin"], s["cout"], s["k"]
+    stride, pad, up2, band, x2s = s.get("stride", 1), s.get("pad", k // 2), s.get("in_up2", False), s.get("band", (0, 0)), s.get("x2")
+    in_h, in_w = (2 * h, 2 * w) if up2 else (h, w)
+    oh, ow = (in_h - band[0] - band[1] + 2 * pad - k) // stride + 1, (in_w + 2 * pad - k) // stride + 1      # = h, w in the epilogue rows
     wt = rng.standard_normal((cout, cin, k, k), dtype=np.float32) * np.float32((2.0 / (cin * k * k)) ** 0.5)
     bias = rng.standard_normal(cout, dtype=np.float32) * np.float32(0.5) if st["bias"] else None
-    pc = E.pack_conv(wt, bias, None, 1, k // 2, device, precision=s["precision"])
-    x = _act(E, torch, device, rng, n, h, w, cin, s["in_fmt"])
+    pc = E.pack_conv(wt, bias, None, stride, pad, device, precision=s["precision"])
+    assert pc.cin4 == s.get("cin4", False)
+    x = _act(E, torch, device, rng, n, h, w, 4 if pc.cin4 else cin - (x2s[0] if x2s else 0), s["in_fmt"])
+    x2 = _act(E, torch, device, rng, n, x2s[1], x2s[2], x2s[0], 1) if x2s else None
     rfmt = s["out_fmt"]                                               # residuals in the output's format
     res1 = res2 = None
     if st["res1"] is not None:
-        rh, rw = ((h + 1) // 2, (w + 1) // 2) if st["res1"] == "post_resized" else (h, w)      # 9 x 11 -> 5 x 6
+        rh, rw = ((oh + 1) // 2, (ow + 1) // 2) if st["res1"] == "post_resized" else (oh, ow)      # 9 x 11 -> 5 x 6
         res1 = _act(E, torch, device, rng, n, rh, rw, cout, rfmt)
     if st["alpha2"] is not None:
-        res2 = _act(E, torch, device, rng, n, h, w, cout, rfmt)
+        res2 = _act(E, torch, device, rng, n, oh, ow, cout, rfmt)
     outs = {}
     for tile in s["tiles"]:
         ld, c0 = s.get("out_ld", cout), s.get("out_c0", 0)
-        buf = torch.full((n, h, w, ld), 7.0, dtype=torch.float32, device=device)      # sentinel: channels outside the view keep it
+        buf = torch.full((n, oh, ow, ld), 7.0, dtype=torch.float32, device=device)      # sentinel: channels outside the view keep it
         out = E.Act(buf, c0, cout, s["out_fmt"])
         E.conv(pc, x, out, act_slope=st["slope"], alpha=st["alpha"], res1=res1, res1_pre=st["res1"] == "pre", res2=res2,
-               alpha2=st["alpha2"] if st["alpha2"] is not None else 1.0, tile_m=tile[0], tile_n=tile[1], balance_tail=len(tile) > 2)
+               alpha2=st["alpha2"] if st["alpha2"] is not None else 1.0, tile_m=tile[0], tile_n=tile[1], balance_tail=len(tile) > 2,
+               in_up2=up2, band=band, x2=x2, x2_stride=x2s[3] if x2s else 1, flat=s.get("flat", False))
         outs["x".join(map(str, tile))] = [_raw(torch, buf)]
     torch.cuda.synchronize()
     info = dict(fmt=s["out_fmt"], view=(s.get("out_c0", 0), cout),
-                res1_smaller=None if st["res1"] != "post_resized" else (res1.h < h and res1.w < w))
+                res1_smaller=None if st["res1"] != "post_resized" else (res1.h < oh and res1.w < ow))
     return outs, info
 
 

@@ -1,12 +1,18 @@
-"""The fused conv epilogue returns the bits it returned before its arithmetic was stated once (fcp_conv_common.h: conv_value).
+"""The conv kernels return the bits they returned before their shared code was stated once (fcp_conv_common.h): the fused
+epilogue's arithmetic (conv_value) and the generic kernels' im2col walk (xcd_tile_order, conv_row, TapWalk / set_tap, dma_slice).
 
 ``torch.equal`` treats -0.0 and 0.0 as equal and no other test compares a commit with its parent, so every case of
-tests/conv_epilogue_cases.py — each generic epilogue behind each generic kernel under five epilogue settings, the halo-tile
-kernels, the bottleneck-chain forms, the fused stem + pool + conv1 — asserts
+tests/conv_epilogue_cases.py asserts
 
 1. that every tile choice offered for the shape gives the same BYTES (compared as int32), and
 2. that their sha256 is the one in tests/golden/conv_epilogue_bits.json, recorded on an MI355X at the parent commit by
    tests/golden/make_golden_conv_epilogue.py.  A case without a recorded hash fails.
+
+The epilogue cases: each generic epilogue behind each generic kernel under five epilogue settings, the halo-tile kernels, the
+bottleneck-chain forms, the fused stem + pool + conv1 (hashes from the parent of the commit that gathered the epilogue).  The
+walk cases, under one epilogue setting: stride 2, 25 taps, one / two / three K slices, a ragged M tile across an image boundary,
+the nearest-x2 fetch, the 3-channel NHWC4 mode, row bands, a second source and flat addressing, each on every generic kernel
+that takes it (hashes from the parent of the commit that gathered the walk, which reproduced the older ones).
 
 A ReLU case must hold at least one -0.0 (a negative pre-activation times slope 0: part of the epilogue's contract) and one
 positive value, a resized-residual case a residual map smaller than the output: no case passes trivially.
