@@ -138,6 +138,18 @@ def write_image(path: str, image: np.ndarray, jpeg: JpegSettings | None = None) 
     return True
 
 
+def read_slots(out, lengths, fitted, overflowed) -> list:
+    """The way back from the device encoders: out (F, capacity) u8 device slots and lengths (F,) int32 device, as
+    ``encode_scans`` / ``encode_streams`` left them -> one entry per face, ``fitted(i, stream bytes)`` where the stream fits
+    its slot and ``overflowed(i)`` where it does not.  What comes to the host is the lengths and, in one read, the part of
+    the slots that is used."""
+    lengths = lengths.cpu().numpy()
+    fits = lengths <= out.shape[1]
+    used = int(lengths[fits].max()) if fits.any() else 0
+    slots = out[:, :used].cpu().numpy() if used else None
+    return [fitted(i, slots[i, :lengths[i]].tobytes()) if fits[i] else overflowed(i) for i in range(len(lengths))]
+
+
 def write_bytes(path: str, data) -> bool:
     """An already encoded file (``Cropper(encoder="device")``: header + the stream the GPU wrote) -> disk, through a
     temporary name so that a failed write never leaves a truncated image behind."""

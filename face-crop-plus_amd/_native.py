@@ -163,3 +163,28 @@ def ptr(t, byte_offset: int = 0):
     if t is None:
         return C.c_void_p(0)
     return C.c_void_p(t.data_ptr() + byte_offset)
+
+
+def encode_slots(who: str, entry: str, pixels_dev, out, op, workspace_bytes, call):
+    """What the calls of the device encoders (``jpegenc.encode_scans``, ``pngenc.encode_streams``) share: pixels (F,H,W[,C])
+    u8 device, out (F, capacity) u8 device -> lengths (F,) int32 device.  ``op``: the torch.ops call when that boundary is
+    on, else None; ``workspace_bytes(f, h, w, c)``: the entry point's sizer (negative for sizes it refuses, whose message
+    ``entry`` then carries); ``call(sizes, slots, work)``: the entry point over (f, h, w, c), (out, out_stride, capacity,
+    lengths) and (workspace, workspace_bytes, stream)."""
+    import torch
+    assert pixels_dev.dtype == torch.uint8 and pixels_dev.is_contiguous() and pixels_dev.dim() in (3, 4)
+    assert out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == pixels_dev.shape[0]
+    if op is not None:
+        return op()
+    f, h, w = pixels_dev.shape[:3]
+    c = pixels_dev.shape[3] if pixels_dev.dim() == 4 else 1
+    capacity = out.shape[1]
+    if capacity and out.stride(1) != 1:
+        raise RuntimeError(f"{who}: the bytes of a row of out must be contiguous")
+    lengths = torch.empty((f,), dtype=torch.int32, device=pixels_dev.device)
+    need = workspace_bytes(f, h, w, c)
+    check(-1 if need < 0 else 0, entry)
+    work = torch.empty((need,), dtype=torch.uint8, device=pixels_dev.device)
+    check(call((f, h, w, c), (ptr(out) if capacity else None, out.stride(0) if f > 1 else capacity, capacity, ptr(lengths)),
+               (ptr(work), need, stream_ptr())), entry)
+    return lengths

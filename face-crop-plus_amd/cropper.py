@@ -18,7 +18,7 @@ import torch
 from . import align, trace
 from . import clahe as equalizing
 from . import matte as matting
-from ._io_codec import JpegSettings, check_jpeg_settings, write_bytes
+from ._io_codec import _ENCODER_KW, JpegSettings, check_jpeg_settings, write_bytes
 from .batch import batch_geometry, build_batch, upload_sources
 from .utils import get_ldm_slices, parse_landmarks_file, read_image, read_images, write_image
 
@@ -588,19 +588,19 @@ class Cropper:
                     row_of.setdefault(face, row)
                 self.save_group([mask_rows[row_of[i]] for i in cell], sources, cell_dir + "_mask")
 
-    def _is_jpeg_target(self, file_names):
-        """Per source file name: whether the face cut from it is written as a JPEG (``_target_paths``' extension rule)."""
-        from .jpegenc import JPEG_EXTENSIONS
+    def _is_target(self, file_names, fmt):
+        """Per source file name: whether the face cut from it is written in the format ``fmt`` of the encoder table, as
+        ``jpegenc.JPEG_EXTENSIONS`` / ``pngenc.PNG_EXTENSIONS`` list it (``_target_paths``' extension rule)."""
+        hit = lambda ext: _ENCODER_KW.get(ext.lower(), {}).get("format") == fmt
         if self.output_format is not None:
-            return np.full(len(file_names), ("." + self.output_format).lower() in JPEG_EXTENSIONS)
-        return np.array([os.path.splitext(str(n))[1].lower() in JPEG_EXTENSIONS for n in file_names], bool)
+            return np.full(len(file_names), hit("." + self.output_format))
+        return np.array([hit(os.path.splitext(str(n))[1]) for n in file_names], bool)
+
+    def _is_jpeg_target(self, file_names):
+        return self._is_target(file_names, "JPEG")
 
     def _is_png_target(self, file_names):
-        """Per source file name: whether the face cut from it is written as a PNG (``_target_paths``' extension rule)."""
-        from .pngenc import PNG_EXTENSIONS
-        if self.output_format is not None:
-            return np.full(len(file_names), ("." + self.output_format).lower() in PNG_EXTENSIONS)
-        return np.array([os.path.splitext(str(n))[1].lower() in PNG_EXTENSIONS for n in file_names], bool)
+        return self._is_target(file_names, "PNG")
 
     def _encode_on_device(self, pixels_dev, pixels, names):
         """``encoder="device"`` / ``png_encoder="device"``: (F,H,W[,3 or 4]) u8 device pixels (and their host copy, if one

@@ -29,16 +29,19 @@
 // They are never transformed.
 #include "fcp_block_scan.h"
 #include "fcp_common.h"
+#include "fcp_entropy.h"
 #include "fcp_hip.h"
 
 namespace {
+
+using fcp_entropy::kFib35;
+using fcp_entropy::round16;
 
 constexpr int kThreads = 256;
 constexpr int kMaxSide = 8192;          // 6 * 512 * 512 blocks * 1658 bits < 2^32: bit offsets of a face fit 32 bits
 constexpr int kMaxBlockBits = 20 + 63 * 26;   // DC: 9-bit code + 11 bits; 63 x (16-bit code + 10 bits); no ZRL can join them
 constexpr int kMaxBlockBitsOpt = 27 + 63 * 26;   // optimised tables: a DC code may be 16 bits long as well
 constexpr int kTableBytes = 272;              // a table's record: 16 counts + up to 256 symbols in code order, zero padded
-constexpr long long kFib35 = 9227465;         // a Huffman tree over fewer counts than Fibonacci(35) is at most 32 deep
 constexpr int kMaxCodeLength = 32;            // libjpeg's MAX_CLEN: the lengths its arrays hold before the limit to 16
 
 // zig-zag position -> natural (row-major) index
@@ -313,15 +316,9 @@ struct HistSink {
   __device__ __forceinline__ void ac(int set, int sym, uint32_t, int) { atomicAdd(ac_bins + set * 256 + (sym & 255), 1u); }
 };
 
-// Bits go out most significant first.  `acc` holds the `n` (< 32) bits not yet written of the word `word` points at; the
-// first word starts with the bits of the block before (zeros here: OR leaves them alone).  put() takes up to 27 bits (a
-// 16-bit DC code of an optimised table and 11 value bits): with n < 32 that is at most 58 bits in the 64 of `acc`.
-struct EmitSink {
+// Bits go out most significant first; put() takes up to 27 bits (a 16-bit DC code of an optimised table and 11 value bits).
+struct EmitSink : fcp_entropy::BitWriter<true> {
   const CodeTables* t;
-  uint32_t* word;
-  uint64_t acc = 0;
-  uint32_t n;
-  bool shared;                  // the word `word` points at may also hold bits of the block before this one
   __device__ __forceinline__ void dc(int set, int s, uint32_t bits) {
     const uint32_t e = t->dc[set][s];
     put(((e & 0xffffu) << s) | bits, (e >> 16) + s);
@@ -329,21 +326,6 @@ struct EmitSink {
   __device__ __forceinline__ void ac(int set, int sym, uint32_t bits, int s) {
     const uint32_t e = t->ac[set][sym];
     put(((e & 0xffffu) << s) | bits, (e >> 16) + s);
-  }
-  __device__ __forceinline__ void put(uint32_t code, uint32_t len) {
-    acc = (acc << len) | code;
-    n += len;
-    if (n >= 32) {
-      n -= 32;
-      const uint32_t full = (uint32_t)(acc >> n);
-      if (shared) atomicOr(word, full); else *word = full;
-      shared = false;
-      ++word;
-      acc &= (1ull << n) - 1ull;
-    }
-  }
-  __device__ __forceinline__ void finish() {                   // the tail shares its word with the block after this one
-    if (n > 0) atomicOr(word, (uint32_t)(acc << (32 - n)));
   }
 };
 
@@ -442,12 +424,8 @@ __global__ void __launch_bounds__(kThreads) jpeg_histogram_kernel(const int16_t*
   }
 }
 
-// libjpeg's jpeg_gen_optimal_table, one wave per table.  Entry i of the 257 (256 symbols and the pseudo-symbol 256 of
-// frequency 1, which keeps the all-ones code free) lives in lane i % 64, in registers.  A merge takes the two smallest
-// non-zero frequencies, ties going to the larger index: one butterfly over the lanes' (smallest, second smallest) pairs of
-// the key frequency << 9 | 511 - index.  libjpeg then walks the two `others` chains to add 1 to the code size of every
-// symbol under c1 and c2 and links them; a chain is only a set, so here every entry carries the head of its set instead:
-// each lane adds 1 to its entries under c1 or c2 and moves those under c2 to c1.  Same code sizes, no serial walk.
+// libjpeg's jpeg_gen_optimal_table, one wave per table, out of the pieces of fcp_entropy.h.  Entry 256 of the merge is
+// the pseudo-symbol of frequency 1, which keeps the all-ones code free.
 // Preconditions (a row sums to less than Fibonacci(35) - 1, so no code is longer than 32 bits) are the caller's; if they
 // do not hold the tables are meaningless but every index below is clamped into its array.
 __global__ void __launch_bounds__(64) jpeg_tables_kernel(const uint32_t* __restrict__ freq, uint8_t* __restrict__ tables,
@@ -460,12 +438,10 @@ __global__ void __launch_bounds__(64) jpeg_tables_kernel(const uint32_t* __restr
   const int lane = threadIdx.x;
   const size_t t = blockIdx.x;
   uint32_t fr[5];
-  int head[5], cs[5];
+  int cs[5];
 #pragma unroll
   for (int j = 0; j < 4; ++j) fr[j] = freq[t * 256 + lane + 64 * j];
   fr[4] = lane == 0 ? 1u : 0u;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) head[j] = lane + 64 * j, cs[j] = 0;
   for (int i = lane; i < kTableBytes; i += 64) record[i] = 0;
   if (lane <= kMaxCodeLength) bits[lane] = 0;
   if (__ballot((fr[0] | fr[1] | fr[2] | fr[3]) != 0u) == 0ull) {          // nothing to code: an all-zero record
@@ -474,35 +450,7 @@ __global__ void __launch_bounds__(64) jpeg_tables_kernel(const uint32_t* __restr
       for (int i = lane; i < 256; i += 64) codes[t * 256 + i] = 0u;
     return;
   }
-  constexpr unsigned long long kNone = ~0ull;
-  for (int merges = 0; merges < 256; ++merges) {                          // every merge empties one of 257 entries
-    unsigned long long k1 = kNone, k2 = kNone;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      if (fr[j] == 0u) continue;
-      const unsigned long long key = ((unsigned long long)fr[j] << 9) | (unsigned long long)(511 - (lane + 64 * j));
-      if (key < k1) k2 = k1, k1 = key; else if (key < k2) k2 = key;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const unsigned long long o1 = __shfl_xor(k1, off, 64), o2 = __shfl_xor(k2, off, 64);
-      const unsigned long long lo = k1 < o1 ? k1 : o1, hi = k1 < o1 ? o1 : k1, rest = k2 < o2 ? k2 : o2;
-      k1 = lo, k2 = hi < rest ? hi : rest;
-    }
-    if (k2 == kNone) break;                                               // one entry left: the tree is complete
-    const int c1 = 511 - (int)(k1 & 511ull), c2 = 511 - (int)(k2 & 511ull);
-    const uint32_t v2 = (uint32_t)(k2 >> 9);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const int idx = lane + 64 * j;
-      if (idx == c1) fr[j] += v2;
-      if (idx == c2) fr[j] = 0u;
-      if (head[j] == c1 || head[j] == c2) {
-        ++cs[j];
-        head[j] = c1;
-      }
-    }
-  }
+  fcp_entropy::huffman_code_sizes(fr, 257, cs);
 #pragma unroll
   for (int j = 0; j < 5; ++j) cs[j] = min(cs[j], kMaxCodeLength);
   __syncthreads();
@@ -513,33 +461,12 @@ __global__ void __launch_bounds__(64) jpeg_tables_kernel(const uint32_t* __restr
   for (int j = 0; j < 4; ++j) size_by_symbol[lane + 64 * j] = (uint8_t)cs[j];
   __syncthreads();
   if (lane == 0) {
-    // libjpeg's limit to 16 bits: take a pair of the longest codes away, give its prefix to one of them and split a
-    // shorter code for the other.  Signed counts and the j > 0 guard only matter when the preconditions do not hold.
-    bool sane = true;
-    for (int i = kMaxCodeLength; i > 16 && sane; --i) {
-      while (bits[i] > 0) {
-        int j = i - 2;
-        while (j > 0 && bits[j] == 0) --j;
-        if (j == 0) {
-          sane = false;
-          break;
-        }
-        bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
-      }
-    }
+    fcp_entropy::limit_code_lengths<kMaxCodeLength, 16>(bits);
     int i = 16;
     while (i > 0 && bits[i] == 0) --i;
     if (i > 0) --bits[i];                                                 // the pseudo-symbol's code is not a symbol's
-    uint32_t code = 0;
-    int pos = 0;
-    for (int len = 1; len <= 16; ++len) {
-      const int n = min(max(bits[len], 0), 255);
-      record[len - 1] = (uint8_t)n;
-      first_pos[len] = pos, first_code[len] = code;
-      pos += n;
-      code = (code + (uint32_t)n) << 1;
-    }
-    first_pos[17] = pos;
+    fcp_entropy::code_starts<16>(bits, 255, first_pos, first_code);
+    for (int len = 1; len <= 16; ++len) record[len - 1] = (uint8_t)(first_pos[len + 1] - first_pos[len]);
   }
   __syncthreads();
   // symbols in code order: by code size before the limit, then by value; the limited lengths go to them in that order
@@ -548,16 +475,10 @@ __global__ void __launch_bounds__(64) jpeg_tables_kernel(const uint32_t* __restr
     const int sym = lane + 64 * j;
     uint32_t entry = 0u;
     if (cs[j] > 0) {
-      const int mine = (cs[j] << 8) | sym;
-      int p = 0;
-      for (int i = 0; i < 256; ++i) {
-        const int other = size_by_symbol[i];
-        p += (other > 0 && ((other << 8) | i) < mine) ? 1 : 0;
-      }
+      const int p = fcp_entropy::symbol_rank(size_by_symbol, 256, cs[j], sym);
       record[16 + p] = (uint8_t)sym;                                      // p < 256: at most 255 symbols come before one
-      for (int len = 1; len <= 16; ++len)
-        if (p >= first_pos[len] && p < first_pos[len + 1])
-          entry = ((first_code[len] + (uint32_t)(p - first_pos[len])) & 0xffffu) | ((uint32_t)len << 16);
+      const int len = fcp_entropy::length_at_rank<16>(first_pos, p);
+      if (len > 0) entry = ((first_code[len] + (uint32_t)(p - first_pos[len])) & 0xffffu) | ((uint32_t)len << 16);
     }
     if (codes) codes[t * 256 + sym] = entry;
   }
@@ -612,8 +533,6 @@ __global__ void __launch_bounds__(kThreads) jpeg_stuff_kernel(const uint32_t* __
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 struct Layout {
   Geometry g;
   size_t raw_words;             // per face, a multiple of 4: the stuffing pass reads 16 bytes at a time
@@ -700,15 +619,12 @@ int encode(const uint8_t* crops, int f, int h, int w, int channels, int quality,
            int64_t out_stride, int64_t capacity, int32_t* lengths, uint8_t* tables, void* workspace, int64_t workspace_bytes,
            const char* sizer, fcp_stream_t stream) {
   FCP_REQUIRE(quality >= 1 && quality <= 100, "jpeg_encode: quality 1..100, not %d", quality);
-  FCP_REQUIRE(capacity >= 0 && out_stride >= capacity, "jpeg_encode: capacity %lld must be >= 0 and fit the stride %lld",
-              (long long)capacity, (long long)out_stride);
-  if (f == 0) return 0;
-  FCP_REQUIRE(crops && lengths && workspace && (out || capacity == 0), "jpeg_encode: null pointer");
-  FCP_REQUIRE(!optimize || tables, "jpeg_encode: optimize needs the tables buffer (null pointer)");
   const Layout l = layout_of(f, h, w, channels, subsampling, optimize);
-  FCP_REQUIRE(workspace_bytes >= (int64_t)l.total(), "jpeg_encode: workspace of %lld bytes, %s asks for %lld",
-              (long long)workspace_bytes, sizer, (long long)l.total());
-  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "jpeg_encode: the workspace must be 16-byte aligned");
+  if (int rc = fcp_entropy::check_slots("jpeg_encode", f, crops && lengths && workspace && (out || capacity == 0), out_stride,
+                                        capacity, workspace, workspace_bytes, l.total(), sizer))
+    return rc;
+  if (f == 0) return 0;
+  FCP_REQUIRE(!optimize || tables, "jpeg_encode: optimize needs the tables buffer (null pointer)");
 
   QuantArg q;
   const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;          // the IJG quality scale, baseline range

@@ -8,9 +8,9 @@
 //            "differs from the byte before" flags -> the run list (byte << 24 | start) in the workspace; then one lane
 //            per run counts its tokens into a 286-bin histogram in LDS, which joins the face's with integer atomics (adds
 //            commute: the counts do not depend on the order)
-//   tables   one wave per face: the code lengths by the merge loop of fcp_jpeg.hip's jpeg_tables_kernel over 286 entries
-//            and no pseudo-symbol, limited to 15 bits, canonical codes bit-reversed for an LSB-first stream, and the
-//            block header (fixed code-length code), written to the front of the face's bits
+//   tables   one wave per face: the code lengths by the merge of fcp_entropy.h over 286 entries, limited to 15 bits,
+//            canonical codes bit-reversed for an LSB-first stream, and the block header (fixed code-length code),
+//            written to the front of the face's bits
 //   count    per row: the bits of its tokens
 //   scan     one workgroup per face: exclusive scan of the rows' bits behind the header -> the bit offset of every row
 //   emit     per row, one lane per run: the run's bits, shifted to its offset (a scan of the runs' bit counts), into
@@ -22,22 +22,25 @@
 // A token walk (walk_run) feeds the histogram, the count and emit, as code_block does in fcp_jpeg.hip.
 #include "fcp_block_scan.h"
 #include "fcp_common.h"
+#include "fcp_entropy.h"
 #include "fcp_hip.h"
 
 namespace {
+
+using fcp_entropy::kEntries;                  // table entries per lane: 5 * 64 >= 286
+using fcp_entropy::kFib35;
+using fcp_entropy::round16;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kRowsPerBlock = 4;              // scanlines a workgroup takes in turn: one histogram flush for all of them
 constexpr int kMaxSide = 8192;
-constexpr long long kFib35 = 9227465;         // a Huffman tree over fewer counts than Fibonacci(35) is at most 32 deep
-constexpr int kSymbols = 286;                 // literals 0..255, end of block, lengths 257..285
+constexpr int kSymbols = 286;                // literals 0..255, end of block, lengths 257..285
 constexpr int kBins = 288;                    // stride of a face's counts and codes in the workspace
 constexpr int kMaxBits = 15;                  // deflate's limit of a literal/length code
 constexpr int kMaxCodeLength = 48;            // the lengths the arrays hold before the limit: counts that sum to less
                                               // than 2^32 < Fibonacci(48) - 1 make no tree deeper than 44
 constexpr int kHeaderWords = 64;              // 2048 bits: 17 + 19 * 3 + 287 lengths of at most 5 bits = 1509 at most
-constexpr int kEntries = 5;                   // table entries per lane: 5 * 64 >= 286
 constexpr unsigned kAdler = 65521u;
 
 struct RowInfo {
@@ -46,20 +49,6 @@ struct RowInfo {
   uint32_t nruns;               // maximal runs of equal bytes
   uint32_t bits;                // bits of the row's tokens (count kernel)
 };
-
-// ------------------------------------------------------------------------------------------------ workgroup helpers
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* scratch) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();                                             // scratch may still be read from the round before
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T all = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) all += scratch[k];
-  return all;
-}
 
 // ------------------------------------------------------------------------------------------------ filter
 __device__ __forceinline__ int paeth(int a, int b, int c) {
@@ -153,25 +142,9 @@ struct CountSink {
   }
 };
 
-// Bits go out least significant first.  `acc` holds the `n` (< 32) bits not yet written of the word `word` points at;
-// put() takes up to 21 bits (a 15-bit code, 5 extra bits, the distance bit).
-struct BitSink {
+// Bits go out least significant first; put() takes up to 21 bits (a 15-bit code, 5 extra bits, the distance bit).
+struct BitSink : fcp_entropy::BitWriter<false> {
   const uint32_t* tab;
-  uint32_t* word;
-  uint64_t acc = 0;
-  uint32_t n;
-  bool shared;                  // the word `word` points at may also hold bits of the run before this one
-  __device__ __forceinline__ void put(uint32_t value, uint32_t len) {
-    acc |= (uint64_t)value << n;
-    n += len;
-    if (n >= 32) {
-      if (shared) atomicOr(word, (uint32_t)acc); else *word = (uint32_t)acc;
-      shared = false;
-      ++word;
-      acc >>= 32;
-      n -= 32;
-    }
-  }
   __device__ __forceinline__ void literal(uint32_t byte, int count) {
     const uint32_t e = tab[byte & 255u];
     for (int k = 0; k < count; ++k) put(e & 0xffffu, e >> 16);
@@ -182,9 +155,6 @@ struct BitSink {
     length_symbol(m, &sym, &ebits, &evalue);
     const uint32_t e = tab[sym], len = e >> 16;
     put((e & 0xffffu) | (evalue << len), len + (uint32_t)ebits + 1u);      // the distance code is the bit 0 on top
-  }
-  __device__ __forceinline__ void finish() {                   // the tail shares its word with the run after this one
-    if (n > 0) atomicOr(word, (uint32_t)acc);
   }
 };
 
@@ -219,7 +189,7 @@ __global__ void __launch_bounds__(kThreads) png_filter_kernel(const uint8_t* __r
     uint32_t best = 0;
 #pragma unroll
     for (int t = 0; t < 5; ++t) {
-      const uint32_t total = block_sum(cost[t], scratch32);
+      const uint32_t total = fcp_block_sum<kThreads>(cost[t], scratch32);
       if (t == 0 || total < best) best = total, type = t;      // ties go to the lowest type
     }
     uint32_t* row_runs = runs + (face * h + y) * (size_t)len;
@@ -238,8 +208,8 @@ __global__ void __launch_bounds__(kThreads) png_filter_kernel(const uint8_t* __r
       if (flag) row_runs[nruns + excl] = (v << 24) | (uint32_t)i;      // nruns + excl <= i < len
       nruns += total;
     }
-    sum = block_sum(sum, scratch64);
-    wsum = block_sum(wsum, scratch64);                         // its barriers also publish the run list to the workgroup
+    sum = fcp_block_sum<kThreads>(sum, scratch64);
+    wsum = fcp_block_sum<kThreads>(wsum, scratch64);                         // its barriers also publish the run list to the workgroup
     HistSink sink;
     sink.bins = bins;
     for (uint32_t r = threadIdx.x; r < nruns; r += kThreads) {
@@ -284,11 +254,10 @@ struct HeaderWriter {
   __device__ __forceinline__ void clen(int s) { put(clen_code_reversed(s), clen_length(s)); }
 };
 
-// Code lengths of a row of 286 frequencies, one wave per row: jpeg_tables_kernel's merge (fcp_jpeg.hip: the two smallest
-// non-zero frequencies, the larger index among equals, every entry carrying the head of its set), without its
-// pseudo-symbol; libjpeg's bits[] adjustment down to 15; the limited lengths to the symbols in order of (length before
-// the limit, symbol); the canonical codes of RFC 1951 section 3.2.2 from those lengths, bit-reversed.  Fewer than two
-// non-zero frequencies make no tree: every length is 0.  count_eob: the row's entry 256 is taken as 1 (the encoder's
+// Code lengths of a row of 286 frequencies, one wave per row, out of the pieces of fcp_entropy.h: the merge (no
+// pseudo-symbol here); libjpeg's bits[] adjustment down to 15; the limited lengths to the symbols in order of (length
+// before the limit, symbol); then the canonical codes of RFC 1951 section 3.2.2 from those lengths, bit-reversed.  Fewer
+// than two non-zero frequencies make no tree: every length is 0.  count_eob: the row's entry 256 is taken as 1 (the encoder's
 // histogram does not count the end-of-block symbol).  lengths (n,286) u8 or null; codes (n,code_stride) u32 or null:
 // reversed code | length << 16, zeros from 286 on.  raw != null: the block header of face t goes to the front of its
 // raw_words words (zeroed before) and its length in bits to header_bits[t].
@@ -308,45 +277,16 @@ __global__ void __launch_bounds__(64) png_tables_kernel(const uint32_t* __restri
   const int lane = threadIdx.x;
   const size_t t = blockIdx.x;
   uint32_t fr[kEntries];
-  int head[kEntries], cs[kEntries];
+  int cs[kEntries];
 #pragma unroll
   for (int j = 0; j < kEntries; ++j) {
     const int idx = lane + 64 * j;
     fr[j] = idx < kSymbols ? freq[t * freq_stride + idx] : 0u;
     if (count_eob && idx == 256) fr[j] = 1u;
-    head[j] = idx, cs[j] = 0;
   }
   if (lane <= kMaxCodeLength) bits[lane] = 0;
   for (int i = lane; i < kHeaderWords; i += 64) header[i] = 0u;
-  constexpr unsigned long long kNone = ~0ull;
-  for (int merges = 0; merges < kSymbols; ++merges) {                     // every merge empties one of 286 entries
-    unsigned long long k1 = kNone, k2 = kNone;
-#pragma unroll
-    for (int j = 0; j < kEntries; ++j) {
-      if (fr[j] == 0u) continue;
-      const unsigned long long key = ((unsigned long long)fr[j] << 9) | (unsigned long long)(511 - (lane + 64 * j));
-      if (key < k1) k2 = k1, k1 = key; else if (key < k2) k2 = key;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const unsigned long long o1 = __shfl_xor(k1, off, 64), o2 = __shfl_xor(k2, off, 64);
-      const unsigned long long lo = k1 < o1 ? k1 : o1, hi = k1 < o1 ? o1 : k1, rest = k2 < o2 ? k2 : o2;
-      k1 = lo, k2 = hi < rest ? hi : rest;
-    }
-    if (k2 == kNone) break;                                               // one entry left: the tree is complete
-    const int c1 = 511 - (int)(k1 & 511ull), c2 = 511 - (int)(k2 & 511ull);
-    const uint32_t v2 = (uint32_t)(k2 >> 9);
-#pragma unroll
-    for (int j = 0; j < kEntries; ++j) {
-      const int idx = lane + 64 * j;
-      if (idx == c1) fr[j] += v2;
-      if (idx == c2) fr[j] = 0u;
-      if (head[j] == c1 || head[j] == c2) {
-        ++cs[j];
-        head[j] = c1;
-      }
-    }
-  }
+  fcp_entropy::huffman_code_sizes(fr, kSymbols, cs);
 #pragma unroll
   for (int j = 0; j < kEntries; ++j) cs[j] = (lane + 64 * j < kSymbols) ? min(cs[j], kMaxCodeLength) : 0;
   __syncthreads();
@@ -358,43 +298,16 @@ __global__ void __launch_bounds__(64) png_tables_kernel(const uint32_t* __restri
   }
   __syncthreads();
   if (lane == 0) {
-    // libjpeg's limit, here to 15 bits: take a pair of the longest codes away, give its prefix to one of them and split a
-    // shorter code for the other.  Signed counts and the j > 0 guard only matter when the preconditions do not hold.
-    bool sane = true;
-    for (int i = kMaxCodeLength; i > kMaxBits && sane; --i) {
-      while (bits[i] > 0) {
-        int j = i - 2;
-        while (j > 0 && bits[j] == 0) --j;
-        if (j == 0) {
-          sane = false;
-          break;
-        }
-        bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
-      }
-    }
-    uint32_t code = 0;
-    int pos = 0;
-    for (int len = 1; len <= kMaxBits; ++len) {
-      const int n = min(max(bits[len], 0), kSymbols);
-      first_pos[len] = pos, first_code[len] = code;
-      pos += n;
-      code = (code + (uint32_t)n) << 1;
-    }
-    first_pos[kMaxBits + 1] = pos;
+    fcp_entropy::limit_code_lengths<kMaxCodeLength, kMaxBits>(bits);
+    fcp_entropy::code_starts<kMaxBits>(bits, kSymbols, first_pos, first_code);
   }
   __syncthreads();
   // the limited lengths go to the symbols in order of (code size before the limit, symbol)
 #pragma unroll
   for (int j = 0; j < kEntries; ++j) {
     if (cs[j] == 0) continue;
-    const int sym = lane + 64 * j, mine = (cs[j] << 9) | sym;
-    int p = 0;
-    for (int i = 0; i < kSymbols; ++i) {
-      const int other = size_by_symbol[i];
-      p += (other > 0 && ((other << 9) | i) < mine) ? 1 : 0;
-    }
-    for (int len = 1; len <= kMaxBits; ++len)
-      if (p >= first_pos[len] && p < first_pos[len + 1]) length_by_symbol[sym] = (uint8_t)len;
+    const int sym = lane + 64 * j, p = fcp_entropy::symbol_rank(size_by_symbol, kSymbols, cs[j], sym);
+    length_by_symbol[sym] = (uint8_t)fcp_entropy::length_at_rank<kMaxBits>(first_pos, p);
   }
   __syncthreads();
   // canonical codes: among the symbols of one length, in symbol order
@@ -480,7 +393,7 @@ __global__ void __launch_bounds__(kThreads) png_count_kernel(const uint32_t* __r
       run_of(row_runs, r, nruns, len, &byte, &n);
       walk_run(byte, n, sink);
     }
-    const uint32_t total = block_sum(sink.bits, scratch32);
+    const uint32_t total = fcp_block_sum<kThreads>(sink.bits, scratch32);
     if (threadIdx.x == 0) rows[face * h + y].bits = total;
   }
 }
@@ -590,8 +503,8 @@ __global__ void __launch_bounds__(kThreads) png_finish_kernel(const uint32_t* __
     a += info.sum % kAdler;
     b += ((total - (unsigned long long)y * len) % kAdler) * (info.sum % kAdler) % kAdler + kAdler - info.wsum % kAdler;
   }
-  a = block_sum(a, scratch64);
-  b = block_sum(b, scratch64);
+  a = fcp_block_sum<kThreads>(a, scratch64);
+  b = fcp_block_sum<kThreads>(b, scratch64);
   if (threadIdx.x == 0) {
     const uint32_t adler = (uint32_t)(((total + b) % kAdler) << 16) | (uint32_t)((1ull + a) % kAdler);
     const long long end = 2 + (long long)nbytes;
@@ -605,8 +518,6 @@ __global__ void __launch_bounds__(kThreads) png_finish_kernel(const uint32_t* __
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 struct Layout {
   int len;                      // bytes of a filtered row
   size_t raw_words;             // per face, a multiple of 4: the finish pass reads 16 bytes at a time
@@ -654,14 +565,11 @@ extern "C" int fcp_png_encode_u8(const uint8_t* pixels, int f, int h, int w, int
                                  int64_t capacity, int32_t* lengths, void* workspace, int64_t workspace_bytes,
                                  fcp_stream_t stream) {
   if (check_sizes(f, h, w, channels) != 0) return FCP_ERR_ARG;
-  FCP_REQUIRE(capacity >= 0 && out_stride >= capacity, "png_encode: capacity %lld must be >= 0 and fit the stride %lld",
-              (long long)capacity, (long long)out_stride);
-  if (f == 0) return 0;
-  FCP_REQUIRE(pixels && lengths && workspace && (out || capacity == 0), "png_encode: null pointer");
   const Layout l = layout_of(f, h, w, channels);
-  FCP_REQUIRE(workspace_bytes >= (int64_t)l.total(), "png_encode: workspace of %lld bytes, fcp_png_workspace_bytes asks for %lld",
-              (long long)workspace_bytes, (long long)l.total());
-  FCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "png_encode: the workspace must be 16-byte aligned");
+  if (int rc = fcp_entropy::check_slots("png_encode", f, pixels && lengths && workspace && (out || capacity == 0), out_stride,
+                                        capacity, workspace, workspace_bytes, l.total(), "fcp_png_workspace_bytes"))
+    return rc;
+  if (f == 0) return 0;
 
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   uint32_t* runs = reinterpret_cast<uint32_t*>(ws);

@@ -12,7 +12,7 @@ import torch
 
 from . import _native as N
 from . import torch_ops as T
-from ._io_codec import _ENCODER_KW, JPEG_SUBSAMPLINGS, JpegSettings, jpeg_kw, save_jpeg
+from ._io_codec import _ENCODER_KW, JPEG_SUBSAMPLINGS, JpegSettings, jpeg_kw, read_slots, save_jpeg
 
 JPEG_EXTENSIONS = tuple(ext for ext, kw in _ENCODER_KW.items() if kw.get("format") == "JPEG")     # .jpg / .jpeg / .jpe
 _KW = _ENCODER_KW[".jpg"]
@@ -120,40 +120,23 @@ def encode_scans(crops_dev: torch.Tensor, out: torch.Tensor, quality: int = QUAL
     ``tables`` (F,4,272) u8 device, contiguous: code every face with Huffman tables made for it (libjpeg's
     ``optimize_coding``); the four records of face i are written to tables[i] (a histogram and a table launch more).
     With 4:2:0 and no ``tables`` this is the call it always was; anything else takes ``fcp_jpeg_encode_ex_u8``."""
-    assert crops_dev.dtype == torch.uint8 and crops_dev.is_contiguous() and crops_dev.dim() in (3, 4)
-    assert out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == crops_dev.shape[0]
     ss = subsampling_index(subsampling)
-    f, h, w = crops_dev.shape[:3]
     if tables is not None:
-        assert tables.dtype == torch.uint8 and tables.is_contiguous() and tuple(tables.shape) == (f, 4, TABLE_BYTES)
-        assert tables.device == crops_dev.device
-    ex = ss != SUBSAMPLING or tables is not None
-    if T.ENABLED:
-        if ex:
-            return T.load().jpeg_encode_ex(crops_dev, int(quality), ss, out, tables)
-        return T.load().jpeg_encode(crops_dev, int(quality), SUBSAMPLING, out)
-    c = crops_dev.shape[3] if crops_dev.dim() == 4 else 1
-    capacity = out.shape[1]
-    if capacity and out.stride(1) != 1:
-        raise RuntimeError("jpeg_encode: the bytes of a row of out must be contiguous")
-    lengths = torch.empty((f,), dtype=torch.int32, device=crops_dev.device)
-    if ex:
-        opt = 0 if tables is None else 1
-        need = N.lib().fcp_jpeg_workspace_bytes_ex(f, h, w, c, ss, opt)
-        N.check(-1 if need < 0 else 0, "fcp_jpeg_encode_ex_u8")
-        work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
-        N.check(N.lib().fcp_jpeg_encode_ex_u8(N.ptr(crops_dev), f, h, w, c, int(quality), ss, opt,
-                                              N.ptr(out) if capacity else None, out.stride(0) if f > 1 else capacity, capacity,
-                                              N.ptr(lengths), N.ptr(tables), N.ptr(work), need, N.stream_ptr()),
-                "fcp_jpeg_encode_ex_u8")
-        return lengths
-    need = N.lib().fcp_jpeg_workspace_bytes(f, h, w, c)
-    N.check(-1 if need < 0 else 0, "fcp_jpeg_encode_u8")
-    work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
-    N.check(N.lib().fcp_jpeg_encode_u8(N.ptr(crops_dev), f, h, w, c, int(quality), SUBSAMPLING, N.ptr(out) if capacity else None,
-                                       out.stride(0) if f > 1 else capacity, capacity, N.ptr(lengths), N.ptr(work), need,
-                                       N.stream_ptr()), "fcp_jpeg_encode_u8")
-    return lengths
+        assert tables.dtype == torch.uint8 and tables.is_contiguous() and tables.device == crops_dev.device
+        assert tuple(tables.shape) == (crops_dev.shape[0], 4, TABLE_BYTES)
+    q, opt = int(quality), 0 if tables is None else 1
+    if ss != SUBSAMPLING or opt:
+        return N.encode_slots(
+            "jpeg_encode", "fcp_jpeg_encode_ex_u8", crops_dev, out,
+            (lambda: T.load().jpeg_encode_ex(crops_dev, q, ss, out, tables)) if T.ENABLED else None,
+            lambda *size: N.lib().fcp_jpeg_workspace_bytes_ex(*size, ss, opt),
+            lambda size, slots, work: N.lib().fcp_jpeg_encode_ex_u8(N.ptr(crops_dev), *size, q, ss, opt, *slots, N.ptr(tables),
+                                                                    *work))
+    return N.encode_slots(
+        "jpeg_encode", "fcp_jpeg_encode_u8", crops_dev, out,
+        (lambda: T.load().jpeg_encode(crops_dev, q, SUBSAMPLING, out)) if T.ENABLED else None,
+        lambda *size: N.lib().fcp_jpeg_workspace_bytes(*size),
+        lambda size, slots, work: N.lib().fcp_jpeg_encode_u8(N.ptr(crops_dev), *size, q, SUBSAMPLING, *slots, *work))
 
 
 def huffman_tables(freq: torch.Tensor, with_codes: bool = False):
@@ -193,21 +176,12 @@ def encode_jpeg(crops_dev: torch.Tensor, quality: int = QUALITY, capacity: int |
     capacity = h * w * c if capacity is None else int(capacity)
     out = torch.empty((f, capacity), dtype=torch.uint8, device=crops_dev.device)
     tables = torch.empty((f, 4, TABLE_BYTES), dtype=torch.uint8, device=crops_dev.device) if optimize else None
-    if ss == SUBSAMPLING and not optimize:
-        lengths = encode_scans(crops_dev, out, quality).cpu().numpy()
-    else:
-        lengths = encode_scans(crops_dev, out, quality, subsampling=ss, tables=tables).cpu().numpy()
-    fits = lengths <= capacity
-    used = int(lengths[fits].max()) if fits.any() else 0
-    scans = out[:, :used].cpu().numpy() if used else None
+    lengths = encode_scans(crops_dev, out, quality, subsampling=ss, tables=tables)
     records = tables.cpu().numpy() if optimize else None
     head = None if optimize else jpeg_header(h, w, c, quality, subsampling=ss)
-    files = []
-    for i in range(f):
-        if fits[i]:
-            face_head = jpeg_header(h, w, c, quality, subsampling=ss, tables=records[i]) if optimize else head
-            files.append(face_head + scans[i, :lengths[i]].tobytes())
-        else:
-            px = crops_dev[i].cpu().numpy()
-            files.append(_host_jpeg(px[..., 0] if px.ndim == 3 and c == 1 else px, quality, ss, optimize))
-    return files
+
+    def on_host(i):
+        px = crops_dev[i].cpu().numpy()
+        return _host_jpeg(px[..., 0] if px.ndim == 3 and c == 1 else px, quality, ss, optimize)
+    return read_slots(out, lengths, lambda i, scan: (jpeg_header(h, w, c, quality, subsampling=ss, tables=records[i])
+                                                    if optimize else head) + scan, on_host)

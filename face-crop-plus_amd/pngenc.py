@@ -14,7 +14,7 @@ import torch
 
 from . import _native as N
 from . import torch_ops as T
-from ._io_codec import _ENCODER_KW
+from ._io_codec import _ENCODER_KW, read_slots
 
 PNG_EXTENSIONS = tuple(ext for ext, kw in _ENCODER_KW.items() if kw.get("format") == "PNG")     # .png
 SYMBOLS = 286                    # literal/length symbols of deflate
@@ -61,23 +61,10 @@ def encode_streams(pixels_dev: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """pixels (F,H,W,3), (F,H,W,4) or (F,H,W) u8 device, out (F, capacity) u8 device (rows may be a view of a wider buffer) ->
     lengths (F,) int32 device.  Row i receives face i's zlib stream, at most ``capacity`` bytes of it; the length is the
     true one even then.  One memset and six launches."""
-    assert pixels_dev.dtype == torch.uint8 and pixels_dev.is_contiguous() and pixels_dev.dim() in (3, 4)
-    assert out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == pixels_dev.shape[0]
-    if T.ENABLED:
-        return T.load().png_encode(pixels_dev, out)
-    f, h, w = pixels_dev.shape[:3]
-    c = pixels_dev.shape[3] if pixels_dev.dim() == 4 else 1
-    capacity = out.shape[1]
-    if capacity and out.stride(1) != 1:
-        raise RuntimeError("png_encode: the bytes of a row of out must be contiguous")
-    lengths = torch.empty((f,), dtype=torch.int32, device=pixels_dev.device)
-    need = N.lib().fcp_png_workspace_bytes(f, h, w, c)
-    N.check(-1 if need < 0 else 0, "fcp_png_encode_u8")
-    work = torch.empty((need,), dtype=torch.uint8, device=pixels_dev.device)
-    N.check(N.lib().fcp_png_encode_u8(N.ptr(pixels_dev), f, h, w, c, N.ptr(out) if capacity else None,
-                                      out.stride(0) if f > 1 else capacity, capacity, N.ptr(lengths), N.ptr(work), need,
-                                      N.stream_ptr()), "fcp_png_encode_u8")
-    return lengths
+    return N.encode_slots("png_encode", "fcp_png_encode_u8", pixels_dev, out,
+                          (lambda: T.load().png_encode(pixels_dev, out)) if T.ENABLED else None,
+                          lambda *size: N.lib().fcp_png_workspace_bytes(*size),
+                          lambda size, slots, work: N.lib().fcp_png_encode_u8(N.ptr(pixels_dev), *size, *slots, *work))
 
 
 def huffman_lengths(freq: torch.Tensor, with_codes: bool = False):
@@ -122,9 +109,5 @@ def encode_png(pixels_dev: torch.Tensor, capacity: int | None = None) -> list:
         return [on_host(i) for i in range(f)]
     capacity = h * (w * c + 1) + 1024 if capacity is None else int(capacity)
     out = torch.empty((f, capacity), dtype=torch.uint8, device=pixels_dev.device)
-    lengths = encode_streams(pixels_dev, out).cpu().numpy()
-    fits = lengths <= capacity
-    used = int(lengths[fits].max()) if fits.any() else 0
-    streams = out[:, :used].cpu().numpy() if used else None
-    wrap = (lambda data: png_file_rgba(h, w, data)) if c == 4 else (lambda data: png_file(h, w, c, data))
-    return [wrap(streams[i, :lengths[i]].tobytes()) if fits[i] else on_host(i) for i in range(f)]
+    wrap = (lambda i, data: png_file_rgba(h, w, data)) if c == 4 else (lambda i, data: png_file(h, w, c, data))
+    return read_slots(out, encode_streams(pixels_dev, out), wrap, on_host)

@@ -337,10 +337,19 @@ def cases():
 
 def huffman_rows():
     """Rows of 286 counts for the Huffman tests, on the CPU and on the GPU: Fibonacci counts over 40 symbols (a tree 39
-    deep, far past the limit) and over 33, degenerate rows, equal counts, a skewed row."""
+    deep, far past the limit) and over 33, degenerate rows, equal counts, a skewed row.  Then the rows that aim at the
+    table builder the kernels share with the JPEG encoder: Fibonacci counts over 45 symbols, the deepest tree (44) a row
+    that sums to less than 2^32 can make (over 46 symbols they sum to 4 807 526 975), so the lengths before the limit come
+    as close to the arrays' bound of 48 as the precondition lets them; a row whose non-zero counts all sit in lane 5 of
+    the wave (index % 64), so that both halves of every merge come from one lane's registers; a row whose two smallest
+    counts are equal and sit in lanes 0 and 63, the two ends of the butterfly."""
     fib = [1, 1]
-    while len(fib) < 40:
+    while len(fib) < 45:
         fib.append(fib[-1] + fib[-2])
+    one_lane, tie = [0] * 286, [0] * 286
+    for i, n in ((5, 3), (69, 1), (133, 4), (197, 1), (261, 5)):
+        one_lane[i] = n
+    tie[0], tie[63], tie[130] = 1, 1, 7
     two = [0] * 286
     two[7], two[256] = 5, 1
     single = [0] * 286
@@ -348,5 +357,6 @@ def huffman_rows():
     lone = [0] * 286
     lone[256] = 1
     skew = [(i * 7919) % 97 + (1000 if i < 3 else 0) for i in range(286)]
-    return {"fib40": fib + [0] * 246, "fib33": fib[:33] + [0] * 253, "two": two, "single_literal": single, "lone": lone,
-            "zeros": [0] * 286, "equal": [1] * 286, "skew": skew}
+    return {"fib40": fib[:40] + [0] * 246, "fib33": fib[:33] + [0] * 253, "two": two, "single_literal": single, "lone": lone,
+            "zeros": [0] * 286, "equal": [1] * 286, "skew": skew, "fib45": fib + [0] * 241, "one_lane": one_lane,
+            "butterfly_tie": tie}

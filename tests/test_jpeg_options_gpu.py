@@ -176,9 +176,15 @@ def test_huffman_tables_of_given_rows(device, boundary):
     one[7], two[[3, 200]] = 5, 9
     rng = np.random.default_rng(5)
     sparse = np.where(rng.random(256) < 0.4, rng.integers(1, 30000, 256), 0)
+    # the rows that aim at the table builder shared with the PNG encoder: every non-zero count in lane 5 of the wave (index
+    # % 64), so that both halves of a merge come from one lane's registers; the two smallest counts equal and in lanes 0 and
+    # 63, the two ends of the butterfly (the pseudo-symbol, entry 256 with count 1, ties with them from lane 0).
+    # fibonacci_row(30) is the row that reaches depth 30 under the arrays' bound of 32
+    one_lane, tie = np.zeros(256, np.int64), np.zeros(256, np.int64)
+    one_lane[[5, 69, 133, 197]], tie[[0, 63, 130]] = (3, 1, 4, 1), (1, 1, 7)
     rows = [O.fibonacci_row(19), O.fibonacci_row(25), O.fibonacci_row(30), O.fibonacci_row(19, 1), O.fibonacci_row(25, 1),
             O.fibonacci_row(30, 1), np.ones(256, np.int64), one, two, np.zeros(256, np.int64), sparse,
-            np.full(256, 36000, np.int64)]
+            np.full(256, 36000, np.int64), one_lane, tie]
     depths = []
     for r in rows:
         info = {}

@@ -135,6 +135,15 @@ def test_huffman_lengths():
     single = R.huffman_lengths(rows["single_literal"], 15)
     assert single[65] == 1 and single[256] == 1 and sum(single) == 2
     assert not any(R.huffman_lengths(rows["lone"], 15)) and not any(R.huffman_lengths(rows["zeros"], 15))
+    # the kernel's preconditions, and what the rows that aim at the shared table builder are for
+    assert all(sum(r) < 2 ** 32 and max(r) < 2 ** 31 for r in rows.values())
+    assert max(R.huffman_lengths(rows["fib45"], 64)) == 44 and max(R.huffman_lengths(rows["fib45"], 15)) == 15
+    assert sum(rows["fib45"]) + rows["fib45"][44] + rows["fib45"][43] >= 2 ** 32       # a 46th Fibonacci count breaks the first
+    assert {i % 64 for i, n in enumerate(rows["one_lane"]) if n} == {5} and sum(1 for n in rows["one_lane"] if n) == 5
+    assert [(i, n) for i, n in enumerate(R.huffman_lengths(rows["one_lane"], 15)) if n] == [(5, 2), (69, 3), (133, 2), (197, 3), (261, 2)]
+    tie = rows["butterfly_tie"]
+    assert tie[0] == tie[63] == min(n for n in tie if n) and sum(1 for n in tie if n) == 3
+    assert [(i, n) for i, n in enumerate(R.huffman_lengths(tie, 15)) if n] == [(0, 2), (63, 2), (130, 1)]
     # among equal frequencies the larger index merges first: 4 equal counts make a balanced tree, 3 leave the lowest short
     assert R.huffman_lengths([1, 1, 1, 1], 15) == [2, 2, 2, 2] and R.huffman_lengths([1, 1, 1], 15) == [1, 2, 2]
     codes = R.canonical_codes([3, 3, 3, 3, 3, 2, 4, 4])          # the example of RFC 1951 section 3.2.2

@@ -113,7 +113,8 @@ def test_huffman_lengths_kernel(device):
     names = sorted(rows)
     freq = torch.tensor([rows[n] for n in names], dtype=torch.int64).to(torch.int32).to(device)
     want = [R.huffman_lengths(rows[n], 15) for n in names]
-    assert max(want[names.index("fib40")]) == 15
+    assert max(want[names.index("fib40")]) == 15 and all(sum(rows[n]) < 2 ** 32 for n in names)
+    assert max(R.huffman_lengths(rows["fib45"], 64)) == 44            # the deepest tree a row below 2^32 makes: bound 48
     old = T.ENABLED
     try:
         for enabled in (True, False):
