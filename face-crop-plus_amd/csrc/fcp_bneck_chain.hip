@@ -94,8 +94,6 @@ constexpr int wgs_per_cu(int cw, int cn, bool has_c2, bool direct = false) {
   return lds_bytes(cw, cn, has_c2) <= 80 * 1024 ? 2 : 1;
 }
 
-__device__ __forceinline__ int swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
-
 // PATCH (the conv2 forms): the tile is an 8 x 16 PATCH of one image instead of 128 consecutive pixels, and phase 1 stages the
 // patch's (8 + 2) x (16 + 2) halo ONCE per 32-channel slice; the nine taps read it at shifted rows (the scheme of
 // conv3x3_halo_f16x3).  A tile of consecutive pixels fetches a 128-byte operand row per pixel, tap and slice: 288 of the ~720

@@ -219,6 +219,9 @@ __device__ __forceinline__ void dma_slice(const ConvK& p, __amdgpu_buffer_rsrc_t
                                              (int)(woff[i] + (unsigned)(kt * BK * 4)), 0, 0, FCP_AUX_B);
 }
 
+// Chunk swizzle of a 128-byte fp16x3 LDS row: 16-byte chunk c of row `row` lives at chunk position c ^ swz(row).
+__device__ __forceinline__ int swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
+
 // Fragment offsets inside a swizzled 128-byte fp16x3 LDS row [hi k0..31 | lo k0..31] (chunk swizzle ((row >> 1) & 7) ^
 // ((row & 1) << 2), row = lane & 31): the hi / lo chunk of k-half s that lane `lane` feeds to v_mfma_f32_32x32x16_f16.
 __device__ __forceinline__ void frag_offsets(int lane, int (&offH)[2], int (&offL)[2]) {

@@ -7,6 +7,14 @@
 // operand-feed limit.  Here a workgroup owns an 8 x 32 patch of output pixels and stages, per 32-channel
 // slice, the (8+2) x (32+2) halo patch ONCE; the nine taps read it at shifted row indices.
 //
+// Layout of the file: the pieces both kernels share (HaloTiles: the persistent tile stream; halo_frag_addrs: the compute
+// waves' fragment addresses; halo_epi_consts: a pass's constants in the tile epilogue), then conv3x3_halo_f16x3 (one pass per
+// 32 filters) and conv3x3_halo_wide_f16x3 (column tiles inner, filters through a tap ring), which differ in how filters reach
+// LDS and in how a compute wave orders fragment reads against MFMAs, then the two launchers over halo_grid.  Two stretches are
+// text in both kernels, word for word, because the shared form cost registers or time (profiles/halo_shared.md): the loader
+// waves' halo addressing and staging (lrow .. dma_halo; a HaloLoader struct made the 128-filter kernel ~1 % slower) and the
+// `epilogue` lambda.  A fix to either is made twice.
+//
 //  * 8 waves, one workgroup per CU: four COMPUTE waves (wave w: image rows 2w, 2w+1 of the patch = two 32x32 MFMA
 //    tiles x 32 filters per pass; cout = 64 runs two passes per slice over the same halo patch) and four LOADER
 //    waves that issue every LDS-DMA.  An LDS-DMA instruction occupies its wave until the vector-memory path has
@@ -48,8 +56,8 @@ constexpr int B_BYTES = 9 * 32 * ROWB;    // 36864: one filter buffer (9 taps x 
 constexpr int B_OFF = 2 * A_BYTES;        // filter buffers follow the two halo stages
 constexpr int LDS_TOTAL = 2 * A_BYTES + 2 * B_BYTES;   // 161792
 constexpr int A_LD = 11;                  // halo DMA instructions per thread: 2752 16-byte pieces / 256 (last: waves 0..2)
+constexpr int HALO_I = A_LD - 1;          // halo instructions every loader wave issues (waves 0..2: one more)
 
-__device__ __forceinline__ int swz(int row) { return ((row >> 1) & 7) ^ ((row & 1) << 2); }
 // epilogue LDS accesses, also inline asm: the next tile's first DMA is in flight while the fp32 tile is staged
 __device__ __forceinline__ void lds_write32(unsigned addr, float v) { asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
 __device__ __forceinline__ f32x4 lds_read128f(unsigned addr) {
@@ -58,19 +66,65 @@ __device__ __forceinline__ f32x4 lds_read128f(unsigned addr) {
   return v;
 }
 
+// ---- the pieces both kernels share
+
+// The persistent tile stream of workgroup bid of nb (grid = min(tiles, CUs): halo_grid).  XCD x (= bid & 7) walks a contiguous
+// range of per_x tiles, so neighbouring patches (which share halo rows) meet in one L2; the workgroups of an XCD (slot = 0 ..
+// slots - 1) take its tiles in turn: stream position it = slot, slot + slots, ... is tile xcd * per_x + it.  A workgroup's
+// tiles form ONE stream of blocks: both roles walk it and meet at the same barriers.
+struct HaloTiles {
+  int tiles_x, tiles_y, ntiles, per_x, xcd, slot, slots;
+  struct Next { int nit, ntile; bool more; };           // the stream position after `it`, its tile, and whether it exists
+  __device__ __forceinline__ HaloTiles(const ConvK& p, int nb, int bid)
+      : tiles_x((p.out_w + TW - 1) / TW), tiles_y((p.out_h + TH - 1) / TH), ntiles(p.n * tiles_x * tiles_y), per_x((ntiles + 7) / 8),
+        xcd(bid & 7), slot(bid >> 3), slots((nb + 7 - xcd) / 8) {}
+  __device__ __forceinline__ int tile(int it) const { return xcd * per_x + it; }
+  __device__ __forceinline__ bool has(int it) const { return it < per_x && tile(it) < ntiles; }   // has(slot): there is a first tile
+  __device__ __forceinline__ Next next(int it) const { return {it + slots, tile(it + slots), has(it + slots)}; }
+  __device__ __forceinline__ void coords(int tile, int& ni, int& y0, int& x0) const {   // image, first row and column of the patch
+    const int tx = tile % tiles_x;
+    const int ty = (tile / tiles_x) % tiles_y;
+    ni = tile / (tiles_x * tiles_y);
+    y0 = ty * TH; x0 = tx * TW;
+  }
+};
+
+// Fragment addresses of a compute wave's lane (tile independent).  Halo rows read by the lane: hr = (2 w + d) * 34 + xl + kw,
+// d = i + kh in 0..3, kw in 0..2.  aaddr[d][kw] is the LDS address (stage 0) of chunk (half ^ swz(hr)); the chunks (2 + half),
+// (4 + half), (6 + half) ^ swz(hr) are that address ^ 0x20 / 0x40 / 0x60 (rows are 128-byte aligned, the chunk index lives in
+// bits 4-6).
+__device__ __forceinline__ void halo_frag_addrs(unsigned (&aaddr)[4][3], unsigned lds0, int wave_u, int xl, int half) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      const int hr = (2 * wave_u + d) * HW_ + xl + kw;
+      aaddr[d][kw] = lds0 + (unsigned)(hr * ROWB + ((half ^ swz(hr)) << 4));
+    }
+}
+
+// The tile epilogue.  A finished tile leaves through a [256 pixels][32 channels] fp32 tile in a halo stage that has just died,
+// one 32-filter pass / column tile at a time; a wave stages, reads back and stores only ITS OWN 64 pixels (LDS accesses of one
+// wave execute in order), so the passes need no barrier between the waves.  Output through a buffer resource: an out-of-range
+// pixel gets offset 0xFFFFFFFF (the hardware drops the store, no divergent branch around it).  Shared: a pass's constants.
+//
+// this thread's 8 channels ccol .. ccol + 7 of a pass: bias and filter scale (cout % 8 == 0 (launcher): whole groups of 8)
+__device__ __forceinline__ void halo_epi_consts(const ConvK& p, int ccol, bool cvalid, f32x4 (&b8)[2], f32x4 (&w8)[2]) {
+  b8[0] = b8[1] = w8[0] = w8[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (cvalid) {
+    if (p.bias != nullptr) { b8[0] = *reinterpret_cast<const f32x4*>(p.bias + ccol); b8[1] = *reinterpret_cast<const f32x4*>(p.bias + ccol + 4); }
+    w8[0] = *reinterpret_cast<const f32x4*>(p.wscale + ccol); w8[1] = *reinterpret_cast<const f32x4*>(p.wscale + ccol + 4);
+  }
+}
+
+// ---- narrow kernel: one pass per 32 filters over the staged halo patch
 template <int TN>   // 32-filter passes per slice: cout <= 32 * TN
 __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* lds = reinterpret_cast<char*>(smem);
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds;
 
-  const int tiles_x = (p.out_w + TW - 1) / TW, tiles_y = (p.out_h + TH - 1) / TH;
-  const int ntiles = p.n * tiles_x * tiles_y;
-  // persistent workgroups; XCD x (= blockIdx & 7) walks a contiguous range of tiles, so neighbouring patches
-  // (which share halo rows) meet in one L2
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int per_x = (ntiles + 7) / 8;
-  const int xcd = bid & 7, slot = bid >> 3, slots = (nb + 7 - xcd) / 8;   // workgroups of this XCD: slot = 0..slots-1
+  const HaloTiles ts(p, gridDim.x, blockIdx.x);
 
   const int lane = threadIdx.x & 63;
   const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -80,11 +134,10 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
   const int nslices = p.ctiles;
   const int nblocks = nslices * TN;
 
-  // ---- the workgroup's tiles form ONE stream of blocks: a block's filter buffer is refilled two blocks ahead and a
-  //      slice's halo stage two slices ahead ACROSS tile boundaries, so a new tile starts with its operands in LDS.
-  //      Both roles walk the same stream and meet at the same barriers.
-  int it = slot;
-  if (it >= per_x || xcd * per_x + it >= ntiles) return;
+  // ---- the stream of blocks: a block's filter buffer is refilled two blocks ahead and a slice's halo stage two slices
+  //      ahead ACROSS tile boundaries, so a new tile starts with its operands in LDS.
+  int it = ts.slot;
+  if (!ts.has(it)) return;
 
   if (loader) {
     // =================================================================== loader waves
@@ -103,10 +156,8 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
       hyx[i] = hr < (TH + 2) * HW_ ? (hy << 8 | hx) : -1;
     }
     auto tile_setup = [&](int tile) {
-      const int tx = tile % tiles_x;
-      const int ty = (tile / tiles_x) % tiles_y;
-      const int ni = tile / (tiles_x * tiles_y);
-      const int y0 = ty * TH, x0 = tx * TW;
+      int ni, y0, x0;
+      ts.coords(tile, ni, y0, x0);
       // halo row (hy, hx) -> input pixel (y0 - pad_h + hy, x0 - 1 + hx); pad_h = 1, or 0 when the input view holds a
       // real row above the output view (fcp_conv_desc.band_top)
 #pragma unroll
@@ -135,7 +186,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
     };
     auto dma_filter = [&](int blk, int buf) {            // block = slice * TN + pass; 9 instructions
       const int cs = blk / TN, pass = blk - cs * TN;
-      char* b = lds + B_OFF + buf * B_BYTES + wave_u * 8 * ROWB;
+      char* b = (lds + wave_u * 8 * ROWB) + B_OFF + buf * B_BYTES;
       const unsigned wo = wbase + (unsigned)(pass * 32 * p.wrow * 4 + cs * 9 * 128);
 #pragma unroll
       for (int t = 0; t < 9; ++t)
@@ -143,10 +194,10 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
                                                  (int)(wo + (unsigned)(t * 128)), 0, 0, 0);
     };
 
-    tile_setup(xcd * per_x + it);
+    tile_setup(ts.tile(it));
     dma_halo(0, 0);
     dma_filter(0, 0);
-    dma_halo(1, 1);                                       // nslices >= 2 (launcher)
+    dma_halo(1, 1);                                    // nslices >= 2 (launcher)
     dma_filter(1, 1);
     int blk = 0;
     unsigned bbuf = 0, astage = 0;                        // filter buffer of the current block, halo stage of the current slice
@@ -156,21 +207,20 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
       const bool new_slice = TN == 1 || (blk & 1) != 0;              // the next block starts the next channel slice
       const int cs = blk / TN;
       const bool last_of_tile = blk == nblocks - 1;
-      const int nit = it + slots, ntile = xcd * per_x + nit;
-      const bool more = nit < per_x && ntile < ntiles;
+      const HaloTiles::Next nx = ts.next(it);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // the NEXT block's operands have landed
       __builtin_amdgcn_s_barrier();                                  // X: ... and this block's buffers are dead
       // refill what just died with the operands of the block two ahead in the stream
       bool halo_delayed = false;
       const int b2 = blk + 2;
       if (b2 < nblocks) dma_filter(b2, (int)bbuf);
-      else if (more) dma_filter(b2 - nblocks, (int)bbuf);
+      else if (nx.more) dma_filter(b2 - nblocks, (int)bbuf);
       if (new_slice) {
         const int s2 = cs + 2;
         if (s2 < nslices) dma_halo(s2, (int)astage);
-        else if (more) {
+        else if (nx.more) {
           if (s2 == nslices) {                                       // next tile's first slice: its addresses replace this tile's
-            tile_setup(ntile);
+            tile_setup(nx.ntile);
             dma_halo(0, (int)astage);
           } else {
             halo_delayed = true;                                     // next tile's second slice: the freed stage hosts the epilogue first
@@ -183,9 +233,9 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
       ++blk;
       if (new_slice && last_of_tile) {
         __builtin_amdgcn_s_barrier();                                  // the compute waves have read the finished tile back from `freed`
-        if (!more) return;
+        if (!nx.more) return;
         if (halo_delayed) dma_halo(1, (int)freed);
-        it = nit;
+        it = nx.nit;
         blk = 0;
       }
     }
@@ -193,18 +243,8 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
 
   // ===================================================================== compute waves
   const int xl = lane & 31, half = lane >> 5;
-  // ---- fragment addressing (per lane, tile independent)
-  // halo rows read by this lane: hr = (2 w + d) * 34 + xl + kw, d = i + kh in 0..3, kw in 0..2.  aaddr[d][kw] is
-  // the LDS address (stage 0) of chunk (half ^ swz(hr)); the chunks (2 + half), (4 + half), (6 + half) ^ swz(hr)
-  // are that address ^ 0x20 / 0x40 / 0x60 (rows are 128-byte aligned, the chunk index lives in bits 4-6).
   unsigned aaddr[4][3];
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-      const int hr = (2 * wave_u + d) * HW_ + xl + kw;
-      aaddr[d][kw] = lds0 + (unsigned)(hr * ROWB + ((half ^ swz(hr)) << 4));
-    }
+  halo_frag_addrs(aaddr, lds0, wave_u, xl, half);
   // filter fragments: row xl of tap t at B_OFF + buf * B_BYTES + t * 4096 + xl * 128, chunk c ^ swz(xl)
   const unsigned baddr0 = lds0 + (unsigned)(B_OFF + xl * ROWB + ((half ^ swz(xl)) << 4));
 
@@ -227,29 +267,13 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
     }
   };
 
-  // output through a buffer resource (out-of-range pixels get offset 0xFFFFFFFF: the hardware drops the store, no
-  // divergent branch around it)
   __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.in2_bytes, 0x00020000);   // in2_bytes: size of `out` (halo launches)
 
   int e_ni = 0, e_y0 = 0, e_x0 = 0;                     // coordinates of the tile being computed
-  auto tile_coords = [&](int tile) {
-    const int tx = tile % tiles_x;
-    const int ty = (tile / tiles_x) % tiles_y;
-    e_ni = tile / (tiles_x * tiles_y);
-    e_y0 = ty * TH; e_x0 = tx * TW;
-  };
-  tile_coords(xcd * per_x + it);
+  ts.coords(ts.tile(it), e_ni, e_y0, e_x0);
 
   f32x16 acc[TN][2];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int n = 0; n < TN; ++n)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[n][i][e] = 0.f;
-  };
-  zero_acc();
+  clear_acc(acc);
 
   __builtin_amdgcn_s_barrier();                         // P: blocks 0 and 1 are in LDS
   __builtin_amdgcn_sched_barrier(0);
@@ -286,11 +310,10 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
     });
   };
 
-  // epilogue of the finished tile through a [256 pixels][32 channels] fp32 tile in halo stage `stage` (just freed)
+  // epilogue of the finished tile through halo stage `stage` (just freed), two pixel rows per LDS round trip; the single barrier
+  // at the end tells the loaders that the stage may be refilled.  (The wide kernel's lambda is this loop with stage 1, one or
+  // two rows and a fence per column tile; kept as text in both: see halo_epi_consts.)
   auto epilogue = [&](int stage) {
-    // A wave stages, reads back and stores only ITS OWN 64 pixels (LDS accesses of one wave execute in order), so the
-    // passes need no barrier between the waves; the single barrier at the end tells the loaders that the stage may
-    // be refilled.
     const unsigned cs0 = lds0 + (unsigned)(stage * A_BYTES + wave_u * 64 * 128);
     const int eq = lane & 3, er = lane >> 2;                       // 8-channel group, row (+ 16 g) within the wave's 64
 #pragma unroll
@@ -298,11 +321,8 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
       // this thread's 8 channels of the pass: constants requested first, consumed after the staging
       const int ccol = n * 32 + eq * 8;
       const bool cvalid = ccol < p.cout;
-      f32x4 b8[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, w8[2] = {b8[0], b8[0]};
-      if (cvalid) {                                                  // cout % 8 == 0 (launcher): whole groups of 8
-        if (p.bias != nullptr) { b8[0] = *reinterpret_cast<const f32x4*>(p.bias + ccol); b8[1] = *reinterpret_cast<const f32x4*>(p.bias + ccol + 4); }
-        w8[0] = *reinterpret_cast<const f32x4*>(p.wscale + ccol); w8[1] = *reinterpret_cast<const f32x4*>(p.wscale + ccol + 4);
-      }
+      f32x4 b8[2], w8[2];
+      halo_epi_consts(p, ccol, cvalid, b8, w8);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -363,8 +383,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
     constexpr bool new_slice = pass == TN - 1;                       // the next block starts the next channel slice
     const unsigned aoff = astage * (unsigned)A_BYTES, boff = bbuf * (unsigned)B_BYTES;
     const bool last_of_tile = blk == nblocks - 1;
-    const int nit = it + slots, ntile = xcd * per_x + nit;
-    const bool more = nit < per_x && ntile < ntiles;
+    const HaloTiles::Next nx = ts.next(it);
     fcp_static_for<0, 8>([&](auto tc) { tap_step(tc, pass_c, aoff, boff); });
     // tap 8's fragments are (about to be) in registers: the block's buffer (and, after the last pass, the slice's
     // stage) is dead for this wave; the loaders arrive when the next block's operands are in LDS
@@ -384,11 +403,11 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
       if (last_of_tile) {
         __builtin_amdgcn_sched_barrier(0);
         epilogue((int)freed);
-        if (!more) return true;
-        it = nit;
+        if (!nx.more) return true;
+        it = nx.nit;
         blk = 0;
-        tile_coords(ntile);
-        zero_acc();
+        ts.coords(nx.ntile, e_ni, e_y0, e_x0);
+        clear_acc(acc);
       }
     }
     return false;
@@ -406,6 +425,8 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_f16x3(const ConvK p) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // "Wide" halo-tile kernel: 3x3 / stride 1 / pad 1 with 33 .. 128 filters (TN = 2 or 4 column tiles of 32), cin % 64 == 0.
+// Tile stream, fragment addresses and the epilogue's constants are the shared pieces above; the loader's halo staging and the
+// epilogue's loop are the narrow kernel's text again; the filter ring and the unit of eighteen taps are this kernel's.
 //
 // The kernel above runs one PASS per 32 filters over a staged halo patch and re-reads the pixel fragments from LDS in every
 // pass (one 16-byte read per MFMA).  Here a compute wave keeps its pixel fragments (2 row tiles x hi / lo) for a k-half
@@ -437,11 +458,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
   char* lds = reinterpret_cast<char*>(smem);
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds;
 
-  const int tiles_x = (p.out_w + TW - 1) / TW, tiles_y = (p.out_h + TH - 1) / TH;
-  const int ntiles = p.n * tiles_x * tiles_y;
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int per_x = (ntiles + 7) / 8;
-  const int xcd = bid & 7, slot = bid >> 3, slots = (nb + 7 - xcd) / 8;
+  const HaloTiles ts(p, gridDim.x, blockIdx.x);
 
   const int lane = threadIdx.x & 63;
   const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -451,18 +468,19 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
   const int nslices = p.ctiles;                       // even (launcher)
   const int T = 9 * nslices;                          // taps per tile
 
-  int it = slot;
-  if (it >= per_x || xcd * per_x + it >= ntiles) return;
+  int it = ts.slot;
+  if (!ts.has(it)) return;
 
   if (loader) {
     // =================================================================== loader waves
-    const int lrow = tid >> 3;
-    const int csrc = (tid & 7) ^ swz(lrow);
+    // (lrow .. dma_halo: the narrow kernel's text without its comments, see the head of the file)
+    const int lrow = tid >> 3;                          // 0..31 (+32 i)
+    const int csrc = (tid & 7) ^ swz(lrow);             // rows differ by multiples of 32: one swizzle per thread
     __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
     __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
     const unsigned wbase = (unsigned)((lrow * p.wrow) * 4 + csrc * 16);
     unsigned abase[A_LD];
-    int hyx[A_LD];
+    int hyx[A_LD];                                       // halo row lrow + 32 i -> (hy << 8 | hx), or -1 past the patch
 #pragma unroll
     for (int i = 0; i < A_LD; ++i) {
       const int hr = lrow + 32 * i;
@@ -470,22 +488,17 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
       hyx[i] = hr < (TH + 2) * HW_ ? (hy << 8 | hx) : -1;
     }
     auto tile_setup = [&](int tile) {
-      const int tx = tile % tiles_x;
-      const int ty = (tile / tiles_x) % tiles_y;
-      const int ni = tile / (tiles_x * tiles_y);
-      const int y0 = ty * TH, x0 = tx * TW;
+      int ni, y0, x0;
+      ts.coords(tile, ni, y0, x0);
 #pragma unroll
       for (int i = 0; i < A_LD; ++i) {
         const int y = y0 - p.pad_h + (hyx[i] >> 8), x = x0 - 1 + (hyx[i] & 255);
         const bool ok = hyx[i] >= 0 && (unsigned)y < (unsigned)p.in_h && (unsigned)x < (unsigned)p.in_w;
-        // in_up2: the logical input is the nearest x2 of the physical one (RRDB's upconv1 / upconv2): the halo row of logical
-        // pixel (y, x) is physical pixel (y / 2, x / 2); p.ph / p.pw are the physical sizes (= in_h / in_w otherwise)
         const int yp = p.in_up2 ? y >> 1 : y, xp = p.in_up2 ? x >> 1 : x;
         abase[i] = ok ? ((unsigned)((ni * p.ph + yp) * p.pw + xp) * (unsigned)p.in_ld + (unsigned)(csrc * 4)) * 4u : 0xFFFFFFFFu;
       }
     };
-    constexpr int HALO_I = A_LD - 1;                      // halo instructions every loader wave issues (waves 0..2: one more)
-    auto dma_halo = [&](int cs, int stage) {
+    auto dma_halo = [&](int cs, int stage) {             // 11 (waves 0..2) / 10 (wave 3) instructions
       char* a = lds + stage * A_BYTES + wave_u * 8 * ROWB;
 #pragma unroll
       for (int i = 0; i < A_LD - 1; ++i) {
@@ -493,7 +506,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (__attribute__((address_space(3))) void*)(a + 32 * i * ROWB), 16,
                                                  (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)(cs * 128)), 0, 0, 0);
       }
-      if (wave_u < 3) {
+      if (wave_u < 3) {   // rows 320..343
         const unsigned ro = abase[A_LD - 1];
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (__attribute__((address_space(3))) void*)(a + 32 * (A_LD - 1) * ROWB), 16,
                                                  (int)(ro == 0xFFFFFFFFu ? 0xFFFFFFFFu : ro + (unsigned)(cs * 128)), 0, 0, 0);
@@ -502,7 +515,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
     // within-tile tap gt (slice gt / 9, tap gt % 9) into ring slot `rs`: TN instructions (32 filter rows each)
     auto dma_tap = [&](int gt, int rs) {
       const int cs = gt / 9, tap = gt - cs * 9;
-      char* b = lds + B_OFF + rs * TAPB + wave_u * 8 * ROWB;
+      char* b = (lds + wave_u * 8 * ROWB) + B_OFF + rs * TAPB;
       const unsigned wo = wbase + (unsigned)(cs * 9 * 128 + tap * 128);
 #pragma unroll
       for (int k = 0; k < TN; ++k)
@@ -510,7 +523,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
                                                  (int)(wo + (unsigned)(k * 32 * p.wrow * 4)), 0, 0, 0);
     };
 
-    tile_setup(xcd * per_x + it);
+    tile_setup(ts.tile(it));
     dma_halo(0, 0);
     dma_halo(1, 1);
 #pragma unroll
@@ -521,8 +534,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                         // P: slices 0, 1 and taps 0 .. PRE - 1 are in LDS
     for (;;) {
-      const int nit = it + slots, ntile = xcd * per_x + nit;
-      const bool more = nit < per_x && ntile < ntiles;
+      const HaloTiles::Next nx = ts.next(it);
       if constexpr (SLACK2) {
         // everything issued before the previous barrier has landed (what was issued behind it may still fly)
         if (pend >= BT * TN + HALO_I) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BT * TN + HALO_I) : "memory");
@@ -537,14 +549,14 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
       for (int e = 0; e < BT; ++e) {
         const int ta = g + PRE + e;                                    // filters do not depend on the tile: only its existence matters
         if (ta < T) { dma_tap(ta, (int)((G + (unsigned)(PRE + e)) & (unsigned)(RS - 1))); pend += TN; }
-        else if (more) { dma_tap(ta - T, (int)((G + (unsigned)(PRE + e)) & (unsigned)(RS - 1))); pend += TN; }
+        else if (nx.more) { dma_tap(ta - T, (int)((G + (unsigned)(PRE + e)) & (unsigned)(RS - 1))); pend += TN; }
       }
       const int t8 = (g / 9) * 9 - 1;                                // the last "tap 8 of a slice" before tap g
       if (t8 >= 0 && t8 >= g - BT) {                                 // it was in the previous block: its stage takes the slice two ahead
         const int died = t8 / 9, s2 = died + 2, stage = died & 1;
         if (s2 < nslices) { dma_halo(s2, stage); pend += HALO_I; }
-        else if (more) {                                             // s2 == nslices: the next tile's first slice; its addresses replace this tile's
-          tile_setup(ntile);
+        else if (nx.more) {                                          // s2 == nslices: the next tile's first slice; its addresses replace this tile's
+          tile_setup(nx.ntile);
           dma_halo(0, stage);
           pend += HALO_I;
         }
@@ -553,10 +565,10 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
       if (g == T) {
         // the tile's last block is running; its last slice lives in stage 1, which hosts the epilogue before it is refilled
         __builtin_amdgcn_s_barrier();                                  // E: the compute waves have read the finished tile back from stage 1
-        if (!more) return;
+        if (!nx.more) return;
         dma_halo(1, 1);
         pend += HALO_I;
-        it = nit;
+        it = nx.nit;
         g = 0;
       }
     }
@@ -564,20 +576,14 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
 
   // ===================================================================== compute waves
   const int xl = lane & 31, half = lane >> 5;
-  // Fragment addresses of the halo patch (see the kernel above).  Recomputed at the top of every unit from an opaque copy
-  // of the lane index (~100 vector instructions per 864 MFMAs): kept across the epilogue they are what the register
-  // allocator spills, and a reload in front of a fragment read stalls the wave's MFMA stream.
+  // Fragment addresses of the halo patch.  Recomputed at the top of every unit from an opaque copy of the lane index (~100
+  // vector instructions per 864 MFMAs): kept across the epilogue they are what the register allocator spills, and a reload
+  // in front of a fragment read stalls the wave's MFMA stream.
   unsigned aaddr[4][3];
   auto make_aaddr = [&]() {
     int xo = xl;
     asm volatile("" : "+v"(xo));
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int hr = (2 * wave_u + d) * HW_ + xo + kw;
-        aaddr[d][kw] = lds0 + (unsigned)(hr * ROWB + ((half ^ swz(hr)) << 4));
-      }
+    halo_frag_addrs(aaddr, lds0, wave_u, xo, half);
   };
   make_aaddr();
   // filter fragments: row xl (+ 32 j) of ring slot k, chunk c ^ swz(xl); the unit's tap t reads slot t % 4 of bslot[],
@@ -610,15 +616,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
   __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.in2_bytes, 0x00020000);   // in2_bytes: size of `out` (halo launches)
 
   f32x16 acc[TN][2];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int n = 0; n < TN; ++n)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[n][i][e] = 0.f;
-  };
-  zero_acc();
+  clear_acc(acc);
 
   __builtin_amdgcn_s_barrier();                         // P
   __builtin_amdgcn_sched_barrier(0);
@@ -684,12 +682,11 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
     });
   };
 
-  // epilogue of the finished tile through a [256 pixels][32 channels] fp32 tile in halo stage 1 (just freed), one column
-  // tile at a time; a wave stages, reads back and stores only ITS OWN 64 pixels
+  // epilogue of the finished tile through halo stage 1 (its last slice's, just freed), one column tile at a time: the narrow
+  // kernel's loop (see there and halo_epi_consts) with a fence per column tile and, without residuals, one row per round trip
   auto epilogue = [&]() {
-    const int tile = xcd * per_x + it;                               // coordinates of the finished tile (scalar, recomputed: registers)
-    const int e_tx = tile % tiles_x, e_ty = (tile / tiles_x) % tiles_y;
-    const int e_ni = tile / (tiles_x * tiles_y), e_y0 = e_ty * TH, e_x0 = e_tx * TW;
+    int e_ni, e_y0, e_x0;                                            // coordinates of the finished tile (scalar, recomputed: registers)
+    ts.coords(ts.tile(it), e_ni, e_y0, e_x0);
     const unsigned cs0 = lds0 + (unsigned)(A_BYTES + wave_u * 64 * 128);
     const int eq = lane & 3, er = lane >> 2;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // the last step's requests for the next tile's fragments
@@ -699,11 +696,8 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
       __builtin_amdgcn_sched_barrier(0);
       const int ccol = n * 32 + eq * 8;
       const bool cvalid = ccol < p.cout;
-      f32x4 b8[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, w8[2] = {b8[0], b8[0]};
-      if (cvalid) {
-        if (p.bias != nullptr) { b8[0] = *reinterpret_cast<const f32x4*>(p.bias + ccol); b8[1] = *reinterpret_cast<const f32x4*>(p.bias + ccol + 4); }
-        w8[0] = *reinterpret_cast<const f32x4*>(p.wscale + ccol); w8[1] = *reinterpret_cast<const f32x4*>(p.wscale + ccol + 4);
-      }
+      f32x4 b8[2], w8[2];
+      halo_epi_consts(p, ccol, cvalid, b8, w8);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -768,7 +762,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
   int unit = 0;                                          // unit index inside the current tile
   const int nunits = nslices / 2;
   for (;;) {
-    if (unit != 0 || it != slot) make_aaddr();           // (the first unit's are in registers already)
+    if (unit != 0 || it != ts.slot) make_aaddr();        // (the first unit's are in registers already)
     fcp_static_for<0, 18>([&](auto tc) {
       constexpr int t = decltype(tc)::value, tn = (t + 1) % 18;
       using OX = std::integral_constant<int, (t / 9) * A_BYTES>;
@@ -783,14 +777,13 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
       bslot[RS - 2] = b0; bslot[RS - 1] = b1;
     }
     if (++unit == nunits) {
-      const int nit = it + slots, ntile = xcd * per_x + nit;
-      const bool more = nit < per_x && ntile < ntiles;
+      const HaloTiles::Next nx = ts.next(it);
       __builtin_amdgcn_sched_barrier(0);
       epilogue();
-      if (!more) break;
-      it = nit;
+      if (!nx.more) break;
+      it = nx.nit;
       unit = 0;
-      zero_acc();
+      clear_acc(acc);
       // The last tap step requested the next tile's first fragments, but holding them across the epilogue costs 24
       // registers the epilogue needs (the allocator spilled the fragment addresses instead): request them again here.
       first_frags();
@@ -802,12 +795,19 @@ __global__ void __launch_bounds__(512, 1) conv3x3_halo_wide_f16x3(const ConvK p)
 
 namespace fcp_conv {
 
-int launch_f16x3_halo(const ConvK& k, hipStream_t s) {
-  const size_t lds = (size_t)LDS_TOTAL;
+// grid of a halo launch: persistent workgroups over the 8 x 32 patches, at most one per CU
+static int halo_grid(const ConvK& k, unsigned* grid) {
   const long tiles = (long)k.n * ((k.out_h + TH - 1) / TH) * ((k.out_w + TW - 1) / TW);
   FCP_REQUIRE(tiles < (1L << 31), "conv(halo): too many tiles");
   const int cus = fcp_cu_count();
-  const unsigned grid = (unsigned)(tiles < cus ? tiles : cus);
+  *grid = (unsigned)(tiles < cus ? tiles : cus);
+  return 0;
+}
+
+int launch_f16x3_halo(const ConvK& k, hipStream_t s) {
+  const size_t lds = (size_t)LDS_TOTAL;
+  unsigned grid = 0;
+  if (const int e = halo_grid(k, &grid)) return e;
   if (k.cout <= 32) {
     FCP_LDS_OPT_IN(&conv3x3_halo_f16x3<1>, lds);
     hipLaunchKernelGGL(conv3x3_halo_f16x3<1>, dim3(grid), dim3(512), lds, s, k);
@@ -824,12 +824,10 @@ constexpr int WIDE2_BT = 2;   // taps per barrier of the 64-filter form (eight 8
 int launch_f16x3_halo_wide(const ConvK& k, hipStream_t s) {
   const int tn = k.cout <= 64 ? 2 : 4;
   const size_t lds = (size_t)(2 * A_BYTES + (tn == 2 ? 8 : 4) * tn * 32 * ROWB);   // TN = 2: eight 8 KB slots; TN = 4: four 16 KB slots
-  const long tiles = (long)k.n * ((k.out_h + TH - 1) / TH) * ((k.out_w + TW - 1) / TW);
-  FCP_REQUIRE(tiles < (1L << 31), "conv(halo): too many tiles");
+  unsigned grid = 0;
+  if (const int e = halo_grid(k, &grid)) return e;
   FCP_REQUIRE(k.ctiles >= 2 && k.ctiles % 2 == 0 && k.cout <= 128, "conv(halo, wide): cin must be a multiple of 64, cout <= 128");
   FCP_REQUIRE(tn == 2 || (k.res1 == nullptr && k.res2 == nullptr), "conv(halo, wide): no residual inputs with more than 64 filters");
-  const int cus = fcp_cu_count();
-  const unsigned grid = (unsigned)(tiles < cus ? tiles : cus);
   if (tn == 2) {
     FCP_LDS_OPT_IN((&conv3x3_halo_wide_f16x3<2, true, WIDE2_BT, 8>), lds);
     hipLaunchKernelGGL((conv3x3_halo_wide_f16x3<2, true, WIDE2_BT, 8>), dim3(grid), dim3(512), lds, s, k);

@@ -6,7 +6,9 @@ after the activation, leaky slope, alpha, second residual): the three generic ep
 kernels, the bottleneck-chain forms and the fused stem + pool + conv1.  The walk cases (``_walk_rows``) hold the epilogue at one
 setting and vary what the front half of the generic kernels keeps books on (fcp_conv_common.h: xcd_tile_order, conv_row,
 TapWalk, set_tap, dma_slice): stride, 25 taps, one / two / three K slices, an image boundary inside a ragged M tile, the
-nearest-x2 fetch, the 3-channel NHWC4 mode, row bands, a second source, and flat 64-bit addressing.
+nearest-x2 fetch, the 3-channel NHWC4 mode, row bands, a second source, and flat 64-bit addressing.  The halo walk cases
+(``_halo_walk_rows``) do the same for what the two halo-tile kernels keep books on around their tap loops
+(fcp_conv_f16x3_halo.hip: HaloTiles, the loader waves' tile_setup / dma_halo, halo_frag_addrs).
 
 Inputs, filters, bias and residuals come from ``numpy.random.default_rng(seed)`` (mean zero; the seed is the CRC of the case
 id); tiles are explicit, so the autotuner plays no part.  ``run_case`` returns, per tile choice, the raw bytes of every output
@@ -67,6 +69,33 @@ def _walk_rows():
     return rows
 
 
+def _halo_walk_rows():
+    """Rows about what the halo-tile kernels keep books on around their tap loops (fcp_conv_f16x3_halo.hip: HaloTiles,
+    tile_setup / dma_halo, halo_frag_addrs), each next to the generic tile of the shape: the nearest-x2 fetch, odd / even / three-unit slice
+    counts, row bands, and workgroups that chain two or three tiles (both refill paths across a tile boundary)."""
+    base = dict(precision="f16x3", in_fmt=1, out_fmt=1, k=3, n=2, settings=WALK)
+    forms = {"n32": dict(base, cout=32, tiles=[(128, 64), (1, 32)]),               # narrow, one pass
+             "n64": dict(base, cout=64, tiles=[(128, 64), (1, 32)]),               # narrow, two passes
+             "w64": dict(base, cout=64, tiles=[(128, 64), (1, 64)]),               # wide, two column tiles (residual form)
+             "w128": dict(base, cout=128, tiles=[(128, 128), (1, 128)])}           # wide, four column tiles
+    rows = []
+    for f in ("n32", "n64", "w64", "w128"):                           # physical 5 x 6 read as 10 x 12
+        rows.append((f"halowalk_up2_{f}", dict(forms[f], cin=128 if f == "w128" else 64, h=5, w=6, in_up2=True)))
+    for cin in (96, 128):                                             # 3 slices (odd: stage parity), 4 slices
+        for f in ("n32", "n64"):
+            rows.append((f"halowalk_cin{cin}_{f}", dict(forms[f], cin=cin, h=9, w=33)))
+    for f in ("w64", "w128"):                                         # three 18-tap units: the ring-slot rotation comes round
+        rows.append((f"halowalk_cin192_{f}", dict(forms[f], cin=192, h=9, w=33)))
+    for band in ((1, 0), (0, 1), (1, 1)):                             # 9 input rows -> 8, 8, 7 output rows
+        for f in ("n32", "w64"):
+            rows.append((f"halowalk_band{band[0]}{band[1]}_{f}", dict(forms[f], cin=64, h=9, w=33, band=band)))
+    # 2 x 130 x 2 = 520 patches, half of them one column wide: with up to 260 workgroups every one walks two or three tiles
+    for f in ("n32", "n64", "w64"):
+        rows.append((f"halowalk_chain_{f}", dict(forms[f], cin=64, h=1040, w=33)))
+    rows.append(("halowalk_chain_cin96_n32", dict(forms["n32"], cin=96, h=1040, w=33)))   # odd slices: the delayed second-slice refill
+    return rows
+
+
 def _generic_rows():
     """(row id, dict(precision, in_fmt, out_fmt, cin, cout, k, n, h, w, tiles, settings[, out_c0, balance])), then the walk rows"""
     rows = []
@@ -96,7 +125,7 @@ def _generic_rows():
         for cout in (72, 128):                                        # halo wide (1, 128): no residual inputs
             rows.append((f"halowide128_c{cout}_{h}x{w}", dict(precision="f16x3", in_fmt=1, out_fmt=int(cout % 32 == 0), cin=128, cout=cout, k=3, n=2, h=h, w=w,
                                                               tiles=[(128, 64), (128, 128), (1, 128)], settings=NO_RES)))
-    return rows + _walk_rows()
+    return rows + _walk_rows() + _halo_walk_rows()
 
 
 def cases():

@@ -4,7 +4,8 @@
 
 Run on an MI355X with the library built from the commit whose bits are the reference (the fixture in the repository was
 recorded at the parent of the commit that introduced the shared epilogue helpers, and again, with the walk cases added and the
-older hashes reproduced, at the parent of the commit that introduced the shared im2col walk).  A case whose tile choices disagree is an
+older hashes reproduced, at the parent of the commit that introduced the shared im2col walk, and once more, with the halo walk
+cases added, at the parent of the commit that gathered the halo kernels' shared pieces).  A case whose tile choices disagree is an
 error here too: the hash would depend on the tile.  A later change of the K order (or of the epilogue's arithmetic) that is
 meant to change bits regenerates the file with this script.
 """

@@ -12,7 +12,10 @@ The epilogue cases: each generic epilogue behind each generic kernel under five 
 bottleneck-chain forms, the fused stem + pool + conv1 (hashes from the parent of the commit that gathered the epilogue).  The
 walk cases, under one epilogue setting: stride 2, 25 taps, one / two / three K slices, a ragged M tile across an image boundary,
 the nearest-x2 fetch, the 3-channel NHWC4 mode, row bands, a second source and flat addressing, each on every generic kernel
-that takes it (hashes from the parent of the commit that gathered the walk, which reproduced the older ones).
+that takes it (hashes from the parent of the commit that gathered the walk, which reproduced the older ones).  The halo walk
+cases, under the same setting, each next to the generic tile of its shape: the nearest-x2 fetch on the four halo forms, 3 / 4
+slices (narrow) and three 18-tap units (wide), row bands, and 2 x 1040 x 33 images whose 520 patches make every workgroup walk
+two or three tiles (hashes from the parent of the commit that gathered the halo kernels' shared pieces, likewise).
 
 A ReLU case must hold at least one -0.0 (a negative pre-activation times slope 0: part of the epilogue's contract) and one
 positive value, a resized-residual case a residual map smaller than the output: no case passes trivially.
