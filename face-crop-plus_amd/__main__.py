@@ -80,6 +80,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="fill the matte's pinholes: the largest enclosed background region, in output pixels "
                         "(1..67108864), that becomes foreground (with --background or --background-blur); by default holes "
                         "stay")
+    p.add_argument("-es", "--edge-shift", type=int, default=argparse.SUPPRESS,
+                   help="grow (positive) or shrink (negative) the matte by this many output pixels, a non-zero int -64..64, "
+                        "before its soft edge is made: -2 removes the ring of old background the parser leaves around the "
+                        "subject (with --background or --background-blur); by default the boundary stays")
     p.add_argument("-dc", "--decontaminate", type=float, default=argparse.SUPPRESS,
                    help="give the soft edge of the matte the subject's own colour in place of its mix with the old "
                         "background: sigma in output pixels, 0.5..16, about the width of the soft edge or more (with "

@@ -69,6 +69,7 @@ class Cropper:
         subject: str | None = None,
         fill_holes: int | None = None,
         decontaminate: float | None = None,
+        edge_shift: int | None = None,
         clahe: float | None = None,
         clahe_grid: int | None = None,
         interpolation: str = "linear",
@@ -148,6 +149,19 @@ class Cropper:
         feather, the guided filter, the composite and the blur's background sums.  They need ``background`` or
         ``background_blur`` (ValueError); mask files are untouched and a face without a foreground pixel behaves as
         before.  None (the default) launches nothing.
+        ``edge_shift``: grow or shrink the matte — the pixels (a non-zero int -64..64) by which the boundary of the hard
+        mask moves before any soft edge is made: negative shrinks the subject, positive grows it.  The parser's label
+        map is computed at its own resolution and resampled, so along hair, ears and shoulders it sits a pixel or two
+        outside the subject; that ring of old background has alpha 255, ``feather``, ``refine`` and ``decontaminate``
+        all keep it, and it shows as a thin halo on every new background: ``edge_shift=-2`` removes it.  A positive
+        value hands ``refine`` a mask that is a few pixels generous, for wisps of hair and the rims of glasses the
+        parser cuts off, and lets the image's own edges pull it back.  It is binary morphology with a Euclidean disc
+        of that radius, on the device, in integers, held byte for byte to a numpy reference (``matte.shift_mask``,
+        INTEGRATION.md section 2o), and it runs after ``subject`` / ``fill_holes`` and before ``refine``, the feather,
+        the composite and the blur's background sums.  Only positions inside the crop count: a shrink does not eat
+        inwards from the crop's border, so shoulders that touch the bottom row stay there.  It needs ``background`` or
+        ``background_blur`` (ValueError); mask files are untouched, and a face whose subject a shrink erases behaves as
+        a face without a foreground pixel does.  None (the default) launches nothing.
         ``background="transparent"``: write RGBA cut-outs — no fill at all: every crop becomes ``(colour, alpha)`` with the
         matte as its alpha channel and ``(0, 0, 0, 0)`` wherever the alpha is 0, so that nothing of the old background ships
         in the file (``matte.cutout``).  It is a background mode like the fill: it creates the
@@ -232,6 +246,7 @@ class Cropper:
                 raise ValueError("refine and feather exclude each other: the soft edge is the guided filter's or the Gaussian's")
         self.subject = matting.check_subject(subject)
         self.fill_holes = matting.check_fill_holes(fill_holes)
+        self.edge_shift = matting.check_edge_shift(edge_shift)
         if self.background is None and self.background_blur is None:
             if foreground is not None or feather is not None:
                 raise ValueError("foreground / feather need background or background_blur: without one they would do nothing")
@@ -239,6 +254,8 @@ class Cropper:
                 raise ValueError("refine needs background or background_blur: without one it would do nothing")
             if self.subject is not None or self.fill_holes is not None:
                 raise ValueError("subject / fill_holes need background or background_blur: without one they would do nothing")
+            if self.edge_shift is not None:
+                raise ValueError("edge_shift needs background or background_blur: without one it would do nothing")
             self.foreground, self.foreground_bits, self.feather = None, 0, None
         else:
             if det_threshold is None and landmarks is None:
@@ -416,7 +433,8 @@ class Cropper:
         uint8 labels -> (the composited crops (F,H,W,3) uint8, the alpha (F,H,W) uint8), with this Cropper's
         ``background`` / ``foreground`` / ``feather`` (``matte.matte``), or with its ``background_blur``
         (``matte.matte_blur``); with ``refine`` the alpha is the guided filter's (``matte.refine_alpha``) and the
-        composite goes through it; with ``subject`` / ``fill_holes`` the mask is cleaned first (``matte.subject_mask``).
+        composite goes through it; with ``subject`` / ``fill_holes`` the mask is cleaned first (``matte.subject_mask``),
+        and with ``edge_shift`` its boundary is then moved (``matte.shift_mask``).
         With ``background="transparent"`` the first array is the RGBA cut-out (F,H,W,4) itself; with ``decontaminate`` its
         colours, or those composited over the fill, are the estimated subject colours (``matte.cutout``)."""
         if self.background is None and self.background_blur is None:
@@ -435,11 +453,16 @@ class Cropper:
 
     def _matte_device(self, crops_dev, labels_dev, with_alpha=False):
         """The matte step on device tensors: the cleaned mask first when ``subject`` / ``fill_holes`` are set (it takes
-        the label map's place, as class 1), the refined alpha when ``refine`` is set, then the composite."""
+        the label map's place, as class 1), its boundary moved when ``edge_shift`` is set (likewise), the refined alpha when
+        ``refine`` is set, then the composite."""
         bits = self.foreground_bits
         subject, fill_holes = getattr(self, "subject", None), getattr(self, "fill_holes", None)
         if subject is not None or fill_holes is not None:
             labels_dev = matting.subject_mask(labels_dev, bits, subject is not None, fill_holes or 0)
+            bits = matting.SUBJECT_BITS
+        edge_shift = getattr(self, "edge_shift", None)         # absent on a Cropper made with __new__, like subject above
+        if edge_shift is not None:
+            labels_dev = matting.shift_mask(labels_dev, bits, edge_shift)
             bits = matting.SUBJECT_BITS
         refined = {}
         if getattr(self, "refine", None) is not None:

@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout / mask_shift
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -696,6 +696,21 @@ Tensor subject_mask(const Tensor& labels, int64_t class_bits, bool keep_largest,
   return out;
 }
 
+// The hard mask (f,h,w) uint8, 0 / 1, of label maps (f,h,w) uint8, grown (shift > 0) or shrunk (shift < 0) by a Euclidean
+// disc of radius |shift| inside the crop (fcp_mask_shift_u8).
+Tensor mask_shift(const Tensor& labels, int64_t class_bits, int64_t shift) {
+  dev(labels, "labels", at::kByte);
+  FCP_DEVICE_GUARD(labels);
+  int64_t f, h, w;
+  labels_plane(labels, class_bits, f, h, w);
+  TORCH_CHECK(shift >= INT_MIN && shift <= INT_MAX, "shift past int");
+  Tensor out = at::empty_like(labels);
+  ok(fcp_mask_shift_u8(labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits, (int)shift, out.data_ptr<uint8_t>(),
+                       cur_stream()),
+     "fcp::mask_shift");
+  return out;
+}
+
 // Crops (f,h,w,3) uint8 with the luma equalised by CLAHE on a grid x grid tiling (fcp_clahe_u8); the LUT workspace
 // lives for the call.
 Tensor clahe(const Tensor& crops, int64_t grid, double clip_limit) {
@@ -787,6 +802,7 @@ TORCH_LIBRARY(fcp, m) {
   m.def("subject_mask(Tensor labels, int class_bits, bool keep_largest, int max_hole) -> Tensor");
   m.def("feather_alpha(Tensor labels, int class_bits, int feather) -> Tensor");
   m.def("cutout(Tensor crops, Tensor alpha, int mode, int bg_r, int bg_g, int bg_b, int[] taps) -> Tensor");
+  m.def("mask_shift(Tensor labels, int class_bits, int shift) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -825,6 +841,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("subject_mask", &subject_mask);
   m.impl("feather_alpha", &feather_alpha);
   m.impl("cutout", &cutout);
+  m.impl("mask_shift", &mask_shift);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

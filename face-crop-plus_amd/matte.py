@@ -40,6 +40,18 @@ with the old background, by an estimate of the subject's own, for the cut-out an
              the window holds no such pixel)
     R      = 255 c - (alpha F^ + (255 - alpha) B^)
     F      = clamp((65025 F^ + alpha R + 32512) // 65025, 0, 255) where 0 < alpha < 255, else c
+
+``Cropper(edge_shift=N)`` (section 2o) moves the boundary of the hard mask out (N > 0) or in (N < 0) by |N| pixels after
+``subject`` / ``fill_holes`` and before every soft edge (``shift_mask``: ``fcp_mask_shift_u8`` /
+``torch.ops.fcp.mask_shift``), every face on its own: binary morphology with a Euclidean disc, r = |N|:
+
+    m0(y,x) = (class_bits >> labels(y,x)) & 1; only positions inside the crop exist: a pixel outside the crop is neither
+            subject nor background, and it is never a source
+    N > 0 (grow): out(y,x) = 1 iff some (y',x') inside the crop has m0 = 1 and (y-y')^2 + (x-x')^2 <= r^2
+    N < 0 (shrink): out(y,x) = 1 iff m0(y,x) = 1 and no (y',x') inside the crop has m0 = 0 and (y-y')^2 + (x-x')^2 <= r^2
+    out(y,x) is one byte, 0 or 1, and takes the label map's place downstream like ``subject_mask``'s (``SUBJECT_BITS``)
+
+A shrink does not eat inwards from the crop's border: shoulders that touch the bottom row stay there.
 """
 from __future__ import annotations
 
@@ -65,6 +77,7 @@ MAX_FILL_HOLES = 8192 * 8192   # the largest crop the kernels take
 SUBJECT_BITS = 1 << 1          # the class bit set that reads ``subject_mask``'s 0 / 1 output as a label map: class 1
 TRANSPARENT = "transparent"    # ``check_background``'s answer for the RGBA cut-out: no fill, the alpha ships in the file
 CUTOUT_RGBA, CUTOUT_FILL = 0, 1   # fcp_hip.h: FCP_CUTOUT_RGBA, FCP_CUTOUT_FILL
+MAX_EDGE_SHIFT = 64            # the largest |edge_shift|, in output pixels: the halo a tile of fcp_mask_shift_u8 stages
 
 
 def _is_int(v) -> bool:
@@ -173,6 +186,17 @@ def check_fill_holes(fill_holes):
     return int(fill_holes)
 
 
+def check_edge_shift(edge_shift):
+    """``edge_shift`` of the Cropper -> None (off) or the pixels the matte's boundary moves, a non-zero int -64..64:
+    positive grows the subject, negative shrinks it."""
+    if edge_shift is None:
+        return None
+    if not _is_int(edge_shift) or int(edge_shift) == 0 or not -MAX_EDGE_SHIFT <= int(edge_shift) <= MAX_EDGE_SHIFT:
+        raise ValueError(f"edge_shift must be None or a non-zero int -{MAX_EDGE_SHIFT}..{MAX_EDGE_SHIFT} (pixels: positive grows "
+                         f"the subject, negative shrinks it), not {edge_shift!r}")
+    return int(edge_shift)
+
+
 def blur_taps(sigma) -> list:
     """sigma -> the integer taps t[0..r] of the background blur, in float64: r = min(48, max(3, ceil(3 sigma))),
     g_k = exp(-k^2 / (2 sigma^2)), s = g_0 + 2 sum g_k, t_k = max(1, floor(4096 g_k / s)) for k >= 1 and t_0 the rest of
@@ -241,6 +265,20 @@ def subject_mask(labels_dev: torch.Tensor, class_bits: int, keep_largest: bool, 
     work = torch.empty((need,), dtype=torch.uint8, device=labels_dev.device)
     N.check(N.lib().fcp_subject_mask_u8(N.ptr(labels_dev), f, h, w, int(class_bits), int(bool(keep_largest)), int(max_hole),
                                         N.ptr(out), N.ptr(work), need, N.stream_ptr()), "fcp_subject_mask_u8")
+    return out
+
+
+def shift_mask(labels_dev: torch.Tensor, class_bits: int, shift: int) -> torch.Tensor:
+    """labels (F,H,W) u8, device -> out (F,H,W) u8 of 0 / 1, device: the hard mask of the labels grown (``shift`` > 0) or
+    shrunk (``shift`` < 0) by a Euclidean disc of radius |shift| <= 64 inside the crop, in integers (INTEGRATION.md section
+    2o); 0 gives the hard mask itself.  One launch, no workspace; H, W <= 8192."""
+    assert labels_dev.dtype == torch.uint8 and labels_dev.is_contiguous() and labels_dev.dim() == 3
+    if T.ENABLED:
+        return T.load().mask_shift(labels_dev, int(class_bits), int(shift))
+    f, h, w = labels_dev.shape
+    out = torch.empty_like(labels_dev)
+    N.check(N.lib().fcp_mask_shift_u8(N.ptr(labels_dev), f, h, w, int(class_bits), int(shift), N.ptr(out), N.stream_ptr()),
+            "fcp_mask_shift_u8")
     return out
 
 

@@ -776,6 +776,34 @@ int64_t fcp_subject_mask_workspace_bytes(int f, int h, int w);
 int fcp_subject_mask_u8(const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int keep_largest, int max_hole, uint8_t* out,
                         void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
 
+/* Grow or shrink the matte: binary morphology of the hard
+ * mask of label maps (f,h,w) uint8 with a Euclidean disc, every face on its
+ * own, in integers.  r = |shift|:
+ *   m0(y,x) = (class_bits >> labels(y,x)) & 1 (the hard mask of fcp_matte_u8;
+ *             label bytes at or above 19 are background, as there);
+ *   only positions inside the crop exist: a pixel outside the crop is
+ *             neither subject nor background, and it is never a source;
+ *   shift > 0 (grow): out(y,x) = 1 iff some (y',x') inside the crop has
+ *             m0 = 1 and (y-y')^2 + (x-x')^2 <= r^2;
+ *   shift < 0 (shrink): out(y,x) = 1 iff m0(y,x) = 1 and no (y',x') inside
+ *             the crop has m0 = 0 and (y-y')^2 + (x-x')^2 <= r^2;
+ *   shift = 0: out = m0 (legal, like fcp_subject_mask_u8 with (0, 0));
+ *   out(y,x) is one byte, 0 or 1, read downstream as class 1.
+ * That is scipy.ndimage.binary_dilation(m0, disc, border_value=0) for a grow
+ * and binary_erosion(m0, disc, border_value=1) for a shrink with
+ * disc = {dy^2 + dx^2 <= r^2}, and the threshold d^2 <= r^2 of the exact
+ * squared Euclidean distance to the nearest source pixel.  A shrink does not
+ * eat inwards from the crop's border: a subject that touches it stays there.
+ * One launch on `stream`, no workspace, nothing allocated, no float and no
+ * atomics: the same bytes from run to run.  labels and out may start at any
+ * byte and must not overlap (a tile reads the halo its neighbours write);
+ * nothing outside out is written.
+ * f == 0 is a no-op; f < 0, h or w < 1 or > 8192, f > 65535, a bit of
+ * class_bits at or above 19, a shift outside -64..64, or (f > 0) a null
+ * labels / out fail with a "mask_shift:" message, before any HIP call. */
+int fcp_mask_shift_u8(const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int shift, uint8_t* out,
+                      fcp_stream_t stream);
+
 /* Contrast-limited adaptive histogram equalisation of the luma of crops
  * (f,h,w,3) uint8 RGB: cv2.createCLAHE(clip_limit,
  * (grid, grid)).apply(Y) between cv2.cvtColor(COLOR_RGB2YCrCb) and
