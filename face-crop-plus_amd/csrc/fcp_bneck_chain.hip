@@ -77,7 +77,7 @@ constexpr int r0_bytes(int cw, int cn, bool has_c2) { return has_c2 ? 2 * STAGE 
 // In the pair forms T2 ALIASES the chunk buffers: a wave's T2 fragments are the same for every chunk and live in
 // registers, so the tile is only needed until they have been read.  That is what lets the 256-wide pair fit at all
 // (144 + 128 KiB otherwise) and brings the 128-wide pairs down to 80 KiB: TWO workgroups per CU, the second one's
-// MFMAs under the first one's epilogue (FCP_CHAIN_NOALIAS: the 128-wide pairs as before, 128-144 KiB, one per CU).
+// MFMAs under the first one's epilogue (without the alias the 128-wide pairs took 128-144 KiB, one per CU).
 constexpr bool alias_t2(bool has_c2) { return !has_c2; }
 // DIRECT (two-source pair forms, round 5): the operand tile never exists in LDS at all — a lane's fragments are 16-byte pieces of
 // the split32 pixel rows, i.e. plain buffer loads straight into the registers they live in for the whole chunk loop (a
@@ -92,6 +92,24 @@ constexpr int wgs_per_cu(int cw, int cn, bool has_c2, bool direct = false) {
   // no conv1' — no accumulators, no conv1' buffers: 80 KiB, < 256 registers) runs two workgroups per CU
   if (direct) return cn == 0 && lds_bytes(cw, cn, has_c2, true) <= 80 * 1024 ? 2 : 1;
   return lds_bytes(cw, cn, has_c2) <= 80 * 1024 ? 2 : 1;
+}
+
+// acc += al * bh + ah * bl + ah * bh: the fp16x3 product of one k-half, the small terms first
+__device__ __forceinline__ void mfma3(f32x16& acc, const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+}
+
+// Eight channels of an fp32 tile row -> relu(acc * ws + b) (conv2's and conv1's tile epilogues)
+__device__ __forceinline__ void row_values8(const float* c8, const float (&ws8)[8], const float (&b8)[8], float (&v)[8]) {
+  const f32x4 a = *reinterpret_cast<const f32x4*>(c8);
+  const f32x4 b = *reinterpret_cast<const f32x4*>(c8 + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[e] = conv_value_relu(a[e], ws8[e], b8[e]);
+    v[4 + e] = conv_value_relu(b[e], ws8[4 + e], b8[4 + e]);
+  }
 }
 
 // PATCH (the conv2 forms): the tile is an 8 x 16 PATCH of one image instead of 128 consecutive pixels, and phase 1 stages the
@@ -134,28 +152,14 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
   // stretch phase 2 to 5250 cycles for 768 cycles of MFMAs: the burst wins there (layer-2 pair 644 -> 525-548 us).  The
   // conv2 forms (two per CU, few filter pieces) are 1.5 % better spread.  profiles/r03_probes.md.
   constexpr bool SPREAD = W1DB && (HAS_C2 || WPS == 1);
-  // Rotated chunk loop (experiment builds, FCP_CHAIN_ROT; the one-wave-per-SIMD pair forms: 512 registers per wave): phase 3
-  // of chunk j - 1 is issued BETWEEN the phase-2 MFMAs of chunk j (phase 2 is one dependent chain on a single accumulator,
-  // phase 3 is 6 TN3 MFMAs on TN3 independent accumulators); conv1' slice j is then fetched during chunk j and the T3
-  // fragments of chunk j are read into registers at the end of chunk j.  Bit-identical (tools/fuzz_chain.py), 10 % fewer
-  // cycles per chunk in the probes (8320 -> 7490) and 7 % MORE wall time on the layer-3 pair (440 -> 471 us; the
-  // 128 -> 512 -> 256 pair 827-867 -> 820-837): not the default.  profiles/r03_probes.md.
-  constexpr bool ROT = false;
-  constexpr int PQ = ROT ? TN3 / CS : 0;                // phase-3 MFMAs behind every phase-2 MFMA (6 TN3 against 6 CS)
-  static_assert(!ROT || (TN3 % CS == 0 && PQ >= 1), "rotated loop: TN3 must be a multiple of CS");
-  constexpr bool W1PRE = !ROT && W1DB && !DIRECT && (HAS_C2 ? CN <= 64 || WPS == 1 : CN <= 128 && WPS == 1);   // conv1' fragments of a chunk requested under phase 2 (registers permitting)
+  constexpr bool W1PRE = W1DB && !DIRECT && (HAS_C2 ? CN <= 64 || WPS == 1 : CN <= 128 && WPS == 1);   // conv1' fragments of a chunk requested under phase 2 (registers permitting)
   constexpr int W3B_OFF = w3b_off(CN, HAS_C2);
   static_assert(!HAS_C2 || W3B_OFF + 2 * W3CH <= 2 * STAGE, "chunk buffers must fit the phase-1 stage region");
   constexpr int NRES = HAS_RES ? 4 : 0;             // residual loads per chunk and thread
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* lds = reinterpret_cast<char*>(smem);
 
-  // (xcd_tile_order spelt out: through the helper the sum's two scalar instructions come out in other registers, and this
-  //  file's kernels are to stay instruction-identical: profiles/conv_walk.md)
-  const int nb = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int tile_m = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int tile_m = xcd_tile_order(gridDim.x, blockIdx.x);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -164,13 +168,13 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
   const int lrow = tid >> 3;                                     // 0..LR-1 (+LR i)
   const int csrc = (tid & 7) ^ swz(lrow);                        // source chunk of LDS position tid & 7
   const int l31 = lane & 31, half = lane >> 5;
-  const int rsw = swz(l31);
   int offH[2], offL[2];                                          // fragment chunk offsets inside a 128-byte row, per k-half
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    offH[s] = ((2 * s + half) ^ rsw) << 4;
-    offL[s] = ((4 + 2 * s + half) ^ rsw) << 4;
-  }
+  frag_offsets(lane, offH, offL);
+  // the hi and lo fragment of k-half s of the 128-byte operand row at `row`
+  auto frag_pair = [&](const char* row, int s, f16x8& hi, f16x8& lo) {
+    hi = *reinterpret_cast<const f16x8*>(row + offH[s]);
+    lo = *reinterpret_cast<const f16x8*>(row + offL[s]);
+  };
   const int hw = p.h * p.w;
   // tile row -> pixel index in (n, h, w) order, or -1 for a row that has no pixel (past the end / outside the image)
   int pn = 0, py0 = 0, px0 = 0;                                  // PATCH: image and top-left pixel of the 8 x 16 patch
@@ -213,11 +217,8 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int row = (tid >> 3) + LR * g;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(Cs + row * C + ccol);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(Cs + row * C + ccol + 4);
-        float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = conv_value_relu(v[e], ws8[e], b8[e]);
+        float v[8];
+        row_values8(Cs + row * C + ccol, ws8, b8, v);
         u32x4_t hi, lo;
         split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);
         const int q = (ccol & 31) >> 3, sw = swz(row);
@@ -302,8 +303,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
         }
 #pragma unroll
         for (int sq = 0; sq < 2; ++sq) {
-          bh[sq] = *reinterpret_cast<const f16x8*>(Bb + offH[sq]);
-          bl[sq] = *reinterpret_cast<const f16x8*>(Bb + offL[sq]);
+          frag_pair(Bb, sq, bh[sq], bl[sq]);
         }
         if constexpr (decltype(uc)::value == TPB - 1) {
           // the step's last fragment reads are out: the next step's filters may go into the stage step g - 1 has left.
@@ -316,11 +316,8 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
 #pragma unroll
         for (int sq = 0; sq < 2; ++sq)
 #pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sq][i], bh[sq], acc1[i], 0, 0, 0);
-            acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sq][i], bl[sq], acc1[i], 0, 0, 0);
-            acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sq][i], bh[sq], acc1[i], 0, 0, 0);
-          }
+          for (int i = 0; i < 2; ++i)
+            mfma3(acc1[i], ah[sq][i], al[sq][i], bh[sq], bl[sq]);
         __builtin_amdgcn_sched_barrier(0);
       });
     });
@@ -349,42 +346,35 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
   constexpr int PW3 = 4 * CS / NW;                  // per wave: CS
   constexpr int PW1 = CN / (8 * NW);                // conv1' slice: CN rows, 8 per wave instruction
   static_assert(PW3 >= 1 && (PW1 >= 1 || !HAS_P3), "filter pieces per wave");
+  // piece i of the wave's share of filter group j: 8 rows of one K slice
+  auto w3_piece = [&](int i, int j, int buf) {
+    const int g = wave_u * PW3 + i, sl = g >> 2, r = (g & 3) * 8 + (lane >> 3);
+    char* dst = lds + W3B_OFF + buf * W3CH + sl * 4096 + (g & 3) * 8 * ROWB;
+    const unsigned src = (unsigned)((j * 32 + r) * (CW * 4) + sl * 128 + (((lane & 7) ^ swz(r)) << 4));
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w3, (__attribute__((address_space(3))) void*)dst, 16, (int)src, 0, 0, 0);
+  };
+  // conv1' K slice j: CN rows.  Wave w moves rows w * CN/NW + 8 i + lane / 8, piece i at a time.
+  auto w1_piece = [&](int i, int j, int buf) {
+    char* dst = lds + W1B_OFF + buf * (CN * ROWB) + wave_u * (CN / NW) * ROWB;
+    const int r = wave_u * (CN / NW) + 8 * i + (lane >> 3);
+    const unsigned src = (unsigned)(r * (NOUT * 4) + j * 128 + (((lane & 7) ^ swz(r)) << 4));
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (__attribute__((address_space(3))) void*)(dst + 8 * i * ROWB), 16, (int)src, 0, 0, 0);
+  };
   auto dma_w3 = [&](int j, int buf) {
 #pragma unroll
-    for (int i = 0; i < PW3; ++i) {
-      const int g = wave_u * PW3 + i, sl = g >> 2, r = (g & 3) * 8 + (lane >> 3);
-      char* dst = lds + W3B_OFF + buf * W3CH + sl * 4096 + (g & 3) * 8 * ROWB;
-      const unsigned src = (unsigned)((j * 32 + r) * (CW * 4) + sl * 128 + (((lane & 7) ^ swz(r)) << 4));
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w3, (__attribute__((address_space(3))) void*)dst, 16, (int)src, 0, 0, 0);
-    }
+    for (int i = 0; i < PW3; ++i) w3_piece(i, j, buf);
   };
-  // conv1' K slice j: CN rows.  Wave w moves rows w * CN/NW + 8 i + lane / 8.
   auto dma_w1 = [&](int j, int buf) {
-    char* dst = lds + W1B_OFF + buf * (CN * ROWB) + wave_u * (CN / NW) * ROWB;
 #pragma unroll
-    for (int i = 0; i < PW1; ++i) {
-      const int r = wave_u * (CN / NW) + 8 * i + (lane >> 3);
-      const unsigned src = (unsigned)(r * (NOUT * 4) + j * 128 + (((lane & 7) ^ swz(r)) << 4));
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (__attribute__((address_space(3))) void*)(dst + 8 * i * ROWB), 16, (int)src, 0, 0, 0);
-    }
+    for (int i = 0; i < PW1; ++i) w1_piece(i, j, buf);
   };
   // instruction k of {filter group j, conv1' slice j} (PW3 + PW1 per wave), for issue between the phase-2 MFMAs
+  // (the loops above written as fcp_static_for over dma_one cost seven kernels their code and two of them registers)
   constexpr int NDMA = PW3 + PW1;
   auto dma_one = [&](auto kc, int j, int buf) {
     constexpr int k = decltype(kc)::value;
-    if constexpr (k < PW3) {
-      const int g = wave_u * PW3 + k, sl = g >> 2, r = (g & 3) * 8 + (lane >> 3);
-      char* dst = lds + W3B_OFF + buf * W3CH + sl * 4096 + (g & 3) * 8 * ROWB;
-      const unsigned src = (unsigned)((j * 32 + r) * (CW * 4) + sl * 128 + (((lane & 7) ^ swz(r)) << 4));
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w3, (__attribute__((address_space(3))) void*)dst, 16, (int)src, 0, 0, 0);
-    } else {
-      constexpr int i = k - PW3;
-      const int j1 = ROT ? j - 1 : j, buf1 = ROT ? (j1 & 1) : buf;       // rotated loop: slice j - 1 of the "next" index j
-      char* dst = lds + W1B_OFF + buf1 * (CN * ROWB) + wave_u * (CN / NW) * ROWB;
-      const int r = wave_u * (CN / NW) + 8 * i + (lane >> 3);
-      const unsigned src = (unsigned)(r * (NOUT * 4) + j1 * 128 + (((lane & 7) ^ swz(r)) << 4));
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (__attribute__((address_space(3))) void*)(dst + 8 * i * ROWB), 16, (int)src, 0, 0, 0);
-    }
+    if constexpr (k < PW3) w3_piece(k, j, buf);
+    else w1_piece(k - PW3, j, buf);
   };
 
   f32x16 acc3[TN3A];
@@ -436,8 +426,6 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
     }
   };
   const int nch = NCH;
-  f16x8 pch[2], pcl[2];                                          // rotated loop: T3 fragments of the previous chunk, per k-half
-  f16x8 wx[ROT ? TN3 : 1], wy[ROT ? TN3 : 1];                    // rotated loop: conv1' fragments of the previous chunk's slice
   float ws_l = p.ws3[l31], b_l = p.b3[l31];                      // this lane's conv3 channel of chunk 0 (MFMA layout: col = lane & 31)
   constexpr int NCONST = 2;
   f16x8 ah[CS][2], al[CS][2];                                    // phase-2 A fragments: the wave's own 32 rows of T2, [slice][k-half]
@@ -446,8 +434,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
     for (int sl = 0; sl < CS; ++sl)
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        ah[sl][s] = *reinterpret_cast<const f16x8*>(a2base + sl * BMT * ROWB + offH[s]);
-        al[sl][s] = *reinterpret_cast<const f16x8*>(a2base + sl * BMT * ROWB + offL[s]);
+        frag_pair(a2base + sl * BMT * ROWB, s, ah[sl][s], al[sl][s]);
       }
   };
   if constexpr (DIRECT) {
@@ -460,7 +447,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
     // chunk 0's filters first: their L2 round trip runs under the fragments' HBM round trip (one wait for both)
     asm volatile("" ::: "memory");
     dma_w3(0, 0);
-    if constexpr (W1DB && !ROT) dma_w1(0, 0);
+    if constexpr (W1DB) dma_w1(0, 0);
     asm volatile("" ::: "memory");
     const long m = pix(wave * 32 + l31);
     unsigned oa = 0xFFFFFFFFu, ob = 0xFFFFFFFFu;
@@ -504,7 +491,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
   asm volatile("" ::: "memory");
   if constexpr (!DIRECT) {
     dma_w3(0, 0);
-    if constexpr (W1DB && !ROT) dma_w1(0, 0);
+    if constexpr (W1DB) dma_w1(0, 0);
   }
   asm volatile("" ::: "memory");
   if (nch > 0) load_res(0);
@@ -543,8 +530,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
       for (int q = 0; q < BG; ++q)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          bh[buf][q][s] = *reinterpret_cast<const f16x8*>(b2base + (g * BG + q) * 4096 + offH[s]);
-          bl[buf][q][s] = *reinterpret_cast<const f16x8*>(b2base + (g * BG + q) * 4096 + offL[s]);
+          frag_pair(b2base + (g * BG + q) * 4096, s, bh[buf][q][s], bl[buf][q][s]);
         }
     };
     read_b2(0, 0);
@@ -557,67 +543,25 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int t = 0; t < TN3; ++t) {
-          dh[s][t] = *reinterpret_cast<const f16x8*>(w1b + (t * 32 + l31) * ROWB + offH[s]);
-          dl[s][t] = *reinterpret_cast<const f16x8*>(w1b + (t * 32 + l31) * ROWB + offL[s]);
+          frag_pair(w1b + (t * 32 + l31) * ROWB, s, dh[s][t], dl[s][t]);
         }
       __builtin_amdgcn_sched_barrier(0);
     }
     f32x16 acc2;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc2[e] = 0.f;
-    // rotated loop: phase 3 of chunk j - 1 rides between the phase-2 MFMAs.  Its conv1' fragments live in two register sets
-    // X, Y of TN3: k-half 0 needs dh0 (terms 0, 2) and dl0 (term 1), k-half 1 dh1 and dl1; X = dh0 -> dl1, Y = dl0 -> dh1,
-    // each reloaded right behind the last MFMA that takes its old contents, TN3 MFMAs before its next use.
-    const bool prev = ROT && j > 0;
-    const char* w1p = lds + W1B_OFF + ((j + 1) & 1) * (CN * ROWB) + l31 * ROWB;     // conv1' slice j - 1
-    auto p3_read = [&](f16x8 (&dst)[ROT ? TN3 : 1], int off) {
-#pragma unroll
-      for (int t = 0; t < (ROT ? TN3 : 0); ++t) dst[t] = *reinterpret_cast<const f16x8*>(w1p + t * 32 * ROWB + off);
-    };
-    if constexpr (ROT) {
-      if (prev) {
-        p3_read(wx, offH[0]);
-        p3_read(wy, offL[0]);
-      }
-    }
-    auto p3_step = [&](auto mc) {                                  // MFMA m3 of phase 3 (chunk j - 1), term-major inside a k-half
-      constexpr int m3 = decltype(mc)::value;
-      constexpr int s3 = m3 / (3 * TN3), term = (m3 % (3 * TN3)) / TN3, t = m3 % TN3;
-      if constexpr (m3 == 2 * TN3) p3_read(wy, offH[1]);           // dl0 is dead: Y <- dh1
-      if constexpr (m3 == 3 * TN3) p3_read(wx, offL[1]);           // dh0 is dead: X <- dl1
-      if constexpr (s3 == 0) {
-        if constexpr (term == 0) acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pcl[0], wx[t], acc3[t], 0, 0, 0);
-        else if constexpr (term == 1) acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pch[0], wy[t], acc3[t], 0, 0, 0);
-        else acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pch[0], wx[t], acc3[t], 0, 0, 0);
-      } else {
-        if constexpr (term == 0) acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pcl[1], wy[t], acc3[t], 0, 0, 0);
-        else if constexpr (term == 1) acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pch[1], wx[t], acc3[t], 0, 0, 0);
-        else acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pch[1], wy[t], acc3[t], 0, 0, 0);
-      }
-    };
     fcp_static_for<0, CS / BG>([&](auto gc) {
       constexpr int g = decltype(gc)::value;
       if constexpr (g + 1 < CS / BG) read_b2((g + 1) & 1, g + 1);  // next group's fragments under this group's MFMAs
       fcp_static_for<0, 2 * BG>([&](auto tc) {
         constexpr int q = decltype(tc)::value / 2, s = decltype(tc)::value % 2, sl = g * BG + q, trip = 2 * sl + s;
-        fcp_static_for<0, 3>([&](auto ec) {
-          constexpr int term = decltype(ec)::value;
-          if constexpr (term == 0) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sl][s], bh[g & 1][q][s], acc2, 0, 0, 0);
-          else if constexpr (term == 1) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sl][s], bl[g & 1][q][s], acc2, 0, 0, 0);
-          else acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sl][s], bh[g & 1][q][s], acc2, 0, 0, 0);
-          if constexpr (ROT) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (prev) fcp_static_for<0, PQ>([&](auto pc) { p3_step(std::integral_constant<int, (3 * trip + term) * PQ + decltype(pc)::value>{}); });
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        });
+        mfma3(acc2, ah[sl][s], al[sl][s], bh[g & 1][q][s], bl[g & 1][q][s]);
         constexpr int PER = (NDMA + 2 * CS - 1) / (2 * CS);       // DMA instructions per MFMA triple (1, or 2 where CN > 32 CS)
         if constexpr (SPREAD && trip * PER < NDMA) {
           __builtin_amdgcn_sched_barrier(0);
-          // rotated loop: the conv1' pieces fetch slice j (consumed by chunk j + 1's phase 3 ride): also in the last chunk
-          if (more || (ROT && trip * PER >= PW3)) dma_one(std::integral_constant<int, trip * PER>{}, j + 1, (j + 1) & 1);
+          if (more) dma_one(std::integral_constant<int, trip * PER>{}, j + 1, (j + 1) & 1);
           if constexpr (PER == 2 && trip * PER + 1 < NDMA) {
-            if (more || (ROT && trip * PER + 1 >= PW3)) dma_one(std::integral_constant<int, trip * PER + 1>{}, j + 1, (j + 1) & 1);
+            if (more) dma_one(std::integral_constant<int, trip * PER + 1>{}, j + 1, (j + 1) & 1);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -689,19 +633,6 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
     };
     if constexpr (!HAS_P3) {
       store_out();                                                 // expand form: the chunk ends with its stores
-    } else if constexpr (ROT) {
-      // rotated loop: T3 of this chunk goes to registers now (the tile is overwritten by the next chunk's staging); its
-      // phase 3 rides in the next chunk's phase 2.  The chunk's `out` stores go out behind the fragment reads.
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        pch[s] = *reinterpret_cast<const f16x8*>(a3base + offH[s]);
-        pcl[s] = *reinterpret_cast<const f16x8*>(a3base + offL[s]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("" ::: "memory");
-      store_out();
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
     } else {
     // ---- phase 3: acc3 += T3 . W1'[:, slice j]^T, one k-half at a time (fragment registers: CN = 128 has none to spare);
     //      this chunk's `out` stores go out behind the first k-half's fragment reads
@@ -709,13 +640,11 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       f16x8 ch, cl;
-      ch = *reinterpret_cast<const f16x8*>(a3base + offH[s]);
-      cl = *reinterpret_cast<const f16x8*>(a3base + offL[s]);
+      frag_pair(a3base, s, ch, cl);
       if constexpr (!W1PRE) {
 #pragma unroll
         for (int t = 0; t < TN3; ++t) {
-          dh[s][t] = *reinterpret_cast<const f16x8*>(w1base + (t * 32 + l31) * ROWB + offH[s]);
-          dl[s][t] = *reinterpret_cast<const f16x8*>(w1base + (t * 32 + l31) * ROWB + offL[s]);
+          frag_pair(w1base + (t * 32 + l31) * ROWB, s, dh[s][t], dl[s][t]);
         }
       }
       if (s == 0) {
@@ -726,11 +655,7 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
-      for (int t = 0; t < TN3; ++t) {
-        acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, dh[s][t], acc3[t], 0, 0, 0);
-        acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, dl[s][t], acc3[t], 0, 0, 0);
-        acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, dh[s][t], acc3[t], 0, 0, 0);
-      }
+      for (int t = 0; t < TN3; ++t) mfma3(acc3[t], ch, cl, dh[s][t], dl[s][t]);
     }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -738,27 +663,6 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
-  if constexpr (ROT) {
-    // phase 3 of the last chunk: its conv1' slice was fetched during the last chunk and has landed (wait + barrier above)
-    if (nch > 0) {
-      const char* w1l = lds + W1B_OFF + ((NCH - 1) & 1) * (CN * ROWB) + l31 * ROWB;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int t = 0; t < TN3; ++t) {
-          wx[t] = *reinterpret_cast<const f16x8*>(w1l + t * 32 * ROWB + offH[s]);
-          wy[t] = *reinterpret_cast<const f16x8*>(w1l + t * 32 * ROWB + offL[s]);
-        }
-#pragma unroll
-        for (int t = 0; t < TN3; ++t) {
-          acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pcl[s], wx[t], acc3[t], 0, 0, 0);
-          acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pch[s], wy[t], acc3[t], 0, 0, 0);
-          acc3[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pch[s], wx[t], acc3[t], 0, 0, 0);
-        }
-      }
-    }
-    __syncthreads();                                               // the conv1' buffers are reused by the fp32 tile below
-  }
 
   // ================================================================================ conv1' epilogue -> t1' (HBM)
   float* Cs = smem;                                              // fp32 tile [BMT][64], one 64-column half at a time
@@ -784,22 +688,10 @@ __global__ void __launch_bounds__(2 * BMT, wgs_per_cu(CW, CN, HAS_C2, direct_for
     for (int g = 0; g < 4; ++g) {
       const int row = (tid >> 3) + LR * g;
       const long m = pix(row);
-      const f32x4 a = *reinterpret_cast<const f32x4*>(Cs + row * 64 + ccol);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(Cs + row * 64 + ccol + 4);
-      float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = conv_value_relu(v[e], ws8[e], b8[e]);
       if (m < 0) continue;
-      u32x4_t hi, lo;                                              // pack8 / store8 (fcp_conv_common.h) for split32, spelled out: through
-      split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);   // them the compiler orders this kernel's code differently
-      char* ob = reinterpret_cast<char*>(p.t1n) + m * p.t1n_ld * 4 + split_chan_off(co);
-      if (p.nt_store) {
-        __builtin_nontemporal_store(hi, reinterpret_cast<u32x4_t*>(ob));
-        __builtin_nontemporal_store(lo, reinterpret_cast<u32x4_t*>(ob + 64));
-      } else {
-        *reinterpret_cast<u32x4_t*>(ob) = hi;
-        *reinterpret_cast<u32x4_t*>(ob + 64) = lo;
-      }
+      float v[8];
+      row_values8(Cs + row * 64 + ccol, ws8, b8, v);
+      pack_store8(p.t1n, m, p.t1n_ld, co, 1, p.nt_store, v);
     }
     __syncthreads();
   }
@@ -815,6 +707,27 @@ int launch(const ChainK& k, hipStream_t s) {
   return 0;
 }
 
+// The supported forms, one row each: what the descriptor must say -> the kernel that runs it.  c: all of conv3's input
+// channels, cb of them from the second source; cn = 0: no conv1' (engine.chain_supported lists the same rows for callers)
+struct ChainForm {
+  bool has_c2;
+  int c, cb, nout;
+  bool residual;
+  int cn;
+  int (*launch)(const ChainK&, hipStream_t);
+};
+const ChainForm FORMS[] = {
+    // conv2, c, cb, nout, residual, cn
+    {true, 64, 0, 256, true, 64, launch<64, 64, 256, true, true>},
+    {true, 64, 0, 256, true, 128, launch<128, 64, 256, true, true>},
+    {false, 128, 0, 512, true, 128, launch<128, 128, 512, false, true>},
+    {false, 128, 0, 256, false, 64, launch<64, 128, 256, false, false>},
+    {false, 256, 0, 1024, true, 256, launch<256, 256, 1024, false, true>},
+    {false, 128, 0, 512, true, 256, launch<256, 128, 512, false, true>},          // CN = 256: 128 accumulator registers, one wave per SIMD only
+    {false, 384, 256, 512, false, 128, launch<128, 384, 512, false, false, 256>},   // two-source pair: [conv2 out 128 | x(::2, ::2) 256] -> 512 -> 128
+    {false, 256, 0, 1024, true, 0, launch<0, 256, 1024, false, true>},              // expand form: conv3 256 -> 1024 + identity, no conv1'
+};
+
 }  // namespace
 
 extern "C" int fcp_bottleneck_chain_f16x3(const fcp_chain_desc* d, fcp_stream_t stream) {
@@ -824,18 +737,14 @@ extern "C" int fcp_bottleneck_chain_f16x3(const fcp_chain_desc* d, fcp_stream_t 
               "chain: null pointer (every convolution carries folded-BN bias and filter scales)");
   const bool has_c2 = d->w2 != nullptr;
   FCP_REQUIRE(!has_c2 || (d->ws2 && d->b2), "chain: conv2 needs its scales and bias");
-  // supported shapes: (c 64, conv2, nout 256, residual, cn 64 | 128)   (c 128, no conv2, nout 512, residual, cn 128)
-  //                   (c 128, no conv2, nout 256, no residual, cn 64)   (c 256, no conv2, nout 1024, residual, cn 256)
-  //                   (c 128, no conv2, nout 512, residual, cn 256)
-  const int variant = (has_c2 && d->c == 64 && d->nout == 256 && d->res && (d->cn == 64 || d->cn == 128)) ? (d->cn == 64 ? 1 : 2)
-                    : (!has_c2 && d->c == 128 && d->nout == 512 && d->res && d->cn == 128) ? 3
-                    : (!has_c2 && d->c == 128 && d->nout == 256 && !d->res && d->cn == 64) ? 4
-                    : (!has_c2 && d->c == 256 && d->nout == 1024 && d->res && d->cn == 256) ? 5
-                    : (!has_c2 && d->c == 128 && d->nout == 512 && d->res && d->cn == 256) ? 6
-                    : (!has_c2 && d->t1b && d->c == 384 && d->cb == 256 && d->nout == 512 && !d->res && d->cn == 128) ? 7
-                    : (!has_c2 && !d->t1b && d->c == 256 && d->nout == 1024 && d->res && d->cn == 0 && !d->w1n) ? 8 : 0;
-  FCP_REQUIRE(variant == 7 || !d->t1b, "chain: a second source (t1b) exists for the two-source pair form only (c 384 = 128 + 256, nout 512, cn 128)");
-  FCP_REQUIRE(variant != 0, "chain: unsupported shape (c %d, conv2 %d, nout %d, residual %d, cn %d)", d->c, (int)has_c2, d->nout,
+  const int cb = d->t1b ? d->cb : 0;                            // channels of the second source
+  const ChainForm* form = nullptr;
+  for (const ChainForm& f : FORMS)
+    if (f.has_c2 == has_c2 && f.c == d->c && f.cb == cb && f.nout == d->nout && f.residual == (d->res != nullptr) && f.cn == d->cn &&
+        (f.cn != 0) == has_p3)
+      form = &f;
+  FCP_REQUIRE((form && form->cb) || !d->t1b, "chain: a second source (t1b) exists for the two-source pair form only (c 384 = 128 + 256, nout 512, cn 128)");
+  FCP_REQUIRE(form != nullptr, "chain: unsupported shape (c %d, conv2 %d, nout %d, residual %d, cn %d)", d->c, (int)has_c2, d->nout,
               d->res != nullptr, d->cn);
   FCP_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0, "chain: bad sizes");
   const long M = (long)d->n * d->h * d->w;
@@ -843,7 +752,7 @@ extern "C" int fcp_bottleneck_chain_f16x3(const fcp_chain_desc* d, fcp_stream_t 
   auto aligned = [](const void* p, int ld) { return ((uintptr_t)p & 127) == 0 && ld % 32 == 0; };
   FCP_REQUIRE(aligned(d->t1, d->t1_ld) && (!d->res || aligned(d->res, d->res_ld)) && aligned(d->out, d->out_ld) && (!has_p3 || aligned(d->t1n, d->t1n_ld)),
               "chain: tensors are split32 views: 128-byte aligned, channel stride a multiple of 32");
-  FCP_REQUIRE(d->t1_ld >= d->c - (d->t1b ? d->cb : 0) && (!d->res || d->res_ld >= d->nout) && d->out_ld >= d->nout && (!has_p3 || d->t1n_ld >= d->cn), "chain: channel strides too small");
+  FCP_REQUIRE(d->t1_ld >= d->c - cb && (!d->res || d->res_ld >= d->nout) && d->out_ld >= d->nout && (!has_p3 || d->t1n_ld >= d->cn), "chain: channel strides too small");
   const unsigned long t1_bytes = (unsigned long)M * d->t1_ld * 4ul;
   FCP_REQUIRE(t1_bytes < 0xFFFFFFF0ul, "chain: t1 must be below 4 GiB");
   ChainK k;
@@ -872,14 +781,5 @@ extern "C" int fcp_bottleneck_chain_f16x3(const fcp_chain_desc* d, fcp_stream_t 
   FCP_REQUIRE(!k.out_even || has_c2, "chain: FCP_CHAIN_OUT_EVEN_ONLY needs a conv2 form");
   hipStream_t s = (hipStream_t)stream;
   // d->tile_m is a hint this library ignores: the conv2 forms run on 8 x 16 patches, the others on 128-pixel tiles
-  switch (variant) {
-    case 1: return launch<64, 64, 256, true, true>(k, s);
-    case 2: return launch<128, 64, 256, true, true>(k, s);
-    case 3: return launch<128, 128, 512, false, true>(k, s);
-    case 5: return launch<256, 256, 1024, false, true>(k, s);
-    case 6: return launch<256, 128, 512, false, true>(k, s);     // CN = 256: 128 accumulator registers, one wave per SIMD only
-    case 7: return launch<128, 384, 512, false, false, 256>(k, s);   // [conv2 out 128 | x(::2, ::2) 256] -> 512 -> 128
-    case 8: return launch<0, 256, 1024, false, true>(k, s);          // expand form: conv3 256 -> 1024 + identity, no conv1'
-    default: return launch<64, 128, 256, false, false>(k, s);
-  }
+  return form->launch(k, s);
 }

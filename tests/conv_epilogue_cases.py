@@ -140,6 +140,11 @@ def cases():
     out.append(("chain_pair_128_512", "chain", dict(form="pair", n=1, h=16, w=16)))
     out.append(("chain_two_source", "chain", dict(form="two_source", n=1, h=7, w=5)))
     out.append(("chain_expand_256_1024", "chain", dict(form="expand", n=1, h=7, w=5)))
+    # 153 pixels: one whole and one ragged 128-pixel tile; as 8 x 16 patches, 2 x 2 of them, ragged on both axes
+    out.append(("chain_pair_128_512_256", "chain", dict(form="pair", c=128, nout=512, cn=256, n=1, h=9, w=17)))
+    out.append(("chain_pair_256_1024_256", "chain", dict(form="pair", c=256, nout=1024, cn=256, n=1, h=9, w=17)))
+    out.append(("chain_pair_128_256_64_nores", "chain", dict(form="pair", c=128, nout=256, cn=64, res=False, n=1, h=9, w=17)))
+    out.append(("chain_conv2_out_even", "chain", dict(form="conv2", cn=128, out_even=True, n=1, h=9, w=17)))
     out.append(("stem_1x9x11", "stem", dict(n=1, h=9, w=11)))
     out.append(("stem_2x75x131", "stem", dict(n=2, h=75, w=131)))
     return out
@@ -208,11 +213,17 @@ def _chain(E, torch, device, case_id, s):
     if form == "conv2":
         pc2, pc3, pc1 = pack(64, 64, 3), pack(256, 64, 1), pack(s["cn"], 256, 1)
         t1, res = _act(E, torch, device, rng, n, h, w, 64, 1), _act(E, torch, device, rng, n, h, w, 256, 1)
-        run = lambda tm: E.bottleneck_chain(pc2, pc3, pc1, t1, res, tile_m=tm)
+        if s.get("out_even"):                                         # `out` over a sentinel: the pixels that are not stored keep it
+            run = lambda tm: E.bottleneck_chain(pc2, pc3, pc1, t1, res, E.Act(torch.full((n, h, w, 256), -7.0, device=device), fmt=1),
+                                                E.Act.empty(n, h, w, s["cn"], device, 1), tile_m=tm, out_even_only=True)
+        else:
+            run = lambda tm: E.bottleneck_chain(pc2, pc3, pc1, t1, res, tile_m=tm)
         tiles = (0, 128, 16, 256, 32)                                 # tile_m is a hint the library may ignore: same bits
     elif form == "pair":
-        pc3, pc1 = pack(512, 128, 1), pack(128, 512, 1)
-        t1, res = _act(E, torch, device, rng, n, h, w, 128, 1), _act(E, torch, device, rng, n, h, w, 512, 1)
+        c, nout, cn = s.get("c", 128), s.get("nout", 512), s.get("cn", 128)
+        pc3, pc1 = pack(nout, c, 1), pack(cn, nout, 1)
+        t1 = _act(E, torch, device, rng, n, h, w, c, 1)
+        res = _act(E, torch, device, rng, n, h, w, nout, 1) if s.get("res", True) else None
         run = lambda tm: E.bottleneck_chain(None, pc3, pc1, t1, res, tile_m=tm)
         tiles = (0,)
     elif form == "two_source":

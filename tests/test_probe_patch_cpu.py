@@ -22,6 +22,13 @@ def test_product_kernels_carry_no_experiment_switches():
                 if re.search(r"FCP_\w*(ABLATE|PROBE|_ROT\b|REG_EPI|STAGES3|BURST\)|SPREAD\)|PROFILING|STEM_PW|WIDE2_BT)", line) \
                         and line.lstrip().startswith("#"):
                     bad.append(f"{name}:{i}: {line.strip()}")
+    # ... and none spelt as a constant either: `constexpr bool ROT = false;` kept a whole retired loop behind `if constexpr`
+    for folder, _, names in os.walk(csrc):
+        for name in names:
+            if name.endswith((".hip", ".h", ".cpp")):
+                for i, line in enumerate(open(os.path.join(folder, name)), 1):
+                    if re.search(r"constexpr bool \w+ = (false|true);", line):
+                        bad.append(f"{name}:{i}: {line.strip()}")
     assert not bad, bad
 
 

@@ -66,3 +66,19 @@ if True:
     t1_ = timeit(lambda: E.conv(pc1, out, t1n, act_slope=0.0))
     tc = timeit(lambda: E.bottleneck_chain(None, pc3, pc1, t, xr, out, t1n)) if E.chain_supported(None, pc3, pc1) else float("nan")
     print(f"pair {hh}x{hh} 256->{nout}->{cn} res=True: {tc:7.1f} us | separate {t3:6.1f} + {t1_:6.1f} = {t3 + t1_:7.1f} us", flush=True)
+    # ---- expand form: the same conv3 + identity alone, the next conv1 an ordinary launch
+    te = timeit(lambda: E.bottleneck_chain(None, pc3, None, t, xr, out))
+    print(f"expand {hh}x{hh} 256->{nout} res=True: {te:7.1f} us | separate {t3:6.1f} us", flush=True)
+
+# ---- two-source pair (layer2.0: [conv2 out 128 @ 80x80 | x 256 @ 160x160, every second pixel] -> 512 -> 128)
+if True:
+    hh, nout, cn = 80, 512, 128
+    pc3 = mk(nout, 128 + 256, 1)
+    pc1 = mk(cn, nout, 1)
+    t = E.f32_to_split32(E.Act(torch.randn(b, hh, hh, 128, device=dev).relu()))
+    tb = E.f32_to_split32(E.Act(torch.randn(b, 2 * hh, 2 * hh, 256, device=dev).relu()))
+    out, t1n = E.Act.empty(b, hh, hh, nout, dev, 1), E.Act.empty(b, hh, hh, cn, dev, 1)
+    tc = timeit(lambda: E.bottleneck_chain(None, pc3, pc1, t, None, out, t1n, t1b=tb, t1b_stride=2))
+    t3 = timeit(lambda: E.conv(pc3, t, out, act_slope=0.0, x2=tb, x2_stride=2))
+    t1_ = timeit(lambda: E.conv(pc1, out, t1n, act_slope=0.0))
+    print(f"two-source pair {hh}x{hh} 128+256->{nout}->{cn}: {tc:7.1f} us | separate {t3:6.1f} + {t1_:6.1f} = {t3 + t1_:7.1f} us", flush=True)
