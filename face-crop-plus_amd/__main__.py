@@ -88,6 +88,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="give the soft edge of the matte the subject's own colour in place of its mix with the old "
                         "background: sigma in output pixels, 0.5..16, about the width of the soft edge or more (with "
                         "--background, fill or 'transparent'); by default the edge keeps the crop's colour")
+    p.add_argument("-dn", "--denoise", type=float, default=argparse.SUPPRESS,
+                   help="remove sensor noise from the crops: filter strength in gray levels, 1..32 (8 suits a small face "
+                        "from a high-ISO photo), of a non-local-means filter; by default the crops keep their noise")
     p.add_argument("-cl", "--clahe", type=float, default=argparse.SUPPRESS,
                    help="equalise the contrast of the crops: clip limit (> 0, usually 2.0) of a contrast-limited adaptive "
                         "histogram equalisation of their luma; by default the crops keep their contrast")

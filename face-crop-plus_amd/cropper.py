@@ -17,6 +17,7 @@ import torch
 
 from . import align, trace
 from . import clahe as equalizing
+from . import denoise as denoising
 from . import matte as matting
 from ._io_codec import _ENCODER_KW, JpegSettings, check_jpeg_settings, write_bytes
 from .batch import batch_geometry, build_batch, upload_sources
@@ -70,6 +71,7 @@ class Cropper:
         fill_holes: int | None = None,
         decontaminate: float | None = None,
         edge_shift: int | None = None,
+        denoise: float | None = None,
         clahe: float | None = None,
         clahe_grid: int | None = None,
         interpolation: str = "linear",
@@ -180,6 +182,18 @@ class Cropper:
         ``background="transparent"`` and with a fill ``background=(R, G, B)`` (``matte.cutout``); with
         ``background_blur`` or without a background it raises ValueError.  None (the default) launches nothing new: a
         fill composites the crop's colour, byte for byte as before.
+        ``denoise``: remove sensor noise from every crop — the filter strength H, in gray levels (a finite number 1..32; 8
+        suits the grain of a small face enlarged from a high-ISO photo), of a non-local-means filter: every pixel becomes
+        the weighted mean of the 21 x 21 pixels around it, each weighted by ``exp(-d / (49 H^2))`` of the squared
+        difference d of the 7 x 7 gray patches around the two (the window sizes are the defaults of
+        ``cv2.fastNlMeansDenoising``), stated in integers and held byte for byte to a numpy reference
+        (``denoise.denoise``).  The weights come from the gray alone and the three channels
+        are averaged with them: pure chroma noise is reduced less than luma noise.  It runs after ``min_sharpness`` and
+        the parse, which both see the original crop (calibrated thresholds, label maps, attribute groups and mask files
+        are the same with and without it), and immediately before ``clahe``, so that everything after it (``clahe``, the
+        guide of ``refine``, both background modes, both encoders) sees the denoised crop.  It needs aligned crops like
+        ``min_sharpness`` and an ``output_size`` of at least 14 x 14.  None (the default) launches nothing.
+        ``Cropper.remove_noise`` applies it to crops one already has.
         ``clahe``: equalise the contrast of every crop — the clip limit (finite, > 0; 2.0 is the usual value) of a
         contrast-limited adaptive histogram equalisation of the luma on a ``clahe_grid`` x ``clahe_grid`` tiling (1..16;
         None: 8), ``cv2.createCLAHE(clahe, (grid, grid)).apply(Y)`` between ``cv2.cvtColor(crop, COLOR_RGB2YCrCb)`` and
@@ -276,6 +290,12 @@ class Cropper:
                                  "landmarks=None (no alignment), where the faces are the images themselves")
             size = (output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size)
             self.clahe_grid = equalizing.check_grid(clahe_grid, size)
+        self.denoise = denoising.check_denoise(denoise)
+        if self.denoise is not None:
+            if det_threshold is None and landmarks is None:
+                raise ValueError("denoise needs aligned crops: it cannot be combined with det_threshold=None and "
+                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            denoising.check_size((output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size))
         self.crop_source = crop_source
         self.interpolation = interpolation
         self.output_size = output_size
@@ -490,6 +510,19 @@ class Cropper:
             return np.zeros(crops.shape, np.uint8)
         with torch.cuda.device(self.device):
             return equalizing.clahe(torch.from_numpy(crops).to(self.device), self.clahe, self.clahe_grid).cpu().numpy()
+
+    def remove_noise(self, crops: np.ndarray) -> np.ndarray:
+        """What ``denoise`` does, for crops one already has: (F,H,W,3) uint8 RGB -> the denoised crops (F,H,W,3) uint8,
+        at this Cropper's filter strength (``denoise.denoise``)."""
+        if self.denoise is None:
+            raise ValueError("Cropper.remove_noise needs a Cropper with denoise=...")
+        crops = np.ascontiguousarray(crops)
+        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
+            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
+        if crops.shape[0] == 0:
+            return np.zeros(crops.shape, np.uint8)
+        with torch.cuda.device(self.device):
+            return denoising.denoise(torch.from_numpy(crops).to(self.device), self.denoise).cpu().numpy()
 
     def encode_jpeg(self, crops: np.ndarray) -> list:
         """What ``encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F JPEG files as
@@ -770,15 +803,21 @@ class Cropper:
                         groups = tuple(groups)
                     else:
                         groups = self.par_model.predict(faces_dev)
-            if len(indices) > 0 and isinstance(faces_dev, torch.Tensor) and (self.clahe is not None or labels is not None):
-                # after the parse, which saw the original crop: first the contrast, over the whole crop, then the fill
+            denoise = getattr(self, "denoise", None)           # absent on a Cropper made with __new__
+            if len(indices) > 0 and isinstance(faces_dev, torch.Tensor) and (denoise is not None or self.clahe is not None
+                                                                             or labels is not None):
+                # after the parse, which saw the original crop: first the noise, then the contrast, over the whole crop,
+                # then the fill
+                if denoise is not None:
+                    with trace.range("fcp:denoise"):
+                        faces_dev = denoising.denoise(faces_dev, denoise)
                 if self.clahe is not None:
                     with trace.range("fcp:clahe"):
                         faces_dev = equalizing.clahe(faces_dev, self.clahe, self.clahe_grid)
                 if labels is not None:
                     with trace.range("fcp:matte"):
                         faces_dev, _ = self._matte_device(faces_dev, labels)
-                # the host copy, if the host encoder needs one, is the equalised / matted crop as well
+                # the host copy, if the host encoder needs one, is the denoised / equalised / matted crop as well
                 faces = None if self._encodes_on_device() else faces_dev.cpu().numpy()
             if self._encodes_on_device() and isinstance(faces_dev, torch.Tensor):
                 # aligned crops (and their masks): same size, on the device.  Faces and mask rows become lists that hold

@@ -56,6 +56,7 @@
 #include "fcp_common.h"
 #include "fcp_crop_checks.h"
 #include "fcp_feather.h"
+#include "fcp_gray.h"
 #include "fcp_hip.h"
 
 namespace {
@@ -73,10 +74,7 @@ constexpr int kMaxRadius = 16;
 constexpr int kMaxEps = 4096;
 constexpr int kSumPitch = kTileW + 1;   // 8-byte row sums of a staged row
 
-// fcp_sharpness.hip's gray_of, restated (that kernel's instruction stream is left alone)
-__device__ __forceinline__ uint32_t gray_of(uint32_t r, uint32_t g, uint32_t b) {
-  return (9798u * r + 19235u * g + 3735u * b + 16384u) >> 15;
-}
+using fcp_gray::gray_of;                // the gray of min_sharpness (fcp_sharpness.hip states it itself)
 
 // u / n for u < 2^48 and 1 <= n < 2^16, as two unsigned 32-bit divisions
 __device__ __forceinline__ uint64_t div_small(uint64_t u, uint32_t n) {

@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout / mask_shift
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout / mask_shift / nlm_denoise
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -728,6 +728,24 @@ Tensor clahe(const Tensor& crops, int64_t grid, double clip_limit) {
   return out;
 }
 
+// Crops (f,h,w,3) uint8 with the noise removed by non-local means under the weight table lut (n,) uint16 and its shift
+// (fcp_nlm_denoise_u8).
+Tensor nlm_denoise(const Tensor& crops, const Tensor& lut, int64_t shift) {
+  dev(crops, "crops", at::kByte);
+  dev(lut, "lut", at::kUInt16);
+  FCP_DEVICE_GUARD(crops);
+  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
+  TORCH_CHECK(lut.dim() == 1 && lut.device() == crops.device(), "lut (n,) uint16 on the device of crops");
+  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2);
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX && lut.numel() <= INT_MAX, "crops (f,h,w,3), lut (n,): sizes past int");
+  TORCH_CHECK(shift >= INT_MIN && shift <= INT_MAX, "shift past int");
+  Tensor out = at::empty_like(crops);
+  ok(fcp_nlm_denoise_u8(crops.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, static_cast<const uint16_t*>(lut.const_data_ptr()),
+                        (int)lut.numel(), (int)shift, out.data_ptr<uint8_t>(), cur_stream()),
+     "fcp::nlm_denoise");
+  return out;
+}
+
 Tensor bicubic_down4_round(const Tensor& x4) {
   dev(x4, "x4", at::kFloat);
   FCP_DEVICE_GUARD(x4);
@@ -803,6 +821,7 @@ TORCH_LIBRARY(fcp, m) {
   m.def("feather_alpha(Tensor labels, int class_bits, int feather) -> Tensor");
   m.def("cutout(Tensor crops, Tensor alpha, int mode, int bg_r, int bg_g, int bg_b, int[] taps) -> Tensor");
   m.def("mask_shift(Tensor labels, int class_bits, int shift) -> Tensor");
+  m.def("nlm_denoise(Tensor crops, Tensor lut, int shift) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -842,6 +861,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("feather_alpha", &feather_alpha);
   m.impl("cutout", &cutout);
   m.impl("mask_shift", &mask_shift);
+  m.impl("nlm_denoise", &nlm_denoise);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

@@ -850,6 +850,33 @@ int fcp_mask_shift_u8(const uint8_t* labels, int f, int h, int w, uint32_t class
  * message, before any HIP call. */
 int fcp_clahe_u8(const uint8_t* crops, int f, int h, int w, int grid, double clip_limit, uint8_t* luts, uint8_t* out, fcp_stream_t stream);
 
+/* Non-local-means noise removal of crops (f,h,w,3) uint8 RGB, in integers
+ * (INTEGRATION.md 2p).  With P = 3 (a 7 x 7 patch), S = 10 (a 21 x 21 search
+ * window), ONE = 4096, every coordinate outside the crop reflected
+ * (BORDER_REFLECT_101), and the table lut[0 .. lut_len - 1] of uint16:
+ *   g        = (9798 R + 19235 G + 3735 B + 16384) >> 15
+ *   d(p,o)   = sum over t in [-P,P]^2 of (g(p + t) - g(p + o + t))^2, for
+ *              every offset o in [-S,S]^2
+ *   k        = d >> shift;  w(p,o) = min(lut[k], ONE) if k < lut_len, else 0
+ *   W        = sum over o of w(p,o)
+ *   out_c(p) = (sum over o of w(p,o) c(p + o) + (W >> 1)) / W for c = R, G,
+ *              B, floor division; W == 0 copies the pixel.
+ * The weights come from the gray alone; the three channels are averaged
+ * with them.  The clamp at ONE keeps W below 2^21 and the numerators below
+ * 2^29 for any table: unsigned 32-bit sums, which commute, so the bytes do
+ * not depend on the tiling or the order of the offsets and are the same
+ * from run to run.  lut is device memory, 2-byte aligned
+ * (denoise.weight_lut builds the table of a filter strength on the host).
+ * One launch on `stream`, no workspace, no float and no atomics.  crops and
+ * out may start at any byte and must not overlap (out == crops included: a
+ * pixel reads its window); nothing outside out is written.
+ * f == 0 is a no-op; f < 0 or > 65535, h or w below P + S + 1 = 14 or above
+ * 8192, a lut_len outside 1..4096, a shift outside 0..10, or (f > 0) a null
+ * crops / lut / out, a misaligned lut or overlapping arrays fail with a
+ * "nlm_denoise:" message, before any HIP call. */
+int fcp_nlm_denoise_u8(const uint8_t* crops, int f, int h, int w, const uint16_t* lut, int lut_len, int shift, uint8_t* out,
+                       fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */
