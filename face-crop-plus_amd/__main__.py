@@ -96,6 +96,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "histogram equalisation of their luma; by default the crops keep their contrast")
     p.add_argument("-cg", "--clahe-grid", type=int, default=argparse.SUPPRESS,
                    help="tiles per side of the equalisation, 1..16 (with --clahe; default 8)")
+    p.add_argument("-sh", "--sharpen", type=float, default=argparse.SUPPRESS,
+                   help="sharpen the crops: amount, 0.05..4 (1.0 adds the whole difference), of an unsharp mask of their "
+                        "gray, added to the three channels alike; by default the crops keep their softness")
+    p.add_argument("-shs", "--sharpen-sigma", type=float, default=argparse.SUPPRESS,
+                   help="sigma of the unsharp mask's blur in output pixels, 0.5..16 (with --sharpen; default 1.5)")
+    p.add_argument("-sht", "--sharpen-threshold", type=int, default=argparse.SUPPRESS,
+                   help="differences of up to this many gray levels, 0..255, are left alone (with --sharpen; default 0)")
     p.add_argument("-jq", "--jpeg-quality", type=int, default=argparse.SUPPRESS,
                    help="quality of the JPEG files written, 1..100 (default 95, cv2.imwrite's)")
     p.add_argument("-jss", "--jpeg-subsampling", type=str, default=argparse.SUPPRESS, choices=("4:4:4", "4:2:2", "4:2:0"),

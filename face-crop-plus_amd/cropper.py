@@ -19,6 +19,7 @@ from . import align, trace
 from . import clahe as equalizing
 from . import denoise as denoising
 from . import matte as matting
+from . import sharpen as sharpening
 from ._io_codec import _ENCODER_KW, JpegSettings, check_jpeg_settings, write_bytes
 from .batch import batch_geometry, build_batch, upload_sources
 from .utils import get_ldm_slices, parse_landmarks_file, read_image, read_images, write_image
@@ -74,6 +75,9 @@ class Cropper:
         denoise: float | None = None,
         clahe: float | None = None,
         clahe_grid: int | None = None,
+        sharpen: float | None = None,
+        sharpen_sigma: float | None = None,
+        sharpen_threshold: int | None = None,
         interpolation: str = "linear",
         min_sharpness: float | None = None,
     ):
@@ -202,6 +206,18 @@ class Cropper:
         stays exact) and the encoder; the histograms are over the whole crop and mask files are unchanged.  It needs
         aligned crops like ``min_sharpness`` and an ``output_size`` of at least ``2 * clahe_grid`` on both sides;
         ``clahe_grid`` without ``clahe`` raises ValueError.  None (the default) launches nothing.
+        ``sharpen``: sharpen every crop — the amount A (a finite number 0.05..4; 1.0 adds the whole difference) of an
+        unsharp mask of the gray: the gray's difference from its own Gaussian blur of ``sharpen_sigma`` output pixels
+        (0.5..16, the range and the taps of ``background_blur``; None: 1.5), less ``sharpen_threshold`` gray levels
+        (an int 0..255, a soft threshold that leaves noise and flat skin alone; None: 0), times A, is added to all three
+        channels alike, so there are no colour fringes; coordinates outside the crop are clamped to its edge.  It is stated
+        in integers and held byte for byte to a numpy reference (``sharpen.sharpen``).  It runs
+        after ``min_sharpness`` and the parse, which both see the original crop (calibrated thresholds, label maps,
+        attribute groups and mask files are the same with and without it), after ``denoise`` and ``clahe`` and before the
+        matte, so that the guide of ``refine``, both background modes and both encoders see the sharpened crop and a fill
+        colour stays exact.  It needs aligned crops like ``min_sharpness``; any ``output_size`` will do.
+        ``sharpen_sigma`` or ``sharpen_threshold`` without ``sharpen`` raises ValueError.  None (the default) launches
+        nothing.  ``Cropper.unsharp`` applies it to crops one already has.
         ``Cropper.equalize`` applies it to crops one already has.
         ``jpeg_quality`` (an int, 1..100; 95), ``jpeg_subsampling`` ("4:4:4", "4:2:2" or "4:2:0"; "4:2:0") and
         ``jpeg_optimize`` (per-file Huffman tables, Pillow's ``optimize=True``: smaller files, the same pixels; False):
@@ -296,6 +312,18 @@ class Cropper:
                 raise ValueError("denoise needs aligned crops: it cannot be combined with det_threshold=None and "
                                  "landmarks=None (no alignment), where the faces are the images themselves")
             denoising.check_size((output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size))
+        self.sharpen = sharpening.check_sharpen(sharpen)
+        if self.sharpen is None:
+            for name, value in (("sharpen_sigma", sharpen_sigma), ("sharpen_threshold", sharpen_threshold)):
+                if value is not None:
+                    raise ValueError(f"{name} needs sharpen: without it it would do nothing")
+            self.sharpen_sigma = self.sharpen_threshold = None
+        else:
+            if det_threshold is None and landmarks is None:
+                raise ValueError("sharpen needs aligned crops: it cannot be combined with det_threshold=None and "
+                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            self.sharpen_sigma = sharpening.check_sigma(sharpen_sigma)
+            self.sharpen_threshold = sharpening.check_threshold(sharpen_threshold)
         self.crop_source = crop_source
         self.interpolation = interpolation
         self.output_size = output_size
@@ -523,6 +551,20 @@ class Cropper:
             return np.zeros(crops.shape, np.uint8)
         with torch.cuda.device(self.device):
             return denoising.denoise(torch.from_numpy(crops).to(self.device), self.denoise).cpu().numpy()
+
+    def unsharp(self, crops: np.ndarray) -> np.ndarray:
+        """What ``sharpen`` does, for crops one already has: (F,H,W,3) uint8 RGB -> the sharpened crops (F,H,W,3) uint8,
+        at this Cropper's amount, sigma and threshold (``sharpen.sharpen``)."""
+        if getattr(self, "sharpen", None) is None:
+            raise ValueError("Cropper.unsharp needs a Cropper with sharpen=...")
+        crops = np.ascontiguousarray(crops)
+        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
+            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
+        if crops.shape[0] == 0:
+            return np.zeros(crops.shape, np.uint8)
+        with torch.cuda.device(self.device):
+            return sharpening.sharpen(torch.from_numpy(crops).to(self.device), self.sharpen, self.sharpen_sigma,
+                                      self.sharpen_threshold).cpu().numpy()
 
     def encode_jpeg(self, crops: np.ndarray) -> list:
         """What ``encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F JPEG files as
@@ -804,20 +846,24 @@ class Cropper:
                     else:
                         groups = self.par_model.predict(faces_dev)
             denoise = getattr(self, "denoise", None)           # absent on a Cropper made with __new__
+            sharpen = getattr(self, "sharpen", None)           # likewise
             if len(indices) > 0 and isinstance(faces_dev, torch.Tensor) and (denoise is not None or self.clahe is not None
-                                                                             or labels is not None):
-                # after the parse, which saw the original crop: first the noise, then the contrast, over the whole crop,
-                # then the fill
+                                                                             or sharpen is not None or labels is not None):
+                # after the parse, which saw the original crop: first the noise, then the contrast, then the edges, over
+                # the whole crop, then the fill
                 if denoise is not None:
                     with trace.range("fcp:denoise"):
                         faces_dev = denoising.denoise(faces_dev, denoise)
                 if self.clahe is not None:
                     with trace.range("fcp:clahe"):
                         faces_dev = equalizing.clahe(faces_dev, self.clahe, self.clahe_grid)
+                if sharpen is not None:
+                    with trace.range("fcp:sharpen"):
+                        faces_dev = sharpening.sharpen(faces_dev, sharpen, self.sharpen_sigma, self.sharpen_threshold)
                 if labels is not None:
                     with trace.range("fcp:matte"):
                         faces_dev, _ = self._matte_device(faces_dev, labels)
-                # the host copy, if the host encoder needs one, is the denoised / equalised / matted crop as well
+                # the host copy, if the host encoder needs one, is the denoised / equalised / sharpened / matted crop as well
                 faces = None if self._encodes_on_device() else faces_dev.cpu().numpy()
             if self._encodes_on_device() and isinstance(faces_dev, torch.Tensor):
                 # aligned crops (and their masks): same size, on the device.  Faces and mask rows become lists that hold

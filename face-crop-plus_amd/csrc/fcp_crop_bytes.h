@@ -31,6 +31,18 @@ __device__ __forceinline__ void load_rgb(const uint8_t* cp, int npx, uint32_t c[
   c[2] = (uint32_t)((((uint64_t)d3 << 32) | d2) >> sh);
 }
 
+// load_rgb with its four loads in flight together: a dword that holds no byte of the group is not skipped by a branch, which
+// makes every load wait for the one before it, but replaced by the group's last dword, read again.  The same contract.
+__device__ __forceinline__ void load_rgb_together(const uint8_t* cp, int npx, uint32_t c[3]) {
+  const int skew = (int)(reinterpret_cast<uintptr_t>(cp) & 3), last = (skew + 3 * npx - 1) >> 2;
+  const uint32_t* p = reinterpret_cast<const uint32_t*>(cp - skew);
+  const uint32_t d0 = p[0], d1 = p[min(1, last)], d2 = p[min(2, last)], d3 = p[min(3, last)];
+  const int sh = 8 * skew;
+  c[0] = (uint32_t)((((uint64_t)d1 << 32) | d0) >> sh);
+  c[1] = (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh);
+  c[2] = (uint32_t)((((uint64_t)d3 << 32) | d2) >> sh);
+}
+
 // The first 3 npx bytes of o[0..2] to op.
 __device__ __forceinline__ void store_rgb(uint8_t* op, int npx, const uint32_t o[3]) {
   if (npx == 4 && aligned4(op)) {

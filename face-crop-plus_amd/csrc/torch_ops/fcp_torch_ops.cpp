@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout / mask_shift / nlm_denoise
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout / mask_shift / nlm_denoise / unsharp
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -746,6 +746,28 @@ Tensor nlm_denoise(const Tensor& crops, const Tensor& lut, int64_t shift) {
   return out;
 }
 
+// Crops (f,h,w,3) uint8 sharpened by an unsharp mask of their gray with the taps t[0..radius] as integers, radius 1..48
+// (fcp_unsharp_u8).
+Tensor unsharp(const Tensor& crops, at::IntArrayRef taps, int64_t amount_q8, int64_t threshold) {
+  dev(crops, "crops", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  TORCH_CHECK(crops.dim() == 4 && crops.size(3) == 3, "crops (f,h,w,3) uint8");
+  const int64_t f = crops.size(0), h = crops.size(1), w = crops.size(2), radius = (int64_t)taps.size() - 1;
+  TORCH_CHECK(f <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "crops (f,h,w,3): sizes past int");
+  TORCH_CHECK(radius >= 1 && radius <= 48, "unsharp: taps must be t[0..radius] with radius 1..48 (got ", taps.size(), " taps)");
+  TORCH_CHECK(amount_q8 >= INT_MIN && amount_q8 <= INT_MAX && threshold >= INT_MIN && threshold <= INT_MAX, "amount_q8, threshold past int");
+  uint16_t t16[49] = {};
+  for (int64_t k = 0; k <= radius; ++k) {
+    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, "unsharp: tap ", k, " past 16 bits");
+    t16[k] = (uint16_t)taps[k];
+  }
+  Tensor out = at::empty_like(crops);
+  ok(fcp_unsharp_u8(crops.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, t16, (int)radius, (int)amount_q8, (int)threshold,
+                    out.data_ptr<uint8_t>(), cur_stream()),
+     "fcp::unsharp");
+  return out;
+}
+
 Tensor bicubic_down4_round(const Tensor& x4) {
   dev(x4, "x4", at::kFloat);
   FCP_DEVICE_GUARD(x4);
@@ -822,6 +844,7 @@ TORCH_LIBRARY(fcp, m) {
   m.def("cutout(Tensor crops, Tensor alpha, int mode, int bg_r, int bg_g, int bg_b, int[] taps) -> Tensor");
   m.def("mask_shift(Tensor labels, int class_bits, int shift) -> Tensor");
   m.def("nlm_denoise(Tensor crops, Tensor lut, int shift) -> Tensor");
+  m.def("unsharp(Tensor crops, int[] taps, int amount_q8, int threshold) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -862,6 +885,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("cutout", &cutout);
   m.impl("mask_shift", &mask_shift);
   m.impl("nlm_denoise", &nlm_denoise);
+  m.impl("unsharp", &unsharp);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

@@ -877,6 +877,38 @@ int fcp_clahe_u8(const uint8_t* crops, int f, int h, int w, int grid, double cli
 int fcp_nlm_denoise_u8(const uint8_t* crops, int f, int h, int w, const uint16_t* lut, int lut_len, int shift, uint8_t* out,
                        fcp_stream_t stream);
 
+/* Unsharp-mask sharpening of crops (f,h,w,3) uint8 RGB, in integers
+ * (INTEGRATION.md 2q): the gray's difference from its own Gaussian blur,
+ * cored and scaled, is added to all three channels alike, so there are no
+ * colour fringes.  With the taps t[0..radius] of uint16 in HOST memory
+ * (matte.blur_taps makes those of a sigma; they travel in the kernel's
+ * argument block):
+ *   t[0..r]  : t[0] + 2 sum(t[1..r]) == 4096, 1 <= r <= 48; a tap may be 0
+ *   g        = (9798 R + 19235 G + 3735 B + 16384) >> 15
+ *   coordinates outside the crop are clamped to its edge (BORDER_REPLICATE):
+ *   any h, w >= 1
+ *   Hs(y,x)  = sum_i t|i| g(y, clamp(x + i))               <= 255 * 4096
+ *   B(y,x)   = sum_j t|j| Hs(clamp(y + j), x)              <= 255 * 2^24 < 2^32
+ *   b8       = (B + 32768) >> 16                           the blurred gray, 8 fraction bits
+ *   d        = (g << 8) - b8                               |d| <= 65280
+ *   e        = sign(d) * max(|d| - (T << 8), 0)            T = threshold, gray levels
+ *   v_c      = (c << 16) + A_q * e + 32768                 c = R, G, B; A_q = amount_q8;
+ *                                                          |A_q e| <= 66 846 720: signed 32 bits
+ *   out_c    = v_c < 0 ? 0 : min(255, v_c >> 16)
+ * amount_q8 = 256 adds the whole difference.  threshold = 255 copies the
+ * crops, and so do the taps {4096, 0, ...}.  Integer sums commute: the bytes
+ * do not depend on the tiling and are the same from run to run.
+ * One launch on `stream`, no workspace, no float and no atomics.  crops and
+ * out may start at any byte and must not overlap (out == crops included: a
+ * workgroup reads its neighbours' pixels); nothing outside out is written.
+ * f < 0 or > 65535, h or w below 1 or above 8192, a radius outside 1..48, an
+ * amount_q8 outside 1..1024, a threshold outside 0..255, null or misaligned
+ * (2 bytes) taps, or taps that do not sum to 4096 fail with an "unsharp:"
+ * message; then f == 0 is a no-op; then a null crops / out or overlapping
+ * arrays fail likewise, all before any HIP call. */
+int fcp_unsharp_u8(const uint8_t* crops, int f, int h, int w, const uint16_t* taps, int radius, int amount_q8, int threshold,
+                   uint8_t* out, fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */
