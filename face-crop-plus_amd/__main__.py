@@ -66,6 +66,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="keep the background of the crops and blur it: sigma in output pixels, 0.5..16, of a Gaussian over "
                         "the background pixels alone (not with --background; --foreground / --feather apply); by default "
                         "the crops keep their background")
+    p.add_argument("-bi", "--background-image", type=str, nargs="+", metavar="PATH", default=argparse.SUPPRESS,
+                   help="put the subject of the crops in front of a picture: image files and / or directories of them (not "
+                        "with --background or --background-blur; --foreground / --feather apply); with several pictures a "
+                        "face gets the one its output file name hashes to; by default the crops keep their background")
+    p.add_argument("-bf", "--background-fit", type=str, default=argparse.SUPPRESS, choices=("cover", "stretch"),
+                   help="how a picture of --background-image meets the output size: 'cover' (default) scales it uniformly "
+                        "until it covers the crop and crops its centre, 'stretch' scales both axes on their own")
     p.add_argument("-rf", "--refine", type=int, default=argparse.SUPPRESS,
                    help="follow the image's edges with the matte: window radius in output pixels, 1..16, of a guided filter "
                         "of the mask (with --background or --background-blur, in place of --feather); by default the edge is "

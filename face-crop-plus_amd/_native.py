@@ -105,6 +105,9 @@ SIGNATURES = {
     "fcp_mask_shift_u8": [_P, _I, _I, _I, C.c_uint32, _I, _P, _P],
     "fcp_nlm_denoise_u8": [_P, _I, _I, _I, _P, _I, _I, _P, _P],
     "fcp_unsharp_u8": [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P],
+    "fcp_matte_image_u8": [_P, _P, _I, _I, _I, C.c_uint32, _I, _P, _I, _P, _P, _P, _P],
+    "fcp_matte_image_alpha_u8": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
+    "fcp_cutout_image_u8": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _L, _P],
 }
 EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes", "fcp_jpeg_workspace_bytes",
            "fcp_jpeg_workspace_bytes_ex", "fcp_matte_blur_workspace_bytes", "fcp_matte_refine_workspace_bytes",

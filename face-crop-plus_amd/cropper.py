@@ -66,6 +66,8 @@ class Cropper:
         foreground: list[int] | None = None,
         feather: int | None = None,
         background_blur: float | None = None,
+        background_image: str | np.ndarray | list | tuple | None = None,
+        background_fit: str | None = None,
         refine: int | None = None,
         refine_eps: int | None = None,
         subject: str | None = None,
@@ -133,6 +135,22 @@ class Cropper:
         INTEGRATION.md section 2i).  It sits where ``background`` sits, cannot be combined with it (ValueError), creates
         the parser and needs aligned crops like it; a face without a background pixel is written unchanged.  None (the
         default) launches nothing.
+        ``background_image``: put the subject in front of a picture — a path to an image file, a path to a directory
+        (every file in it that the input decoder reads, in sorted name order), an (H, W, 3) uint8 RGB array, or a list or
+        tuple of paths and arrays: K >= 1 pictures.  The fill of every pixel is the byte of the face's picture at the
+        pixel's own position; the subject, ``foreground``, ``feather`` and the composite are those of ``background``
+        (``matte.matte_image``), so a picture of one colour gives exactly the files of that
+        ``background``, and ``refine``, ``subject``, ``fill_holes``, ``edge_shift`` and ``decontaminate`` apply as they
+        do with a fill.  The pictures are fitted to ``output_size`` once, at construction, on the host with Pillow's
+        Lanczos filter — ``background_fit="cover"`` (None: that) scales uniformly until the picture covers the crop and
+        crops its centre, ``"stretch"`` scales both axes on their own, and a picture that has the output size already
+        is taken byte for byte — and stay on the device as one bank (at most 4096 pictures and 1 GiB).  With K > 1 a
+        face gets picture ``crc32(stem) % K`` of the name its file has in the output directory
+        (``matte.pick_pictures``): the same picture whatever the batch size, the workers or the other files, which makes
+        background randomisation over a bank repeatable.  It sits where ``background`` sits, cannot be combined with it
+        or with ``background_blur`` (ValueError), creates the parser and needs aligned crops like them;
+        ``background_fit`` without it raises ValueError.  None (the default) launches nothing.  ``Cropper.matte(crops,
+        labels, picks)`` applies it to crops one already has.
         ``refine``: follow the image's edges with the matte — the window radius, in output pixels (an int 1..16), of a
         guided filter (He, Sun, Tang) of the parser's hard mask with the gray of the crop as the guide: the alpha stays
         the parser's over flat regions and snaps to the crop's own edges along hair, ears and shoulders, where the label
@@ -256,13 +274,28 @@ class Cropper:
         if self.background is not None and self.background_blur is not None:
             raise ValueError("background and background_blur exclude each other: the background is filled or blurred")
         self.blur_taps = None if self.background_blur is None else matting.blur_taps(self.background_blur)
+        if background_image is None:
+            if background_fit is not None:
+                raise ValueError("background_fit needs background_image: without it it would do nothing")
+            self.background_image = self.background_fit = None
+        else:
+            if self.background is not None or self.background_blur is not None:
+                raise ValueError("background_image excludes background and background_blur: the background is filled, "
+                                 "blurred or replaced by a picture")
+            if det_threshold is None and landmarks is None:
+                raise ValueError("background_image needs aligned crops: it cannot be combined with det_threshold=None and "
+                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            self.background_fit = matting.check_fit(background_fit)
+            size = (output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size)
+            # the pictures fitted to the output size, (K, oh, ow, 3) uint8 on the host; _init_models uploads them once
+            self.background_image = matting.picture_bank(background_image, size * 2 if len(size) == 1 else size, self.background_fit)
         if self.background == matting.TRANSPARENT and (not isinstance(output_format, str) or output_format.lower() != "png"):
             raise ValueError(f"background='transparent' needs output_format='png', the one format written here that keeps an "
                              f"alpha channel, not {output_format!r}")
         self.decontaminate = matting.check_decontaminate(decontaminate)
         if self.decontaminate is not None and self.background_blur is not None:
             raise ValueError("decontaminate and background_blur exclude each other: the blurred background keeps the crop's colours")
-        if self.decontaminate is not None and self.background is None:
+        if self.decontaminate is not None and self.background is None and self.background_image is None:
             raise ValueError("decontaminate needs background (a fill or 'transparent'): without one it would do nothing")
         self.decontaminate_taps = None if self.decontaminate is None else matting.blur_taps(self.decontaminate)
         self.refine = matting.check_refine(refine)
@@ -277,7 +310,7 @@ class Cropper:
         self.subject = matting.check_subject(subject)
         self.fill_holes = matting.check_fill_holes(fill_holes)
         self.edge_shift = matting.check_edge_shift(edge_shift)
-        if self.background is None and self.background_blur is None:
+        if not self._has_background():
             if foreground is not None or feather is not None:
                 raise ValueError("foreground / feather need background or background_blur: without one they would do nothing")
             if self.refine is not None:
@@ -405,12 +438,19 @@ class Cropper:
             from .rrdb import RRDBNet
             self.enh_model = RRDBNet(self.enh_threshold)
             self.enh_model.load(self.device, self.weights.get("rrdb"), self.precision)
-        if (self.attr_groups is not None or self.mask_groups is not None or self.background is not None
-                or getattr(self, "background_blur", None) is not None):
+        if self.attr_groups is not None or self.mask_groups is not None or self._has_background():
             from .bise import BiSeNet
             self.par_model = BiSeNet(self.attr_groups, self.mask_groups, self.batch_size)
             self.par_model.load(self.device, self.weights.get("bisenet"), self.precision)
             self.par_model.masks_on_device = self._encodes_on_device()
+        image = getattr(self, "background_image", None)
+        self._pictures_dev = None if image is None else torch.from_numpy(image).to(self.device)
+
+    def _has_background(self) -> bool:
+        """Whether a background mode is on: a fill or a cut-out, a blur, or pictures.  The newer attributes are absent on
+        a Cropper made with __new__."""
+        return (self.background is not None or getattr(self, "background_blur", None) is not None
+                or getattr(self, "background_image", None) is not None)
 
     def _init_landmarks_target(self):
         if self.num_std_landmarks != 5:
@@ -476,7 +516,7 @@ class Cropper:
             sums = align.sharpness_sums(torch.from_numpy(crops).to(self.device))
             return align.sharpness_score(sums, crops.shape[1] * crops.shape[2])
 
-    def matte(self, crops: np.ndarray, labels: np.ndarray):
+    def matte(self, crops: np.ndarray, labels: np.ndarray, picks=None):
         """What ``background`` does, for crops and label maps one already has: (F,H,W,3) uint8 RGB crops and (F,H,W)
         uint8 labels -> (the composited crops (F,H,W,3) uint8, the alpha (F,H,W) uint8), with this Cropper's
         ``background`` / ``foreground`` / ``feather`` (``matte.matte``), or with its ``background_blur``
@@ -484,25 +524,42 @@ class Cropper:
         composite goes through it; with ``subject`` / ``fill_holes`` the mask is cleaned first (``matte.subject_mask``),
         and with ``edge_shift`` its boundary is then moved (``matte.shift_mask``).
         With ``background="transparent"`` the first array is the RGBA cut-out (F,H,W,4) itself; with ``decontaminate`` its
-        colours, or those composited over the fill, are the estimated subject colours (``matte.cutout``)."""
-        if self.background is None and self.background_blur is None:
-            raise ValueError("Cropper.matte needs a Cropper with background=... or background_blur=...")
+        colours, or those composited over the fill, are the estimated subject colours (``matte.cutout``).
+        With ``background_image`` the crops must have this Cropper's ``output_size`` and crop i goes over picture
+        ``picks[i]`` of the K (F ints 0..K-1; None: ``i % K``), through ``matte.matte_image`` / ``matte.cutout_image``;
+        without it ``picks`` must be None."""
+        if not self._has_background():
+            raise ValueError("Cropper.matte needs a Cropper with background=..., background_blur=... or background_image=...")
         crops, labels = np.ascontiguousarray(crops), np.ascontiguousarray(labels)
         if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
             raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
         if labels.dtype != np.uint8 or labels.shape != crops.shape[:3]:
             raise ValueError(f"labels must be {crops.shape[:3]} uint8, not {labels.dtype} {labels.shape}")
+        image = getattr(self, "background_image", None)
+        if image is None:
+            if picks is not None:
+                raise ValueError("picks need a Cropper with background_image=...: a fill or a blur has no pictures to pick from")
+        else:
+            if crops.shape[1:3] != image.shape[1:3]:
+                raise ValueError(f"crops must have the output size of the pictures, (F,{image.shape[1]},{image.shape[2]},3), "
+                                 f"not {crops.shape}")
+            if picks is not None:
+                picks = list(picks)
+                if len(picks) != len(crops) or not all(matting._is_int(p) and 0 <= int(p) < len(image) for p in picks):
+                    raise ValueError(f"picks must be {len(crops)} ints 0..{len(image) - 1}, one per crop, not {picks!r}")
         if crops.size == 0:
             return np.zeros(crops.shape, np.uint8), np.zeros(labels.shape, np.uint8)
         with torch.cuda.device(self.device):
             crops_dev, labels_dev = torch.from_numpy(crops).to(self.device), torch.from_numpy(labels).to(self.device)
-            out, alpha = self._matte_device(crops_dev, labels_dev, with_alpha=True)
+            more = {} if image is None else {"picks": picks}
+            out, alpha = self._matte_device(crops_dev, labels_dev, with_alpha=True, **more)
             return out.cpu().numpy(), alpha.cpu().numpy()
 
-    def _matte_device(self, crops_dev, labels_dev, with_alpha=False):
+    def _matte_device(self, crops_dev, labels_dev, with_alpha=False, picks=None):
         """The matte step on device tensors: the cleaned mask first when ``subject`` / ``fill_holes`` are set (it takes
         the label map's place, as class 1), its boundary moved when ``edge_shift`` is set (likewise), the refined alpha when
-        ``refine`` is set, then the composite."""
+        ``refine`` is set, then the composite.  ``picks``: with ``background_image``, the picture of each crop (None:
+        crop i over picture ``i % K``)."""
         bits = self.foreground_bits
         subject, fill_holes = getattr(self, "subject", None), getattr(self, "fill_holes", None)
         if subject is not None or fill_holes is not None:
@@ -517,8 +574,17 @@ class Cropper:
             refined["alpha"] = matting.refine_alpha(crops_dev, labels_dev, bits, self.refine, self.refine_eps)
         if self.background_blur is not None:
             return matting.matte_blur(crops_dev, labels_dev, bits, self.feather, self.blur_taps, with_alpha=with_alpha, **refined)
-        transparent = self.background == matting.TRANSPARENT
         taps = getattr(self, "decontaminate_taps", None)       # absent on a Cropper made with __new__, like refine above
+        if getattr(self, "background_image", None) is not None:                        # likewise
+            # the colour branch below, over the bank: the decontaminated composite reads an alpha plane, the plain one not
+            bank = self._pictures_dev
+            if picks is None:
+                picks = [i % bank.shape[0] for i in range(crops_dev.shape[0])]
+            if taps is None:
+                return matting.matte_image(crops_dev, labels_dev, bits, self.feather, bank, picks, with_alpha=with_alpha, **refined)
+            alpha = refined["alpha"] if refined else matting.feather_alpha(labels_dev, bits, self.feather)
+            return matting.cutout_image(crops_dev, alpha, bank, picks, taps), (alpha if with_alpha else None)
+        transparent = self.background == matting.TRANSPARENT
         if transparent or taps is not None:
             # the cut-out and the decontaminated composite read an alpha plane: the refined one, or the feathered mask
             alpha = refined["alpha"] if refined else matting.feather_alpha(labels_dev, bits, self.feather)
@@ -839,7 +905,7 @@ class Cropper:
                 if faces_dev is None:
                     faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]
                 with trace.range("fcp:parse"):
-                    if (self.background is not None or self.background_blur is not None) and isinstance(faces_dev, torch.Tensor):
+                    if self._has_background() and isinstance(faces_dev, torch.Tensor):
                         # one parse per batch: the label map behind the groups is the one the matte uses
                         *groups, labels = self.par_model.predict(faces_dev, return_labels=True)
                         groups = tuple(groups)
@@ -862,7 +928,10 @@ class Cropper:
                         faces_dev = sharpening.sharpen(faces_dev, sharpen, self.sharpen_sigma, self.sharpen_threshold)
                 if labels is not None:
                     with trace.range("fcp:matte"):
-                        faces_dev, _ = self._matte_device(faces_dev, labels)
+                        image, more = getattr(self, "background_image", None), {}
+                        if image is not None:    # a face's picture comes from the name of its file in the output directory
+                            more["picks"] = matting.pick_pictures(self._target_paths(file_names[indices], output_dir), len(image))
+                        faces_dev, _ = self._matte_device(faces_dev, labels, **more)
                 # the host copy, if the host encoder needs one, is the denoised / equalised / sharpened / matted crop as well
                 faces = None if self._encodes_on_device() else faces_dev.cpu().numpy()
             if self._encodes_on_device() and isinstance(faces_dev, torch.Tensor):

@@ -6,6 +6,7 @@
 
 #include "fcp_common.h"
 #include "fcp_feather.h"
+#include "fcp_fill.h"
 
 #define FCP_CHECK(expr)              \
   do {                               \
@@ -43,6 +44,12 @@ inline int check_class_bits(const char* who, uint32_t class_bits) {
 
 inline int check_feather(const char* who, int feather) {
   FCP_REQUIRE(feather == 0 || feather == 3 || feather == 5 || feather == 7, "%s: feather must be 0, 3, 5 or 7 (got %d)", who, feather);
+  return 0;
+}
+
+// k pictures of a bank (fcp_fill.h's Picture)
+inline int check_pictures(const char* who, int k) {
+  FCP_REQUIRE(k >= 1 && k <= fcp_fill::kMaxPictures, "%s: a bank of 1..%d pictures (got k %d)", who, fcp_fill::kMaxPictures, k);
   return 0;
 }
 

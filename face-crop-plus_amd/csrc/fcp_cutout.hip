@@ -18,6 +18,9 @@
 //   RGBA, radius r : (F_r, F_g, F_b, a) where a > 0, (0,0,0,0) where a == 0
 //   fill, radius r : (F_ch a + fill_ch (255 - a) + 127) / 255, three channels           fcp_feather.h's over255
 //   fill, radius 0 : refused: that is fcp_matte_alpha_u8, which stays the one statement of it
+//   picture, radius r : the fill composite with P_ch, the face's picture of a bank, as fill_ch (fcp_cutout_image_u8,
+//                    Cropper(background_image=...), section 2r): the same kernels with fcp_fill.h's Picture as the fill
+//                    source of the columns pass; radius 0 is refused likewise: that is fcp_matte_image_alpha_u8
 //
 // Bounds.  The sums and their unsigned 32-bit bounds are fcp_masked_blur.h's; F^, B^ <= 255.  The correction is signed
 // 32 bits: |a R| <= 254 * 65025 and 65025 F^ <= 255 * 65025, so the numerator lies in (-255 * 65025, 2^25); the floor
@@ -58,6 +61,7 @@
 #include "fcp_crop_bytes.h"
 #include "fcp_crop_checks.h"
 #include "fcp_feather.h"
+#include "fcp_fill.h"
 #include "fcp_hip.h"
 #include "fcp_masked_blur.h"
 
@@ -67,6 +71,8 @@ using namespace fcp_crop_bytes;
 using namespace fcp_crop_checks;
 using namespace fcp_feather;
 using namespace fcp_masked_blur;
+using fcp_fill::Colour;
+using fcp_fill::Picture;
 
 // columns pass
 constexpr int kTileW = 8;               // output pixels of a tile row: 2 groups of four
@@ -118,11 +124,11 @@ constexpr size_t cols_lds_bytes(int radius) {
   return (size_t)(kTileH + 2 * radius) * kColPitch * sizeof(uint4) + kTapBytes;
 }
 
-// Rgba: out is (f,h,w) dwords; else (f,h,w,3) bytes over `fill`.
-template <bool Rgba>
+// Rgba: out is (f,h,w) dwords; else (f,h,w,3) bytes over `fill`, fcp_fill.h's Colour or Picture.
+template <bool Rgba, class Fill = Colour>
 __global__ void __launch_bounds__(kThreads) cutout_cols_kernel(const uint8_t* __restrict__ crops, const uint8_t* __restrict__ alpha,
                                                                const uint4* __restrict__ sums, int h, int w, int tiles_x,
-                                                               uint32_t fill, Taps taps, int radius, uint8_t* __restrict__ out) {
+                                                               Fill fill, Taps taps, int radius, uint8_t* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* col = reinterpret_cast<uint4*>(smem);                                   // (kTileH + 2 r) rows of kColPitch
   uint32_t* tl = reinterpret_cast<uint32_t*>(col + (kTileH + 2 * radius) * kColPitch);
@@ -174,12 +180,31 @@ __global__ void __launch_bounds__(kThreads) cutout_cols_kernel(const uint8_t* __
     for (int j = 0; j < 4; ++j)
       if (j < npx) o[j] = rgba(fg[j][0], fg[j][1], fg[j][2], a[j]);
   } else {
+    const auto b = fill.face(f, h, w).group((size_t)(y0 + r) * w + x, npx);
     uint32_t o[3] = {0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 12; ++k)              // byte k of the group: pixel k / 3, channel k % 3
-      o[k >> 2] |= over255(fg[k / 3][k % 3], a[k / 3], (fill >> (8 * (k % 3))) & 255u) << (8 * (k & 3));
+      o[k >> 2] |= over255(fg[k / 3][k % 3], a[k / 3], b.byte(k)) << (8 * (k & 3));
     store_rgb(out + pixel * 3, npx, o);
   }
+}
+
+// The two launches of an estimate for the entry point `who`: the rows pass into the caller's workspace, then the columns
+// pass to RGBA or over `fill`.
+template <bool Rgba, class Fill>
+int estimate(const char* who, const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, Fill fill, const Taps& t, int radius,
+             uint8_t* out, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+  FCP_CHECK(check_workspace(who, workspace, workspace_bytes, fcp_cutout_workspace_bytes(f, h, w)));
+  uint4* sums = static_cast<uint4*>(workspace);
+  const int row_tiles_x = fcp_cdiv(w, kRowTileW), row_tiles_y = fcp_cdiv(h, kRowTileH);
+  hipLaunchKernelGGL(cutout_rows_kernel, dim3(row_tiles_x * row_tiles_y, f), dim3(kThreads), rows_lds_bytes<2>(), s, crops, alpha,
+                     h, w, row_tiles_x, t, radius, sums);
+  FCP_LAUNCH_OK();
+  const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
+  hipLaunchKernelGGL((cutout_cols_kernel<Rgba, Fill>), dim3(tiles_x * tiles_y, f), dim3(kThreads), cols_lds_bytes(radius), s, crops,
+                     alpha, sums, h, w, tiles_x, fill, t, radius, out);
+  FCP_LAUNCH_OK();
+  return 0;
 }
 
 }  // namespace
@@ -214,21 +239,23 @@ extern "C" int fcp_cutout_u8(const uint8_t* crops, const uint8_t* alpha, int f, 
     FCP_LAUNCH_OK();
     return 0;
   }
-  FCP_CHECK(check_workspace(who, workspace, workspace_bytes, fcp_cutout_workspace_bytes(f, h, w)));
-  uint4* sums = static_cast<uint4*>(workspace);
-  const int row_tiles_x = fcp_cdiv(w, kRowTileW), row_tiles_y = fcp_cdiv(h, kRowTileH);
-  hipLaunchKernelGGL(cutout_rows_kernel, dim3(row_tiles_x * row_tiles_y, f), dim3(kThreads), rows_lds_bytes<2>(), s, crops, alpha,
-                     h, w, row_tiles_x, t, radius, sums);
-  FCP_LAUNCH_OK();
-  const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
-  const uint32_t fill = packed_fill(bg_r, bg_g, bg_b);
-  if (mode == FCP_CUTOUT_RGBA) {
-    hipLaunchKernelGGL((cutout_cols_kernel<true>), dim3(tiles_x * tiles_y, f), dim3(kThreads), cols_lds_bytes(radius), s, crops,
-                       alpha, sums, h, w, tiles_x, fill, t, radius, out);
-  } else {
-    hipLaunchKernelGGL((cutout_cols_kernel<false>), dim3(tiles_x * tiles_y, f), dim3(kThreads), cols_lds_bytes(radius), s, crops,
-                       alpha, sums, h, w, tiles_x, fill, t, radius, out);
-  }
-  FCP_LAUNCH_OK();
-  return 0;
+  const Colour fill = {packed_fill(bg_r, bg_g, bg_b)};
+  if (mode == FCP_CUTOUT_RGBA) return estimate<true>(who, crops, alpha, f, h, w, fill, t, radius, out, workspace, workspace_bytes, s);
+  return estimate<false>(who, crops, alpha, f, h, w, fill, t, radius, out, workspace, workspace_bytes, s);
+}
+
+extern "C" int fcp_cutout_image_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, const uint8_t* pictures, int k,
+                                   const int32_t* picks, const uint16_t* taps, int radius, uint8_t* out, void* workspace,
+                                   int64_t workspace_bytes, fcp_stream_t stream) {
+  const char* who = "cutout_image";
+  FCP_CHECK(check_sizes(who, f, h, w));
+  FCP_REQUIRE(radius != 0, "%s: the composite needs a radius: without an estimate it is fcp_matte_image_alpha_u8", who);
+  FCP_REQUIRE(radius >= kMinRadius && radius <= kMaxRadius, "%s: radius must be %d..%d (got %d)", who, kMinRadius, kMaxRadius, radius);
+  Taps t = {};
+  FCP_CHECK(load_taps(who, taps, radius, &t));
+  FCP_CHECK(check_pictures(who, k));
+  if (f == 0) return 0;
+  FCP_REQUIRE(crops && alpha && pictures && picks && out, "%s: null pointer", who);
+  return estimate<false>(who, crops, alpha, f, h, w, Picture{pictures, picks, k}, t, radius, out, workspace, workspace_bytes,
+                         (hipStream_t)stream);
 }

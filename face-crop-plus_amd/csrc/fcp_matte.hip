@@ -12,10 +12,15 @@
 // Every output byte has one writer and depends on its own crop pixel and on labels only, so out may be the crops
 // themselves and the result is the same from run to run.
 // fcp_feather_alpha_u8 is the alpha plane of fcp_matte_u8 alone (feather_alpha_kernel): the same tile and LDS, no crop.
+// fcp_matte_image_u8 and fcp_matte_image_alpha_u8 are fcp_matte_u8 and fcp_matte_alpha_u8 over pictures (Cropper(
+// background_image=...)): the same kernel with the fill source fcp_fill.h's Picture in place of
+// Colour, so b is byte for byte the face's picture of a bank that stays on the device, read 12 bytes a group beside
+// the crop's.  The tiles, the LDS and the one launch are the same; feather 0 and the plane still have no LDS and no barrier.
 //
 // The tile.  LDS per workgroup at r = 3: mask 38 rows x 72 B = 2736 B, H 38 rows x 128 B = 4864 B, 7600 B together: 21
 // workgroups fit the 160 KiB of a CU, so the limit is the 32 wave slots of a CU: 8 workgroups of 4 waves, reached because
-// the kernel needs fewer than 64 VGPRs.  The halo costs (38 x 70) / (32 x 64) = 1.3 label bytes per pixel beside the 6
+// the kernel needs fewer than 64 VGPRs (27 to 32 over a colour, 34 or 35 over pictures: the group's picture dwords and
+// their address).  The halo costs (38 x 70) / (32 x 64) = 1.3 label bytes per pixel beside the 6
 // crop bytes a pixel moves; a 256 x 256 crop is 32 tiles, so a batch of 8 fills the 256 CUs once.  Banks: the H rows are 128
 // B, the 8-byte reads of 32 consecutive lanes (two tile rows of 16 groups) cover 256 contiguous bytes: no conflict.  The
 // mask rows are 18 dwords, so the dword reads of a half wave (rows t and t + 1, 16 groups each) meet in two of the 32
@@ -28,6 +33,7 @@
 #include "fcp_crop_bytes.h"
 #include "fcp_crop_checks.h"
 #include "fcp_feather.h"
+#include "fcp_fill.h"
 #include "fcp_hip.h"
 
 namespace {
@@ -35,15 +41,18 @@ namespace {
 using namespace fcp_crop_bytes;
 using namespace fcp_crop_checks;
 using namespace fcp_feather;
+using fcp_fill::Colour;
+using fcp_fill::Picture;
 
 constexpr int kThreads = 256;
 constexpr int kTileW = 64;             // output pixels of a tile row: 16 groups of four
 constexpr int kTileH = 32;
 
 // crops and out may be the same array: neither is __restrict__.  Plane (with R == 0): labels is an alpha plane, read as it is.
-template <int R, bool Plane = false>
+// Fill: fcp_fill.h's Colour or Picture.
+template <int R, bool Plane = false, class Fill = Colour>
 __global__ void __launch_bounds__(kThreads) matte_kernel(const uint8_t* crops, const uint8_t* __restrict__ labels, int h, int w,
-                                                         int tiles_x, uint32_t bits, uint32_t fill, uint8_t* out,
+                                                         int tiles_x, uint32_t bits, Fill fill, uint8_t* out,
                                                          uint8_t* alpha) {
   static_assert(!Plane || R == 0, "a given alpha has no feather");
   using Feather = Tile<R, kTileW, kTileH>;
@@ -53,6 +62,7 @@ __global__ void __launch_bounds__(kThreads) matte_kernel(const uint8_t* crops, c
   const int x0 = tx * kTileW, y0 = ty * kTileH;
   const int nrows = min(kTileH, h - y0);
   const int groups = (min(kTileW, w - x0) + 3) >> 2;
+  const auto behind = fill.face(f, h, w);
 
   if constexpr (R > 0) {
     Feather::stage(lds, labels + (size_t)f * h * w, h, w, x0, y0, nrows, groups, bits, kThreads);
@@ -74,10 +84,11 @@ __global__ void __launch_bounds__(kThreads) matte_kernel(const uint8_t* crops, c
 
     uint32_t c[3];
     load_rgb(crops + pixel * 3, npx, c);
+    const auto b = behind.group((size_t)y * w + x, npx);
     uint32_t o[3] = {0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 12; ++k) {            // byte k of the group: pixel k / 3, channel k % 3
-      const uint32_t v = over255((c[k >> 2] >> (8 * (k & 3))) & 255u, a[k / 3], (fill >> (8 * (k % 3))) & 255u);
+      const uint32_t v = over255((c[k >> 2] >> (8 * (k & 3))) & 255u, a[k / 3], b.byte(k));
       o[k >> 2] |= v << (8 * (k & 3));
     }
     store_rgb(out + pixel * 3, npx, o);
@@ -114,14 +125,14 @@ __global__ void __launch_bounds__(kThreads) feather_alpha_kernel(const uint8_t* 
 }
 
 // Composite false: feather_alpha_kernel, which takes labels, bits and alpha only.
-template <int R, bool Plane = false, bool Composite = true>
-void launch(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t bits, uint32_t fill, uint8_t* out,
+template <int R, bool Plane = false, bool Composite = true, class Fill = Colour>
+void launch(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t bits, Fill fill, uint8_t* out,
             uint8_t* alpha, hipStream_t stream) {
   const int tiles_x = fcp_cdiv(w, kTileW), tiles_y = fcp_cdiv(h, kTileH);
   constexpr size_t lds = Tile<R, kTileW, kTileH>::kBytes;
   const dim3 grid(tiles_x * tiles_y, f);
   if constexpr (Composite) {
-    hipLaunchKernelGGL((matte_kernel<R, Plane>), grid, dim3(kThreads), lds, stream, crops, labels, h, w, tiles_x, bits, fill, out,
+    hipLaunchKernelGGL((matte_kernel<R, Plane, Fill>), grid, dim3(kThreads), lds, stream, crops, labels, h, w, tiles_x, bits, fill, out,
                        alpha);
   } else {
     hipLaunchKernelGGL(feather_alpha_kernel<R>, grid, dim3(kThreads), lds, stream, labels, h, w, tiles_x, bits, alpha);
@@ -140,7 +151,8 @@ extern "C" int fcp_matte_u8(const uint8_t* crops, const uint8_t* labels, int f, 
   if (f == 0) return 0;
   FCP_REQUIRE(crops && labels && out, "%s: null pointer", who);
   with_feather(feather, [&](auto r) {
-    launch<decltype(r)::value>(crops, labels, f, h, w, class_bits, packed_fill(bg_r, bg_g, bg_b), out, alpha, (hipStream_t)stream);
+    launch<decltype(r)::value>(crops, labels, f, h, w, class_bits, Colour{packed_fill(bg_r, bg_g, bg_b)}, out, alpha,
+                               (hipStream_t)stream);
   });
   FCP_LAUNCH_OK();
   return 0;
@@ -153,7 +165,37 @@ extern "C" int fcp_matte_alpha_u8(const uint8_t* crops, const uint8_t* alpha, in
   FCP_CHECK(check_fill(who, bg_r, bg_g, bg_b));
   if (f == 0) return 0;
   FCP_REQUIRE(crops && alpha && out, "%s: null pointer", who);
-  launch<0, true>(crops, alpha, f, h, w, 0u, packed_fill(bg_r, bg_g, bg_b), out, nullptr, (hipStream_t)stream);
+  launch<0, true>(crops, alpha, f, h, w, 0u, Colour{packed_fill(bg_r, bg_g, bg_b)}, out, nullptr, (hipStream_t)stream);
+  FCP_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int fcp_matte_image_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather,
+                                  const uint8_t* pictures, int k, const int32_t* picks, uint8_t* out, uint8_t* alpha,
+                                  fcp_stream_t stream) {
+  const char* who = "matte_image";
+  FCP_CHECK(check_sizes(who, f, h, w));
+  FCP_CHECK(check_feather(who, feather));
+  FCP_CHECK(check_class_bits(who, class_bits));
+  FCP_CHECK(check_pictures(who, k));
+  if (f == 0) return 0;
+  FCP_REQUIRE(crops && labels && pictures && picks && out, "%s: null pointer", who);
+  with_feather(feather, [&](auto r) {
+    launch<decltype(r)::value, false, true>(crops, labels, f, h, w, class_bits, Picture{pictures, picks, k}, out, alpha,
+                                            (hipStream_t)stream);
+  });
+  FCP_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int fcp_matte_image_alpha_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, const uint8_t* pictures, int k,
+                                        const int32_t* picks, uint8_t* out, fcp_stream_t stream) {
+  const char* who = "matte_image_alpha";
+  FCP_CHECK(check_sizes(who, f, h, w));
+  FCP_CHECK(check_pictures(who, k));
+  if (f == 0) return 0;
+  FCP_REQUIRE(crops && alpha && pictures && picks && out, "%s: null pointer", who);
+  launch<0, true, true>(crops, alpha, f, h, w, 0u, Picture{pictures, picks, k}, out, nullptr, (hipStream_t)stream);
   FCP_LAUNCH_OK();
   return 0;
 }
@@ -167,7 +209,7 @@ extern "C" int fcp_feather_alpha_u8(const uint8_t* labels, int f, int h, int w, 
   if (f == 0) return 0;
   FCP_REQUIRE(labels && alpha, "%s: null pointer", who);
   with_feather(feather, [&](auto r) {
-    launch<decltype(r)::value, false, false>(nullptr, labels, f, h, w, class_bits, 0u, nullptr, alpha, (hipStream_t)stream);
+    launch<decltype(r)::value, false, false>(nullptr, labels, f, h, w, class_bits, Colour{0u}, nullptr, alpha, (hipStream_t)stream);
   });
   FCP_LAUNCH_OK();
   return 0;

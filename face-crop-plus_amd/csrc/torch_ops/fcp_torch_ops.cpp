@@ -3,7 +3,7 @@
 //
 //     torch.ops.fcp.conv2d / bottleneck_chain / retina_decode / nms_select / gather_faces / similarity_from_5pt /
 //     warp_affine_u8 / warp_affine_u8_float / warp_affine_u8_ragged / warp_affine_u8_interp / warp_affine_u8_interp_ragged /
-//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout / mask_shift / nlm_denoise / unsharp
+//     resize_area_u8_ragged / bicubic_down4_round / parse_argmax_hist / crop_sharpness / jpeg_encode / jpeg_encode_ex / jpeg_huffman_tables / png_encode / png_huffman_lengths / matte / clahe / matte_blur / matte_refine / matte_alpha / matte_blur_alpha / subject_mask / feather_alpha / cutout / mask_shift / nlm_denoise / unsharp / matte_image / matte_image_alpha / cutout_image
 //
 // Each op validates device / dtype / contiguity with TORCH_CHECK (-> RuntimeError), allocates its outputs with torch's
 // caching allocator, borrows its inputs, enqueues the HIP kernels of libfcp_hip.so on at::hip's CURRENT stream and
@@ -679,6 +679,75 @@ Tensor cutout(const Tensor& crops, const Tensor& alpha, int64_t mode, int64_t bg
   return out;
 }
 
+// The bank of the picture ops: pictures (k,h,w,3) uint8 with the crops' h and w, and picks (f,) int32, one picture per
+// crop, both on the device of the crops.  Returns k.
+static int bank_and_picks(const Tensor& crops, const Tensor& pictures, const Tensor& picks) {
+  dev(pictures, "pictures", at::kByte);
+  dev(picks, "picks", at::kInt);
+  TORCH_CHECK(pictures.get_device() == crops.get_device() && pictures.dim() == 4 && pictures.size(1) == crops.size(1) &&
+                  pictures.size(2) == crops.size(2) && pictures.size(3) == 3,
+              "pictures must be (k,", crops.size(1), ",", crops.size(2), ",3) uint8 on the device of the crops");
+  TORCH_CHECK(pictures.size(0) <= INT_MAX, "pictures (k,h,w,3): k past int");
+  TORCH_CHECK(picks.get_device() == crops.get_device() && picks.dim() == 1 && picks.size(0) == crops.size(0), "picks must be (",
+              crops.size(0), ",) int32 on the device of the crops");
+  return (int)pictures.size(0);
+}
+
+// matte over pictures: the fill of crop i is pictures[picks[i]] (fcp_matte_image_u8).
+std::tuple<Tensor, Tensor> matte_image(const Tensor& crops, const Tensor& labels, int64_t class_bits, int64_t feather,
+                                       const Tensor& pictures, const Tensor& picks, bool with_alpha) {
+  dev(crops, "crops", at::kByte);
+  dev(labels, "labels", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  int64_t f, h, w;
+  crops_and_plane(crops, labels, "labels", f, h, w);
+  const int k = bank_and_picks(crops, pictures, picks);
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  TORCH_CHECK(feather >= INT_MIN && feather <= INT_MAX, "feather past int");
+  Tensor out = at::empty_like(crops);
+  Tensor alpha = with_alpha ? at::empty({f, h, w}, crops.options()) : at::empty({0}, crops.options());
+  ok(fcp_matte_image_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits,
+                        (int)feather, pictures.data_ptr<uint8_t>(), k, picks.data_ptr<int32_t>(), out.data_ptr<uint8_t>(),
+                        with_alpha ? alpha.data_ptr<uint8_t>() : nullptr, cur_stream()),
+     "fcp::matte_image");
+  return {out, alpha};
+}
+
+// matte_alpha over pictures (fcp_matte_image_alpha_u8).
+Tensor matte_image_alpha(const Tensor& crops, const Tensor& alpha, const Tensor& pictures, const Tensor& picks) {
+  dev(crops, "crops", at::kByte);
+  dev(alpha, "alpha", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  int64_t f, h, w;
+  crops_and_plane(crops, alpha, "alpha", f, h, w);
+  const int k = bank_and_picks(crops, pictures, picks);
+  Tensor out = at::empty_like(crops);
+  ok(fcp_matte_image_alpha_u8(crops.data_ptr<uint8_t>(), alpha.data_ptr<uint8_t>(), (int)f, (int)h, (int)w,
+                              pictures.data_ptr<uint8_t>(), k, picks.data_ptr<int32_t>(), out.data_ptr<uint8_t>(), cur_stream()),
+     "fcp::matte_image_alpha");
+  return out;
+}
+
+// The fill mode of cutout over pictures, taps = t[0..radius] (fcp_cutout_image_u8); the 32-bytes-per-pixel workspace
+// lives for the call.
+Tensor cutout_image(const Tensor& crops, const Tensor& alpha, const Tensor& pictures, const Tensor& picks, at::IntArrayRef taps) {
+  dev(crops, "crops", at::kByte);
+  dev(alpha, "alpha", at::kByte);
+  FCP_DEVICE_GUARD(crops);
+  int64_t f, h, w;
+  crops_and_plane(crops, alpha, "alpha", f, h, w);
+  const int k = bank_and_picks(crops, pictures, picks);
+  uint16_t t16[49] = {};
+  const int radius = taps16("cutout_image", taps, false, t16);
+  Tensor out = at::empty_like(crops);
+  Tensor work = workspace(fcp_cutout_workspace_bytes((int)f, (int)h, (int)w), crops);
+  ok(fcp_cutout_image_u8(crops.data_ptr<uint8_t>(), alpha.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, pictures.data_ptr<uint8_t>(),
+                         k, picks.data_ptr<int32_t>(), t16, radius, out.data_ptr<uint8_t>(), work.data_ptr(), work.numel(),
+                         cur_stream()),
+     "fcp::cutout_image");
+  return out;
+}
+
 // The cleaned binary label map (f,h,w) uint8, 0 / 1, of label maps (f,h,w) uint8: the largest 8-connected component of
 // the hard mask and / or its holes of at most max_hole pixels filled (fcp_subject_mask_u8); the 12-bytes-per-pixel
 // workspace lives for the call.
@@ -845,6 +914,10 @@ TORCH_LIBRARY(fcp, m) {
   m.def("mask_shift(Tensor labels, int class_bits, int shift) -> Tensor");
   m.def("nlm_denoise(Tensor crops, Tensor lut, int shift) -> Tensor");
   m.def("unsharp(Tensor crops, int[] taps, int amount_q8, int threshold) -> Tensor");
+  m.def("matte_image(Tensor crops, Tensor labels, int class_bits, int feather, Tensor pictures, Tensor picks, bool with_alpha) "
+        "-> (Tensor, Tensor)");
+  m.def("matte_image_alpha(Tensor crops, Tensor alpha, Tensor pictures, Tensor picks) -> Tensor");
+  m.def("cutout_image(Tensor crops, Tensor alpha, Tensor pictures, Tensor picks, int[] taps) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -886,6 +959,9 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("mask_shift", &mask_shift);
   m.impl("nlm_denoise", &nlm_denoise);
   m.impl("unsharp", &unsharp);
+  m.impl("matte_image", &matte_image);
+  m.impl("matte_image_alpha", &matte_image_alpha);
+  m.impl("cutout_image", &cutout_image);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

@@ -52,11 +52,24 @@ with the old background, by an estimate of the subject's own, for the cut-out an
     out(y,x) is one byte, 0 or 1, and takes the label map's place downstream like ``subject_mask``'s (``SUBJECT_BITS``)
 
 A shrink does not eat inwards from the crop's border: shoulders that touch the bottom row stay there.
+
+``Cropper(background_image=...)`` (section 2r) puts the subject in front of a picture: the fill of a pixel becomes the
+byte of the face's picture P at the pixel's own position,
+
+    out   = (crop * alpha + P * (255 - alpha) + 127) // 255           (the subject's colour F for the crop with
+            ``decontaminate``)
+
+with the alpha the mode already has (``matte_image`` / ``cutout_image``: ``fcp_matte_image_u8``,
+``fcp_matte_image_alpha_u8``, ``fcp_cutout_image_u8``, the kernels of the fill with the picture as their fill source).
+The pictures are fitted to the output size once, on the host (``picture_bank``), and stay on the device as a bank
+(K, H, W, 3); face i reads picture ``picks[i]``, which ``pick_pictures`` makes from the name of the face's file.
 """
 from __future__ import annotations
 
 import ctypes
 import math
+import os
+import zlib
 
 import numpy as np
 import torch
@@ -78,6 +91,10 @@ SUBJECT_BITS = 1 << 1          # the class bit set that reads ``subject_mask``'s
 TRANSPARENT = "transparent"    # ``check_background``'s answer for the RGBA cut-out: no fill, the alpha ships in the file
 CUTOUT_RGBA, CUTOUT_FILL = 0, 1   # fcp_hip.h: FCP_CUTOUT_RGBA, FCP_CUTOUT_FILL
 MAX_EDGE_SHIFT = 64            # the largest |edge_shift|, in output pixels: the halo a tile of fcp_mask_shift_u8 stages
+FITS = ("cover", "stretch")    # ``background_fit``: a uniform scale that covers the crop, centre-cropped; or both axes on their own
+DEFAULT_FIT = "cover"
+MAX_PICTURES = 4096            # csrc/fcp_fill.h: kMaxPictures
+MAX_BANK_BYTES = 1 << 30       # of device memory a Cropper keeps for its pictures
 
 
 def _is_int(v) -> bool:
@@ -195,6 +212,88 @@ def check_edge_shift(edge_shift):
         raise ValueError(f"edge_shift must be None or a non-zero int -{MAX_EDGE_SHIFT}..{MAX_EDGE_SHIFT} (pixels: positive grows "
                          f"the subject, negative shrinks it), not {edge_shift!r}")
     return int(edge_shift)
+
+
+def check_fit(fit) -> str:
+    """``background_fit`` of the Cropper -> "cover" or "stretch" (None: "cover")."""
+    if fit is None:
+        return DEFAULT_FIT
+    if not isinstance(fit, str) or fit not in FITS:
+        raise ValueError(f"background_fit must be None or one of {FITS}, not {fit!r}")
+    return fit
+
+
+def _picture_array(picture) -> np.ndarray:
+    if picture.dtype != np.uint8 or picture.ndim != 3 or picture.shape[2] != 3 or min(picture.shape[:2]) < 1:
+        raise ValueError(f"background_image arrays must be (H, W, 3) uint8 RGB with H, W >= 1, not {picture.dtype} {picture.shape}")
+    return np.ascontiguousarray(picture)
+
+
+def load_pictures(background_image) -> list:
+    """``background_image`` of the Cropper -> its K >= 1 pictures, (H, W, 3) uint8 RGB arrays: a path to an image file, a
+    path to a directory (every file in it that ``utils.read_image`` reads, in sorted name order), an array, or a list
+    or tuple of those.  Files are decoded as the inputs of ``process_dir`` are."""
+    from ._io_codec import read_image
+    if isinstance(background_image, np.ndarray):
+        return [_picture_array(background_image)]
+    if isinstance(background_image, (str, os.PathLike)):
+        path = os.fspath(background_image)
+        if os.path.isdir(path):
+            found = [read_image(os.path.join(path, name)) for name in sorted(os.listdir(path))]
+            found = [p for p in found if p is not None]
+            if not found:
+                raise ValueError(f"background_image: the directory {path!r} holds no image that can be read")
+            return found
+        if not os.path.isfile(path):
+            raise ValueError(f"background_image: no such file or directory: {path!r}")
+        picture = read_image(path)
+        if picture is None:
+            raise ValueError(f"background_image: {path!r} cannot be read as an image")
+        return [picture]
+    if isinstance(background_image, (list, tuple)):
+        if len(background_image) == 0:
+            raise ValueError("background_image must name at least one picture, not an empty list")
+        if any(isinstance(item, (list, tuple)) for item in background_image):
+            raise ValueError("background_image: a list holds paths and (H, W, 3) uint8 arrays, not lists")
+        return [picture for item in background_image for picture in load_pictures(item)]
+    raise ValueError(f"background_image must be None, a path, an (H, W, 3) uint8 array or a list of those, not {background_image!r}")
+
+
+def fit_picture(picture: np.ndarray, size, fit: str = DEFAULT_FIT) -> np.ndarray:
+    """One picture (H, W, 3) uint8 -> (oh, ow, 3) uint8 for ``size`` = (ow, oh).  A picture of that size is taken as it
+    is; otherwise Pillow's Lanczos resample of a box of it: the whole picture ("stretch"), or the centred box of the
+    crop's aspect ratio, the largest the picture holds ("cover": a uniform scale, nothing of the crop left uncovered)."""
+    ow, oh = size
+    H, W = picture.shape[:2]
+    if (W, H) == (ow, oh):
+        return np.ascontiguousarray(picture)
+    from PIL import Image
+    box = (0, 0, W, H)
+    if fit == "cover":
+        s = max(ow / W, oh / H)
+        bw, bh = ow / s, oh / s
+        box = (max((W - bw) / 2, 0), max((H - bh) / 2, 0), min((W + bw) / 2, W), min((H + bh) / 2, H))
+    return np.asarray(Image.fromarray(picture).resize((ow, oh), Image.Resampling.LANCZOS, box=box))
+
+
+def picture_bank(background_image, size, fit: str = DEFAULT_FIT) -> np.ndarray:
+    """``background_image`` -> the bank (K, oh, ow, 3) uint8 for ``size`` = (ow, oh), on the host: every picture of
+    ``load_pictures`` through ``fit_picture``.  At most 4096 pictures and 1 GiB."""
+    ow, oh = size
+    pictures = load_pictures(background_image)
+    nbytes = len(pictures) * oh * ow * 3
+    if len(pictures) > MAX_PICTURES:
+        raise ValueError(f"background_image: at most {MAX_PICTURES} pictures (got {len(pictures)})")
+    if nbytes > MAX_BANK_BYTES:
+        raise ValueError(f"background_image: the bank of {len(pictures)} pictures of {ow} x {oh} px needs {nbytes} bytes of "
+                         f"device memory, more than {MAX_BANK_BYTES}")
+    return np.stack([fit_picture(p, (ow, oh), fit) for p in pictures])
+
+
+def pick_pictures(names, k: int) -> list:
+    """The picture of each face of a bank of ``k``: crc32 of the stem (the base name without its extension, UTF-8) of the
+    face's file, modulo k.  It depends on nothing but the name: not on the batch, its order or the other files."""
+    return [zlib.crc32(os.path.splitext(os.path.basename(str(name)))[0].encode("utf-8")) % k for name in names]
 
 
 def blur_taps(sigma) -> list:
@@ -381,4 +480,75 @@ def matte(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, fe
     alpha = torch.empty((f, h, w), dtype=torch.uint8, device=crops_dev.device) if with_alpha else None
     N.check(N.lib().fcp_matte_u8(N.ptr(crops_dev), N.ptr(labels_dev), f, h, w, int(class_bits), int(feather), r, g, b,
                                  N.ptr(out), N.ptr(alpha), N.stream_ptr()), "fcp_matte_u8")
+    return out, alpha
+
+
+def _check_bank(pictures_dev, picks, crops_dev) -> torch.Tensor:
+    """The bank (K,H,W,3) u8, contiguous, on the crops' device and of the crops' H and W, and the picks, F ints 0..K-1 on
+    the host -> the picks (F,) int32 on the device."""
+    f, h, w, _ = crops_dev.shape
+    if not isinstance(pictures_dev, torch.Tensor) or pictures_dev.dtype != torch.uint8 or not pictures_dev.is_contiguous() or \
+            pictures_dev.dim() != 4 or pictures_dev.shape[0] < 1 or tuple(pictures_dev.shape[1:]) != (h, w, 3) or \
+            pictures_dev.device != crops_dev.device:
+        raise ValueError(f"pictures must be a contiguous (K,{h},{w},3) uint8 tensor on {crops_dev.device}, K >= 1, not "
+                         f"{getattr(pictures_dev, 'dtype', type(pictures_dev))} {tuple(getattr(pictures_dev, 'shape', ()))} on "
+                         f"{getattr(pictures_dev, 'device', 'the host')}")
+    k = pictures_dev.shape[0]
+    picks = list(picks)
+    if len(picks) != f or not all(_is_int(p) and 0 <= int(p) < k for p in picks):
+        raise ValueError(f"picks must be {f} ints 0..{k - 1}, one per crop, not {picks!r}")
+    return torch.tensor([int(p) for p in picks], dtype=torch.int32).to(crops_dev.device)
+
+
+def cutout_image(crops_dev: torch.Tensor, alpha: torch.Tensor, pictures_dev: torch.Tensor, picks, taps) -> torch.Tensor:
+    """``cutout`` with a fill, over pictures: crops (F,H,W,3) u8, an alpha plane (F,H,W) u8, a bank (K,H,W,3) u8, all on one
+    device, and F picks 0..K-1 on the host -> the composite (F,H,W,3) u8 of the subject's colour, estimated with the taps
+    t[0..r] of ``blur_taps``, over picture ``picks[i]`` for crop i.  Without an estimate that is ``matte_image`` with the
+    plane.  Two launches and a workspace of 32 bytes per pixel that lives for the call; H, W <= 8192."""
+    _check_crops(crops_dev)
+    _check_alpha(alpha, crops_dev)
+    picks_dev = _check_bank(pictures_dev, picks, crops_dev)
+    taps = [int(t) for t in taps]
+    if T.ENABLED:
+        return T.load().cutout_image(crops_dev, alpha, pictures_dev, picks_dev, taps)
+    _check_taps("fcp_cutout_image_u8", taps)
+    f, h, w, _ = crops_dev.shape
+    out = torch.empty_like(crops_dev)
+    need = max(int(N.lib().fcp_cutout_workspace_bytes(f, h, w)), 0)
+    work = torch.empty((need,), dtype=torch.uint8, device=crops_dev.device)
+    t16 = (ctypes.c_uint16 * len(taps))(*taps)
+    N.check(N.lib().fcp_cutout_image_u8(N.ptr(crops_dev), N.ptr(alpha), f, h, w, N.ptr(pictures_dev), pictures_dev.shape[0],
+                                        N.ptr(picks_dev), t16, len(taps) - 1, N.ptr(out), N.ptr(work), need, N.stream_ptr()),
+            "fcp_cutout_image_u8")
+    return out
+
+
+def matte_image(crops_dev: torch.Tensor, labels_dev: torch.Tensor, class_bits: int, feather: int, pictures_dev: torch.Tensor, picks,
+                with_alpha: bool = False, alpha: torch.Tensor | None = None):
+    """``matte`` over pictures: crops (F,H,W,3) u8, labels (F,H,W) u8 and a bank (K,H,W,3) u8, all on one device, and F
+    picks 0..K-1 on the host -> (out (F,H,W,3) u8, alpha (F,H,W) u8 or None), device: crop i over picture ``picks[i]``.
+    One launch; H, W <= 8192.  With ``alpha`` (F,H,W) u8 the composite goes through that plane, as in ``matte``."""
+    _check_crops(crops_dev, labels_dev)
+    picks_dev = _check_bank(pictures_dev, picks, crops_dev)
+    k = pictures_dev.shape[0]
+    if alpha is not None:
+        _check_alpha(alpha, crops_dev)
+        if T.ENABLED:
+            out = T.load().matte_image_alpha(crops_dev, alpha, pictures_dev, picks_dev)
+        else:
+            f, h, w, _ = crops_dev.shape
+            out = torch.empty_like(crops_dev)
+            N.check(N.lib().fcp_matte_image_alpha_u8(N.ptr(crops_dev), N.ptr(alpha), f, h, w, N.ptr(pictures_dev), k, N.ptr(picks_dev),
+                                                     N.ptr(out), N.stream_ptr()), "fcp_matte_image_alpha_u8")
+        return out, (alpha if with_alpha else None)
+    if T.ENABLED:
+        out, alpha = T.load().matte_image(crops_dev, labels_dev, int(class_bits), int(feather), pictures_dev, picks_dev,
+                                          bool(with_alpha))
+        return out, (alpha if with_alpha else None)
+    f, h, w, _ = crops_dev.shape
+    out = torch.empty_like(crops_dev)
+    alpha = torch.empty((f, h, w), dtype=torch.uint8, device=crops_dev.device) if with_alpha else None
+    N.check(N.lib().fcp_matte_image_u8(N.ptr(crops_dev), N.ptr(labels_dev), f, h, w, int(class_bits), int(feather),
+                                       N.ptr(pictures_dev), k, N.ptr(picks_dev), N.ptr(out), N.ptr(alpha), N.stream_ptr()),
+            "fcp_matte_image_u8")
     return out, alpha

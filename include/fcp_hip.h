@@ -740,6 +740,43 @@ int64_t fcp_cutout_workspace_bytes(int f, int h, int w);
 int fcp_cutout_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, int mode, int bg_r, int bg_g, int bg_b,
                   const uint16_t* taps, int radius, uint8_t* out, void* workspace, int64_t workspace_bytes, fcp_stream_t stream);
 
+/* Crops over pictures: the composites above with the
+ * fill of a pixel read from a bank of pictures that is resident on the
+ * device.  pictures (k,h,w,3) uint8 RGB, 1 <= k <= 4096, with the crops' h
+ * and w; picks (f,) int32 on the device, 0 <= picks[i] < k; P = the picture
+ * picks[face] at the pixel's own position:
+ *   fcp_matte_image_u8:       fcp_matte_u8 with P_ch as bg_ch (m, alpha and
+ *       the rounding are that entry's; alpha may be NULL);
+ *   fcp_matte_image_alpha_u8: fcp_matte_alpha_u8 likewise, through an alpha
+ *       plane (f,h,w) of the caller's;
+ *   fcp_cutout_image_u8:      the FCP_CUTOUT_FILL mode of fcp_cutout_u8
+ *       likewise: out = (F * alpha + P * (255 - alpha) + 127) / 255 with the
+ *       estimate F of that entry, its taps, radius 3..48 and its workspace of
+ *       fcp_cutout_workspace_bytes(f,h,w) bytes; radius 0 is refused: that
+ *       composite is fcp_matte_image_alpha_u8.
+ * So alpha == 0 gives the picture's bytes, alpha == 255 the crop's, and a
+ * picture of one colour the bytes of the sibling with that colour as bg.
+ * The same kernels and launches as the siblings (one; one; two), the fill
+ * source being their template parameter; a group's 12 picture bytes are read
+ * beside the crop's, rows of 3 w bytes at any byte offset, and no dword is
+ * read that holds no byte of the bank.  A pick outside 0..k-1 breaks the
+ * precondition; the kernels clamp it, so that the read stays inside the bank.
+ * out MAY BE crops for the two matte entries, as for their siblings, and is
+ * its own array for the cutout; pictures and picks are only read and must
+ * not overlap out or alpha.  The same bytes from run to run.
+ * f == 0 is a no-op; the sizes, feather, class_bits, radius, taps and
+ * workspace fail as in the siblings, a k outside 1..4096 and (f > 0) a null
+ * crops / labels / alpha plane / pictures / picks / out fail too, with a
+ * "matte_image:", "matte_image_alpha:" or "cutout_image:" message, before
+ * any HIP call. */
+int fcp_matte_image_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, int feather,
+                       const uint8_t* pictures, int k, const int32_t* picks, uint8_t* out, uint8_t* alpha, fcp_stream_t stream);
+int fcp_matte_image_alpha_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, const uint8_t* pictures, int k,
+                             const int32_t* picks, uint8_t* out, fcp_stream_t stream);
+int fcp_cutout_image_u8(const uint8_t* crops, const uint8_t* alpha, int f, int h, int w, const uint8_t* pictures, int k,
+                        const int32_t* picks, const uint16_t* taps, int radius, uint8_t* out, void* workspace,
+                        int64_t workspace_bytes, fcp_stream_t stream);
+
 /* One connected subject in a matte: connected-component
  * labelling of the hard mask of label maps (f,h,w) uint8, every face on its
  * own, in integers.  H = h, W = w:
