@@ -35,7 +35,33 @@ def landmarks_target(output_size, face_factor):
     return std
 
 
+def _pair(v):
+    """An int, a numpy integer or a sequence of one or two of them -> the (width, height) pair."""
+    v = (v,) if isinstance(v, (int, np.integer)) else tuple(v)
+    return v * 2 if len(v) == 1 else v
+
+
+def _u8_crops(crops, channels=(3,), gray=False):
+    """The checked, contiguous form of a crop array the public per-step helpers take: uint8, (F,H,W,C) with C one of
+    ``channels``, or (F,H,W) where ``gray`` allows it."""
+    crops = np.ascontiguousarray(crops)
+    if crops.dtype != np.uint8 or not ((crops.ndim == 4 and crops.shape[3] in channels) or (gray and crops.ndim == 3)):
+        shapes = [f"(F,H,W,{c})" for c in channels] + ["(F,H,W)"] * gray
+        shapes = ", ".join(shapes[:-1]) + " or " * (len(shapes) > 1) + shapes[-1]         # "a, b or c"
+        raise ValueError(f"crops must be {shapes} uint8, not {crops.dtype} {crops.shape}")
+    return crops
+
+
 class Cropper:
+    # Every optional setting and every lazily created piece of state, at its "off" value: a Cropper made with __new__
+    # (the CPU tests make them) or unpickled from an older build reads whatever __init__ never set on it as switched off.
+    background = background_blur = background_image = background_fit = blur_taps = decontaminate = decontaminate_taps = None
+    refine = refine_eps = subject = fill_holes = edge_shift = denoise = clahe = clahe_grid = None
+    sharpen = sharpen_sigma = sharpen_threshold = min_sharpness = jpeg = io_ring_mb = None
+    _io = _io_procs = _io_procs_active = _rows_cache = _pictures_dev = None
+    png_encoder = encoder = "host"
+    foreground_bits = 0
+
     def __init__(
         self,
         output_size: int | tuple[int, int] | list[int] = 256,
@@ -224,6 +250,7 @@ class Cropper:
         stays exact) and the encoder; the histograms are over the whole crop and mask files are unchanged.  It needs
         aligned crops like ``min_sharpness`` and an ``output_size`` of at least ``2 * clahe_grid`` on both sides;
         ``clahe_grid`` without ``clahe`` raises ValueError.  None (the default) launches nothing.
+        ``Cropper.equalize`` applies it to crops one already has.
         ``sharpen``: sharpen every crop — the amount A (a finite number 0.05..4; 1.0 adds the whole difference) of an
         unsharp mask of the gray: the gray's difference from its own Gaussian blur of ``sharpen_sigma`` output pixels
         (0.5..16, the range and the taps of ``background_blur``; None: 1.5), less ``sharpen_threshold`` gray levels
@@ -236,7 +263,6 @@ class Cropper:
         colour stays exact.  It needs aligned crops like ``min_sharpness``; any ``output_size`` will do.
         ``sharpen_sigma`` or ``sharpen_threshold`` without ``sharpen`` raises ValueError.  None (the default) launches
         nothing.  ``Cropper.unsharp`` applies it to crops one already has.
-        ``Cropper.equalize`` applies it to crops one already has.
         ``jpeg_quality`` (an int, 1..100; 95), ``jpeg_subsampling`` ("4:4:4", "4:2:2" or "4:2:0"; "4:2:0") and
         ``jpeg_optimize`` (per-file Huffman tables, Pillow's ``optimize=True``: smaller files, the same pixels; False):
         the settings of every JPEG file (.jpg / .jpeg / .jpe) this Cropper writes — aligned crops, the mask files of
@@ -244,6 +270,16 @@ class Cropper:
         (INTEGRATION.md section 2j); other formats are untouched.  A gray mask file has no chroma: the subsampling only
         changes the sampling byte of its frame header, as it does in Pillow.  The defaults are ``cv2.imwrite``'s, i.e. the
         reference's, and change nothing.  ``Cropper.encode_jpeg`` uses them too."""
+        # the size checks of clahe and denoise quote the size in their messages as it was given: one number stays one
+        size_given = (output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size)
+        self.output_size, self.resize_size = output_size, resize_size = _pair(size_given), _pair(resize_size)
+        aligned = det_threshold is not None or landmarks is not None
+
+        def needs_aligned(subject, plural=False):
+            if not aligned:
+                raise ValueError(f"{subject} {'need' if plural else 'needs'} aligned crops: {'they' if plural else 'it'} "
+                                 f"cannot be combined with det_threshold=None and landmarks=None (no alignment), where the "
+                                 f"faces are the images themselves")
         if encoder not in ("host", "device"):
             raise ValueError(f"unknown encoder {encoder!r}: choose 'host' or 'device'")
         self.encoder = encoder
@@ -264,9 +300,7 @@ class Cropper:
                 raise ValueError(f"min_sharpness must be a number or None, not {min_sharpness!r}")
             if not np.isfinite(min_sharpness) or min_sharpness < 0:
                 raise ValueError(f"min_sharpness must be finite and >= 0 (a variance), not {min_sharpness!r}")
-            if det_threshold is None and landmarks is None:
-                raise ValueError("min_sharpness needs aligned crops: it cannot be combined with det_threshold=None and "
-                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            needs_aligned("min_sharpness")
             min_sharpness = float(min_sharpness)
         self.min_sharpness = min_sharpness
         self.background = matting.check_background(background)
@@ -277,18 +311,14 @@ class Cropper:
         if background_image is None:
             if background_fit is not None:
                 raise ValueError("background_fit needs background_image: without it it would do nothing")
-            self.background_image = self.background_fit = None
         else:
             if self.background is not None or self.background_blur is not None:
                 raise ValueError("background_image excludes background and background_blur: the background is filled, "
                                  "blurred or replaced by a picture")
-            if det_threshold is None and landmarks is None:
-                raise ValueError("background_image needs aligned crops: it cannot be combined with det_threshold=None and "
-                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            needs_aligned("background_image")
             self.background_fit = matting.check_fit(background_fit)
-            size = (output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size)
             # the pictures fitted to the output size, (K, oh, ow, 3) uint8 on the host; _init_models uploads them once
-            self.background_image = matting.picture_bank(background_image, size * 2 if len(size) == 1 else size, self.background_fit)
+            self.background_image = matting.picture_bank(background_image, output_size, self.background_fit)
         if self.background == matting.TRANSPARENT and (not isinstance(output_format, str) or output_format.lower() != "png"):
             raise ValueError(f"background='transparent' needs output_format='png', the one format written here that keeps an "
                              f"alpha channel, not {output_format!r}")
@@ -302,7 +332,6 @@ class Cropper:
         if self.refine is None:
             if refine_eps is not None:
                 raise ValueError("refine_eps needs refine: without it it would do nothing")
-            self.refine_eps = None
         else:
             self.refine_eps = matting.check_refine_eps(refine_eps)
             if feather is not None:
@@ -321,10 +350,7 @@ class Cropper:
                 raise ValueError("edge_shift needs background or background_blur: without one it would do nothing")
             self.foreground, self.foreground_bits, self.feather = None, 0, None
         else:
-            if det_threshold is None and landmarks is None:
-                raise ValueError("background / background_blur need aligned crops: they cannot be combined with "
-                                 "det_threshold=None and landmarks=None (no alignment), where the faces are the images "
-                                 "themselves")
+            needs_aligned("background / background_blur", plural=True)
             self.foreground_bits = matting.check_foreground(foreground)
             self.foreground = tuple(c for c in range(matting.NUM_CLASSES) if self.foreground_bits >> c & 1)
             self.feather = 0 if self.refine is not None else matting.check_feather(feather)
@@ -332,48 +358,31 @@ class Cropper:
         if self.clahe is None:
             if clahe_grid is not None:
                 raise ValueError("clahe_grid needs clahe: without it it would do nothing")
-            self.clahe_grid = None
         else:
-            if det_threshold is None and landmarks is None:
-                raise ValueError("clahe needs aligned crops: it cannot be combined with det_threshold=None and "
-                                 "landmarks=None (no alignment), where the faces are the images themselves")
-            size = (output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size)
-            self.clahe_grid = equalizing.check_grid(clahe_grid, size)
+            needs_aligned("clahe")
+            self.clahe_grid = equalizing.check_grid(clahe_grid, size_given)
         self.denoise = denoising.check_denoise(denoise)
         if self.denoise is not None:
-            if det_threshold is None and landmarks is None:
-                raise ValueError("denoise needs aligned crops: it cannot be combined with det_threshold=None and "
-                                 "landmarks=None (no alignment), where the faces are the images themselves")
-            denoising.check_size((output_size,) if isinstance(output_size, (int, np.integer)) else tuple(output_size))
+            needs_aligned("denoise")
+            denoising.check_size(size_given)
         self.sharpen = sharpening.check_sharpen(sharpen)
         if self.sharpen is None:
             for name, value in (("sharpen_sigma", sharpen_sigma), ("sharpen_threshold", sharpen_threshold)):
                 if value is not None:
                     raise ValueError(f"{name} needs sharpen: without it it would do nothing")
-            self.sharpen_sigma = self.sharpen_threshold = None
         else:
-            if det_threshold is None and landmarks is None:
-                raise ValueError("sharpen needs aligned crops: it cannot be combined with det_threshold=None and "
-                                 "landmarks=None (no alignment), where the faces are the images themselves")
+            needs_aligned("sharpen")
             self.sharpen_sigma = sharpening.check_sigma(sharpen_sigma)
             self.sharpen_threshold = sharpening.check_threshold(sharpen_threshold)
-        self.crop_source = crop_source
-        self.interpolation = interpolation
-        self.output_size = output_size
-        self.output_format = output_format
-        self.resize_size = resize_size
-        self.face_factor = face_factor
-        self.strategy = strategy
-        self.padding = padding
-        self.allow_skew = allow_skew
-        self.landmarks = landmarks
-        self.attr_groups = attr_groups
-        self.mask_groups = mask_groups
-        self.det_threshold = det_threshold
-        self.enh_threshold = enh_threshold
-        self.batch_size = batch_size
-        self.num_processes = num_processes
+        self.crop_source, self.interpolation, self.output_format = crop_source, interpolation, output_format
+        self.face_factor, self.strategy, self.padding, self.allow_skew = face_factor, strategy, padding, allow_skew
+        self.attr_groups, self.mask_groups = attr_groups, mask_groups
+        self.det_threshold, self.enh_threshold = det_threshold, enh_threshold
+        self.batch_size, self.num_processes = batch_size, num_processes
         self.device = device
+        if isinstance(device, str):
+            self.device = torch.device("cuda:0" if device in ("cuda", "hip") else device.replace("hip", "cuda"))
+        self.landmarks = parse_landmarks_file(landmarks) if isinstance(landmarks, str) else landmarks
         self.weights = weights or {}
         self.precision = precision   # "f16x3" (default) | "f32": arithmetic of the conv engine
         self.num_std_landmarks = 5
@@ -395,19 +404,6 @@ class Cropper:
         # flight, semaphore bounding them), so that a task of a failed run can never see a half-reset state
         self._io = None
         self._write_lock = Lock()
-
-        if isinstance(self.output_size, int):
-            self.output_size = (self.output_size, self.output_size)
-        if len(self.output_size) == 1:
-            self.output_size = (self.output_size[0], self.output_size[0])
-        if isinstance(self.resize_size, int):
-            self.resize_size = (self.resize_size, self.resize_size)
-        if len(self.resize_size) == 1:
-            self.resize_size = (self.resize_size[0], self.resize_size[0])
-        if isinstance(self.device, str):
-            self.device = torch.device("cuda:0" if device in ("cuda", "hip") else device.replace("hip", "cuda"))
-        if isinstance(self.landmarks, str):
-            self.landmarks = parse_landmarks_file(self.landmarks)
 
         self._init_models()
         self._init_landmarks_target()
@@ -443,14 +439,12 @@ class Cropper:
             self.par_model = BiSeNet(self.attr_groups, self.mask_groups, self.batch_size)
             self.par_model.load(self.device, self.weights.get("bisenet"), self.precision)
             self.par_model.masks_on_device = self._encodes_on_device()
-        image = getattr(self, "background_image", None)
+        image = self.background_image
         self._pictures_dev = None if image is None else torch.from_numpy(image).to(self.device)
 
     def _has_background(self) -> bool:
-        """Whether a background mode is on: a fill or a cut-out, a blur, or pictures.  The newer attributes are absent on
-        a Cropper made with __new__."""
-        return (self.background is not None or getattr(self, "background_blur", None) is not None
-                or getattr(self, "background_image", None) is not None)
+        """Whether a background mode is on: a fill or a cut-out, a blur, or pictures."""
+        return self.background is not None or self.background_blur is not None or self.background_image is not None
 
     def _init_landmarks_target(self):
         if self.num_std_landmarks != 5:
@@ -507,9 +501,7 @@ class Cropper:
     def sharpness(self, crops: np.ndarray) -> np.ndarray:
         """The score ``min_sharpness`` is compared with, for crops one already has: (F,H,W,3) uint8 RGB -> (F,) float64
         variance of the Laplacian (``align.sharpness_score``)."""
-        crops = np.ascontiguousarray(crops)
-        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
-            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
+        crops = _u8_crops(crops)
         if crops.shape[0] == 0:
             return np.zeros(0, np.float64)
         with torch.cuda.device(self.device):
@@ -530,12 +522,10 @@ class Cropper:
         without it ``picks`` must be None."""
         if not self._has_background():
             raise ValueError("Cropper.matte needs a Cropper with background=..., background_blur=... or background_image=...")
-        crops, labels = np.ascontiguousarray(crops), np.ascontiguousarray(labels)
-        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
-            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
+        crops, labels = _u8_crops(crops), np.ascontiguousarray(labels)
         if labels.dtype != np.uint8 or labels.shape != crops.shape[:3]:
             raise ValueError(f"labels must be {crops.shape[:3]} uint8, not {labels.dtype} {labels.shape}")
-        image = getattr(self, "background_image", None)
+        image = self.background_image
         if image is None:
             if picks is not None:
                 raise ValueError("picks need a Cropper with background_image=...: a fill or a blur has no pictures to pick from")
@@ -561,21 +551,19 @@ class Cropper:
         ``refine`` is set, then the composite.  ``picks``: with ``background_image``, the picture of each crop (None:
         crop i over picture ``i % K``)."""
         bits = self.foreground_bits
-        subject, fill_holes = getattr(self, "subject", None), getattr(self, "fill_holes", None)
-        if subject is not None or fill_holes is not None:
-            labels_dev = matting.subject_mask(labels_dev, bits, subject is not None, fill_holes or 0)
+        if self.subject is not None or self.fill_holes is not None:
+            labels_dev = matting.subject_mask(labels_dev, bits, self.subject is not None, self.fill_holes or 0)
             bits = matting.SUBJECT_BITS
-        edge_shift = getattr(self, "edge_shift", None)         # absent on a Cropper made with __new__, like subject above
-        if edge_shift is not None:
-            labels_dev = matting.shift_mask(labels_dev, bits, edge_shift)
+        if self.edge_shift is not None:
+            labels_dev = matting.shift_mask(labels_dev, bits, self.edge_shift)
             bits = matting.SUBJECT_BITS
         refined = {}
-        if getattr(self, "refine", None) is not None:
+        if self.refine is not None:
             refined["alpha"] = matting.refine_alpha(crops_dev, labels_dev, bits, self.refine, self.refine_eps)
         if self.background_blur is not None:
             return matting.matte_blur(crops_dev, labels_dev, bits, self.feather, self.blur_taps, with_alpha=with_alpha, **refined)
-        taps = getattr(self, "decontaminate_taps", None)       # absent on a Cropper made with __new__, like refine above
-        if getattr(self, "background_image", None) is not None:                        # likewise
+        taps = self.decontaminate_taps
+        if self.background_image is not None:
             # the colour branch below, over the bank: the decontaminated composite reads an alpha plane, the plain one not
             bank = self._pictures_dev
             if picks is None:
@@ -592,53 +580,41 @@ class Cropper:
             return out, (alpha if with_alpha else None)
         return matting.matte(crops_dev, labels_dev, bits, self.feather, self.background, with_alpha=with_alpha, **refined)
 
+    def _filter_crops(self, crops, step) -> np.ndarray:
+        """One device step over crops one already has: (F,H,W,3) uint8 on the host -> what ``step`` makes of them on the
+        device, back on the host."""
+        crops = _u8_crops(crops)
+        if crops.shape[0] == 0:
+            return np.zeros(crops.shape, np.uint8)
+        with torch.cuda.device(self.device):
+            return step(torch.from_numpy(crops).to(self.device)).cpu().numpy()
+
     def equalize(self, crops: np.ndarray) -> np.ndarray:
         """What ``clahe`` does, for crops one already has: (F,H,W,3) uint8 RGB -> the equalised crops (F,H,W,3) uint8,
         with this Cropper's ``clahe`` / ``clahe_grid`` (``clahe.clahe``)."""
         if self.clahe is None:
             raise ValueError("Cropper.equalize needs a Cropper with clahe=...")
-        crops = np.ascontiguousarray(crops)
-        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
-            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
-        if crops.shape[0] == 0:
-            return np.zeros(crops.shape, np.uint8)
-        with torch.cuda.device(self.device):
-            return equalizing.clahe(torch.from_numpy(crops).to(self.device), self.clahe, self.clahe_grid).cpu().numpy()
+        return self._filter_crops(crops, lambda dev: equalizing.clahe(dev, self.clahe, self.clahe_grid))
 
     def remove_noise(self, crops: np.ndarray) -> np.ndarray:
         """What ``denoise`` does, for crops one already has: (F,H,W,3) uint8 RGB -> the denoised crops (F,H,W,3) uint8,
         at this Cropper's filter strength (``denoise.denoise``)."""
         if self.denoise is None:
             raise ValueError("Cropper.remove_noise needs a Cropper with denoise=...")
-        crops = np.ascontiguousarray(crops)
-        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
-            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
-        if crops.shape[0] == 0:
-            return np.zeros(crops.shape, np.uint8)
-        with torch.cuda.device(self.device):
-            return denoising.denoise(torch.from_numpy(crops).to(self.device), self.denoise).cpu().numpy()
+        return self._filter_crops(crops, lambda dev: denoising.denoise(dev, self.denoise))
 
     def unsharp(self, crops: np.ndarray) -> np.ndarray:
         """What ``sharpen`` does, for crops one already has: (F,H,W,3) uint8 RGB -> the sharpened crops (F,H,W,3) uint8,
         at this Cropper's amount, sigma and threshold (``sharpen.sharpen``)."""
-        if getattr(self, "sharpen", None) is None:
+        if self.sharpen is None:
             raise ValueError("Cropper.unsharp needs a Cropper with sharpen=...")
-        crops = np.ascontiguousarray(crops)
-        if crops.dtype != np.uint8 or crops.ndim != 4 or crops.shape[3] != 3:
-            raise ValueError(f"crops must be (F,H,W,3) uint8, not {crops.dtype} {crops.shape}")
-        if crops.shape[0] == 0:
-            return np.zeros(crops.shape, np.uint8)
-        with torch.cuda.device(self.device):
-            return sharpening.sharpen(torch.from_numpy(crops).to(self.device), self.sharpen, self.sharpen_sigma,
-                                      self.sharpen_threshold).cpu().numpy()
+        return self._filter_crops(crops, lambda dev: sharpening.sharpen(dev, self.sharpen, self.sharpen_sigma, self.sharpen_threshold))
 
     def encode_jpeg(self, crops: np.ndarray) -> list:
         """What ``encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F JPEG files as
         bytes, each equal to the file the host encoder writes for those pixels (``jpegenc.encode_jpeg``)."""
         from . import jpegenc
-        crops = np.ascontiguousarray(crops)
-        if crops.dtype != np.uint8 or not (crops.ndim == 3 or (crops.ndim == 4 and crops.shape[3] == 3)):
-            raise ValueError(f"crops must be (F,H,W,3) or (F,H,W) uint8, not {crops.dtype} {crops.shape}")
+        crops = _u8_crops(crops, gray=True)
         if crops.shape[0] == 0:
             return []
         with torch.cuda.device(self.device):
@@ -649,9 +625,7 @@ class Cropper:
         (F,H,W) uint8 -> F PNG files as bytes, each of which decodes to those pixels (``pngenc.encode_png``); not the host
         encoder's bytes."""
         from . import pngenc
-        crops = np.ascontiguousarray(crops)
-        if crops.dtype != np.uint8 or not (crops.ndim == 3 or (crops.ndim == 4 and crops.shape[3] in (3, 4))):
-            raise ValueError(f"crops must be (F,H,W,3), (F,H,W,4) or (F,H,W) uint8, not {crops.dtype} {crops.shape}")
+        crops = _u8_crops(crops, channels=(3, 4), gray=True)
         if crops.shape[0] == 0:
             return []
         with torch.cuda.device(self.device):
@@ -659,11 +633,11 @@ class Cropper:
 
     def _encodes_on_device(self) -> bool:
         """Whether some format is compressed on the GPU: then crops and masks stay there until they are saved."""
-        return self.encoder == "device" or getattr(self, "png_encoder", "host") == "device"
+        return self.encoder == "device" or self.png_encoder == "device"
 
     def _jpeg_kw(self) -> dict:
         """Keywords of ``jpegenc.encode_jpeg`` for this Cropper's settings; none at all for the defaults."""
-        jpeg = getattr(self, "jpeg", None)
+        jpeg = self.jpeg
         if jpeg is None or jpeg == JpegSettings():
             return {}
         return dict(quality=jpeg.quality, subsampling=jpeg.subsampling, optimize=jpeg.optimize)
@@ -693,16 +667,16 @@ class Cropper:
         MAX_PENDING_WRITES tasks are in flight: a slow disk stalls the GPU worker here instead of piling uint8
         crops up in host memory, and a failed write surfaces at the next batch, not at the end of the run."""
         # Locals: process_dir resets the attributes when it unwinds, while tasks of a failed run may still be in flight.
-        writer, writes, slots = getattr(self, "_io", None) or (None, None, None)      # ONE read: never a torn triple
+        writer, writes, slots = self._io or (None, None, None)      # ONE read: never a torn triple
         encoded = isinstance(pixels, bytes)
-        jpeg = getattr(self, "jpeg", None)
+        jpeg = self.jpeg
         # the defaults are the encoder table's own entry: the writers are called as they always were
         jpeg = {} if jpeg is None or jpeg == JpegSettings() else {"jpeg": jpeg}
         if writer is None:
             write_bytes(path, pixels) if encoded else write_image(path, pixels, **jpeg)
             return
         slots.acquire()
-        procs = getattr(self, "_io_procs_active", None)       # encode in the thread's worker process, or on the thread
+        procs = self._io_procs_active        # encode in the thread's worker process, or on the thread
 
         def task():
             try:
@@ -774,7 +748,7 @@ class Cropper:
         from . import jpegenc, pngenc
         none = np.zeros(len(names), bool)
         jpeg = self._is_jpeg_target(names) if self.encoder == "device" else none
-        png = self._is_png_target(names) if getattr(self, "png_encoder", "host") == "device" else none
+        png = self._is_png_target(names) if self.png_encoder == "device" else none
         out = [None] * len(names)
         for which, label, encode in ((jpeg, "fcp:jpeg", lambda rows: jpegenc.encode_jpeg(rows, **self._jpeg_kw())),
                                      (png, "fcp:png", pngenc.encode_png)):
@@ -793,7 +767,7 @@ class Cropper:
     # ------------------------------------------------------------- processing
     def _landmark_rows(self, table_names):
         """file name -> rows of the user's landmark table, built once per table (not per batch)."""
-        cached = getattr(self, "_rows_cache", None)
+        cached = self._rows_cache
         if cached is None or cached[0] is not table_names:
             rows_of = defaultdict(list)
             for row, name in enumerate(table_names):
@@ -807,133 +781,157 @@ class Cropper:
         images, file_names = read_images(file_names, input_dir)
         self._process_images(images, file_names, output_dir)
 
+    def _locate(self, images, file_names, pinned):
+        """Where the faces are.  Decoded images (host) and their names in -> (indices, landmarks, images_dev, paddings,
+        sources): the image of every face (a list), its five landmarks there ((F,5,2) on the host; None without alignment:
+        every image is one "face"), and what the detector path leaves: the resized batch on the device, its paddings on the
+        host and, with ``crop_source="original"``, the (blob, (N,3) table) of the decoded images on the device."""
+        landmarks = images_dev = paddings = sources = None
+        if self.landmarks is None and self.det_model is None:
+            indices = list(range(len(file_names)))              # one "face" per image, no alignment
+        elif self.landmarks is not None:
+            # user-supplied landmark sets (cropper.py:796-813): rows of the landmark table whose file name is in
+            # this batch, grouped by image in batch order; images without a row are dropped
+            table, table_names = self.landmarks
+            rows_of = self._landmark_rows(table_names)
+            pairs = [(i, row) for i, name in enumerate(file_names) for row in rows_of.get(str(name), ())]
+            indices = [i for i, _ in pairs]
+            landmarks = table[[row for _, row in pairs]]
+        else:
+            original = self.crop_source == "original"
+            with trace.range("fcp:build_batch"):
+                images_dev, _, paddings, *kept = build_batch(images, self.resize_size, "constant", self.device, pinned,
+                                                             keep_sources=original)
+            with trace.range("fcp:detect"):
+                landmarks, indices = self.det_model.predict(images_dev)
+            if original:
+                sources = kept[0]
+                if len(indices):
+                    landmarks = self._source_landmarks(images, paddings, indices, landmarks)
+            elif len(indices):
+                landmarks = landmarks - paddings[indices][:, None, [2, 0]].astype(np.float32)
+        if landmarks is not None and len(landmarks) > 0 and landmarks.shape[1] != self.num_std_landmarks:
+            slices = get_ldm_slices(self.num_std_landmarks, landmarks.shape[1])
+            landmarks = np.stack([landmarks[:, s].mean(1) for s in slices], 1)
+        return indices, landmarks, images_dev, paddings, sources
+
+    def _enhance(self, images, images_dev, landmarks, indices):
+        """The enhancer over the images whose faces pass its gate: the device batch in -> the enhanced batch out; without
+        one (given landmarks: a ragged list on the host) the enhanced images replace their entries of ``images``."""
+        with trace.range("fcp:enhance"):
+            if images_dev is not None:
+                return self.enh_model.predict(images_dev, landmarks, indices)
+            # ragged list (no detector): the reference hands the whole list to RRDBNet.predict (cropper.py:833-836), whose
+            # gate measures every image's faces against the area of images[0] (rrdb.py:124-140) and skips images that have no landmark set
+            todo = self.enh_model.gate(len(images), images[0].shape[0], images[0].shape[1], landmarks, indices)
+            for i in todo:
+                images[i] = self.enh_model.predict(torch.from_numpy(images[i]).to(self.device)[None], None, None)[0].cpu().numpy()
+        return None
+
+    def _align(self, images, images_dev, paddings, sources, indices, landmarks, pinned):
+        """Estimate + warp.  What ``_locate`` returned in -> (faces, faces_dev, indices): the crops on the host (None when
+        a device encoder will read them where they are), the same crops (F,oh,ow,3) u8 on the device, and the image of
+        every face that is left.  Without alignment the faces are the decoded images, on the host alone."""
+        if landmarks is None:
+            # no alignment: the decoded images themselves are the "faces".  Inside process_dir they may be views of a
+            # decode worker's shared-memory ring, which is recycled as soon as this call returns, while the encode
+            # tasks run later: they get their own copies
+            return ([np.array(im) for im in images] if pinned is not None else images), None, indices
+        original = self.crop_source == "original"
+        if not original and images_dev is None:          # given landmarks: a ragged list of images on the host
+            with trace.range("fcp:align"):
+                faces = self.crop_align(images, paddings, indices, landmarks)
+            return faces, (torch.from_numpy(faces).to(self.device) if len(faces) else None), indices
+        with trace.range("fcp:align"):
+            landmarks = np.ascontiguousarray(landmarks, dtype=np.float32)
+            if original:
+                if sources is None:          # given landmarks: the originals have not been uploaded yet
+                    sources = upload_sources(images, self.device, pinned)
+                crops_dev, ok, _, _ = align.crop_align_sources(
+                    *sources, indices, landmarks, self.landmarks_target, self.output_size, align.border_code(self.padding),
+                    self.allow_skew, self.warp_family, self.interpolation)
+            else:
+                crops_dev, ok = self._crop_align_device(images_dev, paddings, list(indices), torch.from_numpy(landmarks).to(self.device))
+        _, crops_dev, indices = self._keep(ok.cpu().numpy() != 0, None, crops_dev, indices)
+        return self._host_copy(crops_dev), crops_dev, indices
+
+    @staticmethod
+    def _keep(keep, faces, faces_dev, indices):
+        """Drop faces.  ``keep``: (F,) bool on the host -> the kept rows of ``faces`` (host, or None), of ``faces_dev``
+        (device) and of ``indices`` (a list), in their order."""
+        faces = None if faces is None else faces[keep]
+        return faces, faces_dev[torch.from_numpy(keep).to(faces_dev.device)], [i for i, k in zip(indices, keep) if k]
+
+    def _drop_blurry(self, faces, faces_dev, indices):
+        """``min_sharpness``: the crops (host and / or device) in -> ``_keep`` of those whose score reaches it."""
+        with trace.range("fcp:sharpness"):
+            if faces_dev is None:
+                faces_dev = torch.from_numpy(np.ascontiguousarray(faces)).to(self.device)
+            score = align.sharpness_score(align.sharpness_sums(faces_dev), faces_dev.shape[1] * faces_dev.shape[2])
+        return self._keep(score >= self.min_sharpness, faces, faces_dev, indices)
+
+    def _parse(self, faces, faces_dev):
+        """The face parser over the crops (device; host crops are uploaded one by one) -> (groups, labels): the
+        (attr_groups, mask_groups) pair ``save_groups`` takes and, when a background mode will use it, the label map
+        (F,oh,ow) u8 on the device behind them, else None."""
+        if faces_dev is None:
+            faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]
+        with trace.range("fcp:parse"):
+            if self._has_background() and isinstance(faces_dev, torch.Tensor):
+                # one parse per batch: the label map behind the groups is the one the matte uses
+                *groups, labels = self.par_model.predict(faces_dev, return_labels=True)
+                return tuple(groups), labels
+            return self.par_model.predict(faces_dev), None
+
+    def _finish_crops(self, faces_dev, labels, names, output_dir):
+        """What changes the pixels of a crop, after the parse, which saw the original crop: first the noise, then the
+        contrast, then the edges, over the whole crop, then the fill.  Crops (F,oh,ow,3) u8 and label map (or None), both
+        on the device, and the source file name of every face in -> the finished crops on the device: the very object that
+        came in when no step is switched on.  Nothing is read back here."""
+        if self.denoise is not None:
+            with trace.range("fcp:denoise"):
+                faces_dev = denoising.denoise(faces_dev, self.denoise)
+        if self.clahe is not None:
+            with trace.range("fcp:clahe"):
+                faces_dev = equalizing.clahe(faces_dev, self.clahe, self.clahe_grid)
+        if self.sharpen is not None:
+            with trace.range("fcp:sharpen"):
+                faces_dev = sharpening.sharpen(faces_dev, self.sharpen, self.sharpen_sigma, self.sharpen_threshold)
+        if labels is not None:
+            with trace.range("fcp:matte"):
+                more = {}
+                if self.background_image is not None:    # a face's picture comes from the name of its file in the output directory
+                    more["picks"] = matting.pick_pictures(self._target_paths(names, output_dir), len(self.background_image))
+                faces_dev, _ = self._matte_device(faces_dev, labels, **more)
+        return faces_dev
+
+    def _host_copy(self, pixels_dev):
+        """Device pixels -> their copy on the host, or None with a device encoder: the pixels stay where they are, and
+        what is read back is decided when they are saved."""
+        return None if self._encodes_on_device() else pixels_dev.cpu().numpy()
+
     @torch.no_grad()
     def _process_images(self, images, file_names, output_dir: str, pinned=None):
         """Everything of ``process_batch`` after the files have been decoded.  ``pinned``: per-image flags of arrays that
         live in page-locked memory (``build_batch`` uploads those without a staging copy)."""
         if len(images) == 0:
             return
-        paddings, landmarks, indices, images_dev = None, None, None, None
-        original = self.crop_source == "original"
-        sources = None                       # crop_source="original": (device blob, (N,3) table) of the decoded images
         with torch.cuda.device(self.device):
-            if self.landmarks is None and self.det_model is None:
-                indices = list(range(len(file_names)))              # one "face" per image, no alignment
-            elif self.landmarks is not None:
-                # user-supplied landmark sets (cropper.py:796-813): rows of the landmark table whose file name is in
-                # this batch, grouped by image in batch order; images without a row are dropped
-                table, table_names = self.landmarks
-                rows_of = self._landmark_rows(table_names)
-                pairs = [(i, row) for i, name in enumerate(file_names) for row in rows_of.get(str(name), ())]
-                indices = [i for i, _ in pairs]
-                landmarks = table[[row for _, row in pairs]]
-            else:
-                with trace.range("fcp:build_batch"):
-                    images_dev, _, paddings, *kept = build_batch(images, self.resize_size, "constant", self.device, pinned,
-                                                                 keep_sources=original)
-                with trace.range("fcp:detect"):
-                    lm_np, indices = self.det_model.predict(images_dev)
-                if original:
-                    sources = kept[0]
-                    landmarks = self._source_landmarks(images, paddings, indices, lm_np) if len(indices) else lm_np
-                else:
-                    landmarks = lm_np - paddings[indices][:, None, [2, 0]].astype(np.float32) if len(indices) else lm_np
-
+            indices, landmarks, images_dev, paddings, sources = self._locate(images, file_names, pinned)
             if landmarks is not None and len(landmarks) == 0:
                 return
-            if landmarks is not None and landmarks.shape[1] != self.num_std_landmarks:
-                slices = get_ldm_slices(self.num_std_landmarks, landmarks.shape[1])
-                landmarks = np.stack([landmarks[:, s].mean(1) for s in slices], 1)
-
             if self.enh_model is not None:
-                with trace.range("fcp:enhance"):
-                    if images_dev is not None:
-                        images_dev = self.enh_model.predict(images_dev, landmarks, indices)
-                    else:
-                        # ragged list (no detector): the reference hands the whole list to RRDBNet.predict
-                        # (cropper.py:833-836), whose gate measures every image's faces against the area of
-                        # images[0] (rrdb.py:124-140) and skips images that have no landmark set
-                        todo = self.enh_model.gate(len(images), images[0].shape[0], images[0].shape[1], landmarks, indices)
-                        for i in todo:
-                            images[i] = self.enh_model.predict(torch.from_numpy(images[i]).to(self.device)[None],
-                                                               None, None)[0].cpu().numpy()
-
-            groups = (None, None)
-            if landmarks is not None:
-                if original:
-                    with trace.range("fcp:align"):
-                        if sources is None:          # given landmarks: the originals have not been uploaded yet
-                            sources = upload_sources(images, self.device, pinned)
-                        crops_dev, ok, _, _ = align.crop_align_sources(
-                            *sources, indices, np.ascontiguousarray(landmarks, dtype=np.float32), self.landmarks_target,
-                            self.output_size, align.border_code(self.padding), self.allow_skew, self.warp_family,
-                            self.interpolation)
-                    keep = ok.cpu().numpy() != 0
-                    crops_dev = crops_dev[torch.from_numpy(keep).to(self.device)]
-                    indices = [i for i, k in zip(indices, keep) if k]
-                    # a device encoder: the pixels stay where they are; what is read back is decided when they are saved
-                    faces_dev, faces = crops_dev, (None if self._encodes_on_device() else crops_dev.cpu().numpy())
-                elif images_dev is not None:
-                    with trace.range("fcp:align"):
-                        crops_dev, ok = self._crop_align_device(
-                            images_dev, paddings, list(indices),
-                            torch.from_numpy(np.ascontiguousarray(landmarks, dtype=np.float32)).to(self.device))
-                    keep = ok.cpu().numpy() != 0
-                    crops_dev = crops_dev[torch.from_numpy(keep).to(self.device)]
-                    indices = [i for i, k in zip(indices, keep) if k]
-                    # a device encoder: the pixels stay where they are; what is read back is decided when they are saved
-                    faces_dev, faces = crops_dev, (None if self._encodes_on_device() else crops_dev.cpu().numpy())
-                else:
-                    with trace.range("fcp:align"):
-                        faces = self.crop_align(images, paddings, indices, landmarks)
-                    faces_dev = torch.from_numpy(faces).to(self.device) if len(faces) else None
-            else:
-                # no alignment: the decoded images themselves are the "faces".  Inside process_dir they may be views of a
-                # decode worker's shared-memory ring, which is recycled as soon as this call returns, while the encode
-                # tasks run later: they get their own copies
-                faces, faces_dev = ([np.array(im) for im in images] if pinned is not None else images), None
+                images_dev = self._enhance(images, images_dev, landmarks, indices)
+            faces, faces_dev, indices = self._align(images, images_dev, paddings, sources, indices, landmarks, pinned)
             if self.min_sharpness is not None and landmarks is not None and len(indices) > 0:
-                with trace.range("fcp:sharpness"):
-                    if faces_dev is None:
-                        faces_dev = torch.from_numpy(np.ascontiguousarray(faces)).to(self.device)
-                    score = align.sharpness_score(align.sharpness_sums(faces_dev), faces_dev.shape[1] * faces_dev.shape[2])
-                keep = score >= self.min_sharpness
-                faces, faces_dev = (None if faces is None else faces[keep]), faces_dev[torch.from_numpy(keep).to(self.device)]
-                indices = [i for i, k in zip(indices, keep) if k]
-            labels = None
+                faces, faces_dev, indices = self._drop_blurry(faces, faces_dev, indices)
+            groups, labels = (None, None), None
             if self.par_model is not None and len(indices) > 0:
-                if faces_dev is None:
-                    faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]
-                with trace.range("fcp:parse"):
-                    if self._has_background() and isinstance(faces_dev, torch.Tensor):
-                        # one parse per batch: the label map behind the groups is the one the matte uses
-                        *groups, labels = self.par_model.predict(faces_dev, return_labels=True)
-                        groups = tuple(groups)
-                    else:
-                        groups = self.par_model.predict(faces_dev)
-            denoise = getattr(self, "denoise", None)           # absent on a Cropper made with __new__
-            sharpen = getattr(self, "sharpen", None)           # likewise
-            if len(indices) > 0 and isinstance(faces_dev, torch.Tensor) and (denoise is not None or self.clahe is not None
-                                                                             or sharpen is not None or labels is not None):
-                # after the parse, which saw the original crop: first the noise, then the contrast, then the edges, over
-                # the whole crop, then the fill
-                if denoise is not None:
-                    with trace.range("fcp:denoise"):
-                        faces_dev = denoising.denoise(faces_dev, denoise)
-                if self.clahe is not None:
-                    with trace.range("fcp:clahe"):
-                        faces_dev = equalizing.clahe(faces_dev, self.clahe, self.clahe_grid)
-                if sharpen is not None:
-                    with trace.range("fcp:sharpen"):
-                        faces_dev = sharpening.sharpen(faces_dev, sharpen, self.sharpen_sigma, self.sharpen_threshold)
-                if labels is not None:
-                    with trace.range("fcp:matte"):
-                        image, more = getattr(self, "background_image", None), {}
-                        if image is not None:    # a face's picture comes from the name of its file in the output directory
-                            more["picks"] = matting.pick_pictures(self._target_paths(file_names[indices], output_dir), len(image))
-                        faces_dev, _ = self._matte_device(faces_dev, labels, **more)
-                # the host copy, if the host encoder needs one, is the denoised / equalised / sharpened / matted crop as well
-                faces = None if self._encodes_on_device() else faces_dev.cpu().numpy()
+                groups, labels = self._parse(faces, faces_dev)
+            if len(indices) > 0 and isinstance(faces_dev, torch.Tensor):
+                finished = self._finish_crops(faces_dev, labels, file_names[indices], output_dir)
+                if finished is not faces_dev:       # the host encoder's copy is the finished crop as well
+                    faces_dev, faces = finished, self._host_copy(finished)
             if self._encodes_on_device() and isinstance(faces_dev, torch.Tensor):
                 # aligned crops (and their masks): same size, on the device.  Faces and mask rows become lists that hold
                 # the encoded file of every target a device encoder takes, in the order save_groups indexes them
@@ -1108,7 +1106,7 @@ class Cropper:
             have.close()
         try:
             from ._io_pool import IOProcesses
-            kw = {} if getattr(self, "io_ring_mb", None) is None else {"ring_mb": int(self.io_ring_mb)}
+            kw = {} if self.io_ring_mb is None else {"ring_mb": int(self.io_ring_mb)}
             self._io_procs = IOProcesses(*want, register=self._pin_ring if os.environ.get("FCP_IO_PIN", "1") != "0" else None, **kw)
         except (ValueError, OSError) as e:           # no memfd / no processes left on this host: threads still work
             import warnings

@@ -261,7 +261,7 @@ def test_the_matte_step_shifts_after_the_subject_and_before_every_soft_edge(monk
     monkeypatch.setattr(M, "cutout", lambda crops, alpha, *a: calls.append(("cutout", alpha)) or "rgba")
     c = Cropper.__new__(Cropper)
     c.background, c.background_blur, c.foreground_bits, c.feather = (0, 0, 0), None, R.ONE_17, 5
-    assert not hasattr(c, "edge_shift")
+    assert "edge_shift" not in vars(c)
     assert c._matte_device("crops", "labels") == ("out", None)
     assert calls == [("matte", "labels", R.ONE_17)]                  # the attribute absent: nothing new is called
     del calls[:]

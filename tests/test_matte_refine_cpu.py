@@ -255,7 +255,7 @@ def test_init_models_works_without_the_new_attributes(monkeypatch):
     c.device, c.det_threshold, c.landmarks, c.enh_threshold = torch.device("cuda:0"), None, (None, None), None
     c.attr_groups, c.mask_groups, c.batch_size, c.weights, c.precision, c.encoder = None, None, 8, {}, None, "host"
     c.background, c.background_blur = None, None
-    assert not hasattr(c, "refine")
+    assert "refine" not in vars(c)
     c._init_models()
     assert c.par_model is None
 

@@ -259,7 +259,7 @@ def test_a_cropper_built_with_new_works_without_the_attributes(monkeypatch):
     monkeypatch.setattr(M, "refine_alpha", lambda crops, labels, bits, *a: calls.append(("refine", labels, bits)) or "alpha")
     c = Cropper.__new__(Cropper)
     c.background, c.background_blur, c.foreground_bits, c.feather = (0, 0, 0), None, R.ONE_17, 5
-    assert not hasattr(c, "subject") and not hasattr(c, "fill_holes") and not hasattr(c, "refine")
+    assert "subject" not in vars(c) and "fill_holes" not in vars(c) and "refine" not in vars(c)
     assert c._matte_device("crops", "labels") == ("out", None)
     assert calls == [("matte", "labels", R.ONE_17)]                  # nothing new runs, the labels and the bits go through
     del calls[:]
