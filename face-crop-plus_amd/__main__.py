@@ -110,6 +110,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="sigma of the unsharp mask's blur in output pixels, 0.5..16 (with --sharpen; default 1.5)")
     p.add_argument("-sht", "--sharpen-threshold", type=int, default=argparse.SUPPRESS,
                    help="differences of up to this many gray levels, 0..255, are left alone (with --sharpen; default 0)")
+    p.add_argument("-sk", "--smooth-skin", type=float, default=argparse.SUPPRESS,
+                   help="smooth the skin and nothing else: range strength, 1..64 gray levels (10 suits a portrait), of a "
+                        "bilateral filter over the pixels the face parser labels skin; by default the crops keep their skin")
+    p.add_argument("-sks", "--smooth-sigma", type=float, default=argparse.SUPPRESS,
+                   help="spatial sigma of the skin smoothing in output pixels, 0.5..8 (with --smooth-skin; default 3.0)")
+    p.add_argument("-ska", "--smooth-amount", type=float, default=argparse.SUPPRESS,
+                   help="how much of the smoothed skin replaces the crop's, 0.05..1 (with --smooth-skin; default 1.0)")
+    p.add_argument("-skc", "--skin-classes", type=json.loads, default=argparse.SUPPRESS,
+                   help="JSON list of the parser classes that count as skin (with --smooth-skin; default [1, 7, 8, 10, 14])")
     p.add_argument("-jq", "--jpeg-quality", type=int, default=argparse.SUPPRESS,
                    help="quality of the JPEG files written, 1..100 (default 95, cv2.imwrite's)")
     p.add_argument("-jss", "--jpeg-subsampling", type=str, default=argparse.SUPPRESS, choices=("4:4:4", "4:2:2", "4:2:0"),

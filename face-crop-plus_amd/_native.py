@@ -108,6 +108,7 @@ SIGNATURES = {
     "fcp_matte_image_u8": [_P, _P, _I, _I, _I, C.c_uint32, _I, _P, _I, _P, _P, _P, _P],
     "fcp_matte_image_alpha_u8": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
     "fcp_cutout_image_u8": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _L, _P],
+    "fcp_skin_smooth_u8": [_P, _P, _I, _I, _I, C.c_uint32, _P, _I, _P, _I, _P, _P],
 }
 EXPORTS = ["fcp_abi_version", "fcp_last_error", "fcp_retina_nms_workspace_bytes", "fcp_jpeg_workspace_bytes",
            "fcp_jpeg_workspace_bytes_ex", "fcp_matte_blur_workspace_bytes", "fcp_matte_refine_workspace_bytes",

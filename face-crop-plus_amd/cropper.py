@@ -20,6 +20,7 @@ from . import clahe as equalizing
 from . import denoise as denoising
 from . import matte as matting
 from . import sharpen as sharpening
+from . import skin as smoothing
 from ._io_codec import _ENCODER_KW, JpegSettings, check_jpeg_settings, write_bytes
 from .batch import batch_geometry, build_batch, upload_sources
 from .utils import get_ldm_slices, parse_landmarks_file, read_image, read_images, write_image
@@ -58,9 +59,10 @@ class Cropper:
     background = background_blur = background_image = background_fit = blur_taps = decontaminate = decontaminate_taps = None
     refine = refine_eps = subject = fill_holes = edge_shift = denoise = clahe = clahe_grid = None
     sharpen = sharpen_sigma = sharpen_threshold = min_sharpness = jpeg = io_ring_mb = None
+    smooth_skin = smooth_sigma = smooth_amount = skin_classes = None
     _io = _io_procs = _io_procs_active = _rows_cache = _pictures_dev = None
     png_encoder = encoder = "host"
-    foreground_bits = 0
+    foreground_bits = skin_bits = 0
 
     def __init__(
         self,
@@ -98,6 +100,10 @@ class Cropper:
         refine_eps: int | None = None,
         subject: str | None = None,
         fill_holes: int | None = None,
+        smooth_skin: float | None = None,
+        smooth_sigma: float | None = None,
+        smooth_amount: float | None = None,
+        skin_classes: list[int] | None = None,
         decontaminate: float | None = None,
         edge_shift: int | None = None,
         denoise: float | None = None,
@@ -263,6 +269,24 @@ class Cropper:
         colour stays exact.  It needs aligned crops like ``min_sharpness``; any ``output_size`` will do.
         ``sharpen_sigma`` or ``sharpen_threshold`` without ``sharpen`` raises ValueError.  None (the default) launches
         nothing.  ``Cropper.unsharp`` applies it to crops one already has.
+        ``smooth_skin``: smooth the skin and nothing else — the range strength S, in gray levels (a finite number 1..64;
+        10 suits a portrait), of a bilateral filter that the face parser guides: only pixels labelled as one of
+        ``skin_classes`` (BiSeNet indices; None: (1, 7, 8, 10, 14): skin, both ears, nose, neck) change, only such pixels
+        are averaged, and every other pixel of the crop stays byte-identical, so eyes, brows, lips and hair keep their
+        detail and their colour does not bleed into the cheek.  Gray differences well below S are averaged away,
+        differences well above S survive.  ``smooth_sigma`` (0.5..8 output pixels; None: 3.0) is the spatial sigma of the
+        window (the taps of ``background_blur``, radius 3..24), ``smooth_amount`` (0.05..1; None: 1.0) how much of the
+        smoothed skin replaces the crop's: below 1 some texture stays.  The effect ramps in over about three pixels from
+        the edge of the skin region (the shared feather of 7), so the jagged label boundary does not show as a seam.  It is
+        stated in integers and held byte for byte to a numpy reference (``skin.smooth``).  It
+        runs after ``min_sharpness`` and the parse, which both see the original crop (calibrated thresholds, label maps,
+        attribute groups and mask files are the same with and without it), after ``denoise``, so that grain is not
+        mistaken for texture worth keeping, and before ``clahe``, ``sharpen`` and the matte, which see the smoothed crop as
+        the guide of ``refine``, the background modes and both encoders do.  It creates the parser even without
+        ``attr_groups`` / ``mask_groups`` or a background mode (one parse per batch serves both), needs aligned crops
+        like ``min_sharpness``; any ``output_size`` will do.  ``smooth_sigma``, ``smooth_amount`` or ``skin_classes``
+        without ``smooth_skin`` raises ValueError.  None (the default) launches nothing.  ``Cropper.retouch`` applies it
+        to crops and label maps one already has.
         ``jpeg_quality`` (an int, 1..100; 95), ``jpeg_subsampling`` ("4:4:4", "4:2:2" or "4:2:0"; "4:2:0") and
         ``jpeg_optimize`` (per-file Huffman tables, Pillow's ``optimize=True``: smaller files, the same pixels; False):
         the settings of every JPEG file (.jpg / .jpeg / .jpe) this Cropper writes — aligned crops, the mask files of
@@ -374,6 +398,17 @@ class Cropper:
             needs_aligned("sharpen")
             self.sharpen_sigma = sharpening.check_sigma(sharpen_sigma)
             self.sharpen_threshold = sharpening.check_threshold(sharpen_threshold)
+        self.smooth_skin = smoothing.check_smooth_skin(smooth_skin)
+        if self.smooth_skin is None:
+            for name, value in (("smooth_sigma", smooth_sigma), ("smooth_amount", smooth_amount), ("skin_classes", skin_classes)):
+                if value is not None:
+                    raise ValueError(f"{name} needs smooth_skin: without it it would do nothing")
+        else:
+            needs_aligned("smooth_skin")
+            self.smooth_sigma = smoothing.check_sigma(smooth_sigma)
+            self.smooth_amount = smoothing.check_amount(smooth_amount)
+            self.skin_bits = smoothing.check_classes(skin_classes)
+            self.skin_classes = tuple(c for c in range(matting.NUM_CLASSES) if self.skin_bits >> c & 1)
         self.crop_source, self.interpolation, self.output_format = crop_source, interpolation, output_format
         self.face_factor, self.strategy, self.padding, self.allow_skew = face_factor, strategy, padding, allow_skew
         self.attr_groups, self.mask_groups = attr_groups, mask_groups
@@ -434,7 +469,7 @@ class Cropper:
             from .rrdb import RRDBNet
             self.enh_model = RRDBNet(self.enh_threshold)
             self.enh_model.load(self.device, self.weights.get("rrdb"), self.precision)
-        if self.attr_groups is not None or self.mask_groups is not None or self._has_background():
+        if self.attr_groups is not None or self.mask_groups is not None or self._needs_labels():
             from .bise import BiSeNet
             self.par_model = BiSeNet(self.attr_groups, self.mask_groups, self.batch_size)
             self.par_model.load(self.device, self.weights.get("bisenet"), self.precision)
@@ -445,6 +480,10 @@ class Cropper:
     def _has_background(self) -> bool:
         """Whether a background mode is on: a fill or a cut-out, a blur, or pictures."""
         return self.background is not None or self.background_blur is not None or self.background_image is not None
+
+    def _needs_labels(self) -> bool:
+        """Whether a finishing step reads the parser's label map: a background mode, or ``smooth_skin``."""
+        return self._has_background() or self.smooth_skin is not None
 
     def _init_landmarks_target(self):
         if self.num_std_landmarks != 5:
@@ -609,6 +648,25 @@ class Cropper:
         if self.sharpen is None:
             raise ValueError("Cropper.unsharp needs a Cropper with sharpen=...")
         return self._filter_crops(crops, lambda dev: sharpening.sharpen(dev, self.sharpen, self.sharpen_sigma, self.sharpen_threshold))
+
+    def retouch(self, crops: np.ndarray, labels: np.ndarray) -> np.ndarray:
+        """What ``smooth_skin`` does, for crops and label maps one already has: (F,H,W,3) uint8 RGB crops and (F,H,W)
+        uint8 labels -> the crops with the skin smoothed (F,H,W,3) uint8, at this Cropper's strength, sigma, amount and
+        skin classes (``skin.smooth``)."""
+        if self.smooth_skin is None:
+            raise ValueError("Cropper.retouch needs a Cropper with smooth_skin=...")
+        crops, labels = _u8_crops(crops), np.ascontiguousarray(labels)
+        if labels.dtype != np.uint8 or labels.shape != crops.shape[:3]:
+            raise ValueError(f"labels must be {crops.shape[:3]} uint8, not {labels.dtype} {labels.shape}")
+        if crops.size == 0:
+            return np.zeros(crops.shape, np.uint8)
+        with torch.cuda.device(self.device):
+            labels_dev = torch.from_numpy(labels).to(self.device)
+            return self._smooth_device(torch.from_numpy(crops).to(self.device), labels_dev).cpu().numpy()
+
+    def _smooth_device(self, crops_dev, labels_dev):
+        """The skin step on device tensors."""
+        return smoothing.smooth(crops_dev, labels_dev, self.smooth_skin, self.smooth_sigma, self.smooth_amount, self.skin_bits)
 
     def encode_jpeg(self, crops: np.ndarray) -> list:
         """What ``encoder="device"`` writes, for crops one already has: (F,H,W,3) or (F,H,W) uint8 -> F JPEG files as
@@ -872,25 +930,29 @@ class Cropper:
 
     def _parse(self, faces, faces_dev):
         """The face parser over the crops (device; host crops are uploaded one by one) -> (groups, labels): the
-        (attr_groups, mask_groups) pair ``save_groups`` takes and, when a background mode will use it, the label map
-        (F,oh,ow) u8 on the device behind them, else None."""
+        (attr_groups, mask_groups) pair ``save_groups`` takes and, when a background mode or ``smooth_skin`` will use it,
+        the label map (F,oh,ow) u8 on the device behind them, else None."""
         if faces_dev is None:
             faces_dev = [torch.from_numpy(np.ascontiguousarray(f)).to(self.device) for f in faces]
         with trace.range("fcp:parse"):
-            if self._has_background() and isinstance(faces_dev, torch.Tensor):
-                # one parse per batch: the label map behind the groups is the one the matte uses
+            if self._needs_labels() and isinstance(faces_dev, torch.Tensor):
+                # one parse per batch: the label map behind the groups is the one the skin step and the matte use
                 *groups, labels = self.par_model.predict(faces_dev, return_labels=True)
                 return tuple(groups), labels
             return self.par_model.predict(faces_dev), None
 
-    def _finish_crops(self, faces_dev, labels, names, output_dir):
+    def _finish_crops(self, faces_dev, labels, names, output_dir, skin_labels=None):
         """What changes the pixels of a crop, after the parse, which saw the original crop: first the noise, then the
-        contrast, then the edges, over the whole crop, then the fill.  Crops (F,oh,ow,3) u8 and label map (or None), both
-        on the device, and the source file name of every face in -> the finished crops on the device: the very object that
-        came in when no step is switched on.  Nothing is read back here."""
+        skin, then the contrast, then the edges, over the whole crop, then the fill.  Crops (F,oh,ow,3) u8, the label map
+        of the matte (or None: no matte) and that of the skin step (or None: no skin step), all on the device, and the
+        source file name of every face in -> the finished crops on the device: the very object that came in when no step
+        is switched on.  Nothing is read back here."""
         if self.denoise is not None:
             with trace.range("fcp:denoise"):
                 faces_dev = denoising.denoise(faces_dev, self.denoise)
+        if self.smooth_skin is not None and skin_labels is not None:
+            with trace.range("fcp:skin"):
+                faces_dev = self._smooth_device(faces_dev, skin_labels)
         if self.clahe is not None:
             with trace.range("fcp:clahe"):
                 faces_dev = equalizing.clahe(faces_dev, self.clahe, self.clahe_grid)
@@ -929,7 +991,8 @@ class Cropper:
             if self.par_model is not None and len(indices) > 0:
                 groups, labels = self._parse(faces, faces_dev)
             if len(indices) > 0 and isinstance(faces_dev, torch.Tensor):
-                finished = self._finish_crops(faces_dev, labels, file_names[indices], output_dir)
+                finished = self._finish_crops(faces_dev, labels if self._has_background() else None, file_names[indices], output_dir,
+                                              skin_labels=labels)
                 if finished is not faces_dev:       # the host encoder's copy is the finished crop as well
                     faces_dev, faces = finished, self._host_copy(finished)
             if self._encodes_on_device() and isinstance(faces_dev, torch.Tensor):

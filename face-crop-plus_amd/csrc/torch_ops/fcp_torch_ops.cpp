@@ -837,6 +837,36 @@ Tensor unsharp(const Tensor& crops, at::IntArrayRef taps, int64_t amount_q8, int
   return out;
 }
 
+// Crops (f,h,w,3) uint8 with the pixels their label maps (f,h,w) uint8 call skin smoothed by a bilateral filter over the
+// skin alone: taps t[0..radius] as integers, radius 3..24, the range table (256,) uint16 and the amount 1..256
+// (fcp_skin_smooth_u8).
+Tensor skin_smooth(const Tensor& crops, const Tensor& labels, int64_t class_bits, at::IntArrayRef taps, const Tensor& range_lut,
+                   int64_t amount_q8) {
+  dev(crops, "crops", at::kByte);
+  dev(labels, "labels", at::kByte);
+  dev(range_lut, "range_lut", at::kUInt16);
+  FCP_DEVICE_GUARD(crops);
+  int64_t f, h, w;
+  crops_and_plane(crops, labels, "labels", f, h, w);
+  TORCH_CHECK(range_lut.dim() == 1 && range_lut.numel() == 256 && range_lut.device() == crops.device(),
+              "range_lut (256,) uint16 on the device of crops");
+  TORCH_CHECK(class_bits >= 0 && class_bits <= (int64_t)UINT_MAX, "class_bits past 32 bits");
+  TORCH_CHECK(amount_q8 >= INT_MIN && amount_q8 <= INT_MAX, "amount_q8 past int");
+  const int64_t radius = (int64_t)taps.size() - 1;
+  TORCH_CHECK(radius >= 3 && radius <= 24, "skin_smooth: taps must be t[0..radius] with radius 3..24 (got ", taps.size(), " taps)");
+  uint16_t t16[25] = {};
+  for (int64_t k = 0; k <= radius; ++k) {
+    TORCH_CHECK(taps[k] >= 0 && taps[k] <= 65535, "skin_smooth: tap ", k, " past 16 bits");
+    t16[k] = (uint16_t)taps[k];
+  }
+  Tensor out = at::empty_like(crops);
+  ok(fcp_skin_smooth_u8(crops.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), (int)f, (int)h, (int)w, (uint32_t)class_bits, t16,
+                        (int)radius, static_cast<const uint16_t*>(range_lut.const_data_ptr()), (int)amount_q8,
+                        out.data_ptr<uint8_t>(), cur_stream()),
+     "fcp::skin_smooth");
+  return out;
+}
+
 Tensor bicubic_down4_round(const Tensor& x4) {
   dev(x4, "x4", at::kFloat);
   FCP_DEVICE_GUARD(x4);
@@ -918,6 +948,7 @@ TORCH_LIBRARY(fcp, m) {
         "-> (Tensor, Tensor)");
   m.def("matte_image_alpha(Tensor crops, Tensor alpha, Tensor pictures, Tensor picks) -> Tensor");
   m.def("cutout_image(Tensor crops, Tensor alpha, Tensor pictures, Tensor picks, int[] taps) -> Tensor");
+  m.def("skin_smooth(Tensor crops, Tensor labels, int class_bits, int[] taps, Tensor range_lut, int amount_q8) -> Tensor");
   m.def("bicubic_down4_round(Tensor x4) -> Tensor");
   m.def("parse_argmax_hist(Tensor logits, int ncls, int mid_h, int mid_w, int out_h, int out_w) -> (Tensor, Tensor)");
   // ABI the veneer was COMPILED against (struct layouts of include/fcp_hip.h) and the ABI of the libfcp_hip.so it is
@@ -962,6 +993,7 @@ TORCH_LIBRARY_IMPL(fcp, CUDA, m) {
   m.impl("matte_image", &matte_image);
   m.impl("matte_image_alpha", &matte_image_alpha);
   m.impl("cutout_image", &cutout_image);
+  m.impl("skin_smooth", &skin_smooth);
   m.impl("bicubic_down4_round", &bicubic_down4_round);
   m.impl("parse_argmax_hist", &parse_argmax_hist);
 }

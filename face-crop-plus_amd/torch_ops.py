@@ -61,4 +61,4 @@ OPS = ("conv2d", "conv2d_out", "bottleneck_chain", "retina_decode", "nms_select"
        "parse_argmax_hist", "warp_affine_u8_interp", "warp_affine_u8_interp_ragged", "crop_sharpness", "jpeg_encode", "matte", "clahe", "matte_blur",
        "jpeg_encode_ex", "jpeg_huffman_tables", "matte_refine", "matte_alpha", "matte_blur_alpha",
        "subject_mask", "png_encode", "png_huffman_lengths", "feather_alpha", "cutout", "mask_shift", "nlm_denoise", "unsharp",
-       "matte_image", "matte_image_alpha", "cutout_image")
+       "matte_image", "matte_image_alpha", "cutout_image", "skin_smooth")

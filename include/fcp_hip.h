@@ -946,6 +946,43 @@ int fcp_nlm_denoise_u8(const uint8_t* crops, int f, int h, int w, const uint16_t
 int fcp_unsharp_u8(const uint8_t* crops, int f, int h, int w, const uint16_t* taps, int radius, int amount_q8, int threshold,
                    uint8_t* out, fcp_stream_t stream);
 
+/* Parser-guided skin smoothing of crops (f,h,w,3) uint8 RGB from label maps
+ * (f,h,w) uint8, in integers: a bilateral filter that
+ * changes only pixels labelled skin, averages only over pixels labelled
+ * skin and leaves every other pixel byte-identical.  With the taps
+ * t[0..radius] of uint16 in HOST memory (matte.blur_taps makes those of a
+ * sigma; they travel in the kernel's argument block), the range table
+ * range_lut[0..255] of uint16 in DEVICE memory (skin.range_lut makes that of
+ * a strength) and ONE = 4096:
+ *   g(p)     = (9798 R + 19235 G + 3735 B + 16384) >> 15
+ *   m(p)     = 1 if l(p) < 32 and bit l(p) of class_bits is set, else 0;
+ *              m = 0 outside the crop (nothing is reflected: any h, w >= 1)
+ *   s(o)     = (t[|oy|] t[|ox|] + 2048) >> 12, o in [-radius, radius]^2
+ *   w(p,o)   = m(p + o) ((s(o) min(range_lut[|g(p + o) - g(p)|], ONE)
+ *              + 2048) >> 12)
+ *   W(p)     = sum over o of w(p,o)
+ *   b_c(p)   = (sum over o of w(p,o) c_c(p + o) + (W >> 1)) / W for c = R,
+ *              G, B, floor division; W == 0: b = c(p)
+ *   alpha(p) = the feather-7 alpha of fcp_matte_u8 for class_bits
+ *   e(p)     = max(0, 2 alpha(p) - 255);  E(p) = (e(p) amount_q8 + 128) >> 8
+ *   out_c(p) = (b_c E + c_c (255 - E) + 127) / 255 if m(p) == 1, else c_c(p)
+ * Every tap is at most ONE, so s <= ONE and w <= ONE for any table, and a
+ * window has at most 2401 positions: the numerators stay below 2^32,
+ * unsigned 32-bit sums, which commute, so the bytes do not depend on the
+ * tiling or the order of the offsets and are the same from run to run.
+ * amount_q8 = 256 replaces the skin by its mean inside the ramp e.
+ * One launch on `stream`, no workspace, no float and no atomics.  crops,
+ * labels and out may start at any byte; out must not overlap crops (out ==
+ * crops included: a pixel reads its window) or labels; nothing outside out
+ * is written.
+ * f < 0 or > 65535, h or w below 1 or above 8192, a bit of class_bits at or
+ * above 19, a radius outside 3..24, null taps, a tap above 4096 or an
+ * amount_q8 outside 1..256 fail with a "skin_smooth:" message; then f == 0
+ * is a no-op; then a null crops / labels / range_lut / out, a misaligned
+ * range_lut or overlapping arrays fail likewise, all before any HIP call. */
+int fcp_skin_smooth_u8(const uint8_t* crops, const uint8_t* labels, int f, int h, int w, uint32_t class_bits, const uint16_t* taps,
+                       int radius, const uint16_t* range_lut, int amount_q8, uint8_t* out, fcp_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * BiSeNet face parser glue (models/bise.py, _layers.py:206-368).
  * ------------------------------------------------------------------------ */
